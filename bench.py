@@ -45,6 +45,10 @@ SECONDARY = "sponza_like_1920x1080_256spp_envmap_is"
 SECONDARIES = [(SECONDARY, 3, 1, None),
                ("courtyard_like_10M_1920x1080_121spp", 2, 1, None),
                ("measured_like_3840x2160_529spp_rgl", 1, 1, 6)]
+# --dump-outputs: a frame of more pixels than this is written as a fixed, seeded sample of this many pixels, so that the
+# default line (the primary frame and three secondary ones) writes at most 4 x 12 MiB
+DUMP_MAX_PIXELS = 1 << 20
+DUMP_SEED = 1
 
 WORKLOADS = {
     # name: (builder kwargs, width, height, samples_sqrt)
@@ -172,6 +176,20 @@ def parity_of(gpu_frame, oracle_frame, start, pixels, width):
     rel = float(np.sqrt(((a.astype(np.float64) - b.astype(np.float64)) ** 2).sum()) / norm) if norm > 0 else 0.0
     return {"rows": "%d-%d" % (start // width, (start + pixels - 1) // width), "pixels": pixels, "values": int(a.size), "bits_differ": differ,
             "rel_l2": rel, "max_abs": float(np.abs(a - b).max()) if a.size else 0.0, "against": "oracle (CPU restatement), same seeds"}
+
+
+def dump_frame(out_dir, name, frame):
+    """--dump-outputs: the frame a render call left in `frame` (float32 [h, w, 3]) as out_dir/<name>.npy.  Up to
+    DUMP_MAX_PIXELS pixels the whole frame, [h, w, 3]; above that the pixels at DUMP_MAX_PIXELS positions drawn with
+    DUMP_SEED (the same positions every run for a frame of that size), in raster order, [DUMP_MAX_PIXELS, 3]."""
+    import numpy as np
+    a = np.ascontiguousarray(frame.cpu().numpy(), dtype=np.float32)
+    pixels = a.shape[0] * a.shape[1]
+    if pixels > DUMP_MAX_PIXELS:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, DUMP_MAX_PIXELS, replace=False))
+        a = a.reshape(pixels, 3)[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def load_pmc(name):
@@ -340,7 +358,12 @@ def main():
     ap.add_argument("--wide-walk", action="store_true", help="wpt_set_walk(WPT_WALK_WIDE): scenes fetched from HBM are walked over the tree collapsed by one level (experiments)")
     ap.add_argument("--triangles-as-given", action="store_true", help="wpt_set_walk(WPT_WALK_TRIANGLES_AS_GIVEN): triangle records stay in the caller's order (experiments)")
     ap.add_argument("--top-nodes", type=int, default=-1, help="BVH nodes stored level by level in front of the array (wpt_set_top_nodes; experiments)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of each workload's last timed step to DIR/<workload>.npy (float32; frames over "
+                         "%d pixels as a fixed, seeded sample of that many), for output-by-output comparison of two builds" % DUMP_MAX_PIXELS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # before anything initialises the HIP / HSA runtime: the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -429,6 +452,8 @@ def main():
     if not sharded:
         # ---- N = 1: one render call per step ----
         m, frame = measure_one_gpu(name, w, scene, dscene, args.steps, args.warmup, cpu_seconds, lib_id, torch, device, host, barrier, walk_flags, count_sqrt=args.count_sqrt or None)
+        if args.dump_outputs:
+            dump_frame(args.dump_outputs, name, frame)
         verified = None
         out = {
             "metric": "Msamples/s", "value": m["value"], "unit": "Msamples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -454,6 +479,8 @@ def main():
                 sd = device.DeviceScene(sscene)
                 sm, sframe = measure_one_gpu(sname, sw, sscene, sd, ssteps if sname0 != SECONDARY else args.secondary_steps, swarm, min(cpu_seconds, 8.0), lib_id,
                                              torch, device, host, walk_flags=walk_flags, count_sqrt=scount)
+                if args.dump_outputs:
+                    dump_frame(args.dump_outputs, sname, sframe)
                 sm.update(workload=sname, unit="Msamples/s", scene_build_s=t2,
                           config={"workload": sname, "width": sw["width"], "height": sw["height"], "spp": sw["samples_sqrt"] ** 2,
                                   "triangles": int(sscene.d.tri_count), "bvh_nodes": int(sscene.d.node_count), "parallelism": "1 launch"})
@@ -539,6 +566,8 @@ def main():
         elapsed = float(t.item())
 
     ok = bool(torch.isfinite(frame).all().item()) if rank == 0 else True
+    if args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, name, frame)  # rank 0 holds the reduced frame of the last step
     verified = None
     parity = None
     if (args.verify or (distributed and not args.no_verify)) and rank == 0:

@@ -34,6 +34,24 @@ def test_parity_field_counts_differing_values_bit_by_bit():
     assert bench.parity_of(a, b, 8, 24, 8)["bits_differ"] == 2
 
 
+def test_dumped_outputs_are_the_frame_or_the_same_seeded_sample_of_it(tmp_path):
+    import torch
+    small = torch.arange(6 * 8 * 3, dtype=torch.float32).reshape(6, 8, 3)
+    bench.dump_frame(str(tmp_path / "a"), "small", small)
+    got = np.load(str(tmp_path / "a" / "small.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    # above DUMP_MAX_PIXELS: that many distinct pixels in raster order, whole (all three channels), the same ones every time
+    h, w = 1100, 1000
+    big = torch.arange(h * w, dtype=torch.float32).repeat_interleave(3).reshape(h, w, 3)
+    big[:, :, 1] += 0.5
+    for d in ("a", "b"):
+        bench.dump_frame(str(tmp_path / d), "big", big)
+    a, b = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_PIXELS, 3) and np.array_equal(a, b)
+    assert (np.diff(a[:, 0]) > 0).all() and np.array_equal(a[:, 2], a[:, 0]) and np.array_equal(a[:, 1], a[:, 0] + 0.5)
+    assert a.nbytes * 4 <= 64 * 1024 * 1024      # the default line: the primary frame and three secondary ones
+
+
 def test_roofline_of_a_scene_in_lds_is_the_vector_one(monkeypatch):
     sc = host.cornell(64, 64, 1, 2)
     cnt = counters(1000, 7000, 170000, 21000, 12000, 3800)
