@@ -936,11 +936,12 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * reference's; measurements (wpt_set_walk): WPT_WALK_COUNT_PRODUCT makes them count what the product kernel walks,
      * WPT_WALK_FULL_SHADOW switches the short cut off everywhere. */
     args.shadowWalksEnd = (g_walk & WPT_WALK_FULL_SHADOW) ? 0u : (count ? ((g_walk & WPT_WALK_COUNT_PRODUCT) ? 1u : 0u) : 1u);
-    const size_t ldsBytes = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48;
+    const size_t sceneBytes = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48;
+    const size_t ldsBytes = sceneBytes + 32; /* the LDS copy: nodes, the null node, triangles */
     /* scheduler defaults from sweeps on the Cornell box (scene in LDS, short walks) and on the
      * Sponza-class scene (deep tree in HBM: traversal dominates, so long blocks may run with fewer
      * lanes and leaf tests earlier) */
-    const bool smallScene = ldsBytes <= LDS_SCENE_MAX_BYTES;
+    const bool smallScene = sceneBytes <= LDS_SCENE_MAX_BYTES;
     /* clamped: with more than 8 eighths the traversal block would leave before doing anything */
     args.leaveEighths = g_leaveEighths ? (g_leaveEighths > 8u ? 8u : g_leaveEighths) : (smallScene ? 1u : 3u);
     args.heavyMin = g_heavyMin ? g_heavyMin : (smallScene ? 16u : 8u);

@@ -158,6 +158,7 @@ template<uint32_t F, bool COUNT, bool LDSSCENE, int OCC, bool WIDE = false>
 __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 {
     static_assert(!WIDE || (!LDSSCENE && !COUNT), "the wide walk: product kernels that fetch the scene from HBM (counting launches walk like the reference)");
+    static_assert(!LDSSCENE || !(F & FEAT_SPHERES), "the LDS copy of the tree tells leaves (complemented word) from inner nodes by the sign bit: triangle leaves only");
     /* node prefetch: for scenes in HBM (Sponza-class frame 3 % faster); not from LDS, where the fetch is short and the
      * registers that hold the node ahead lengthen every step (Cornell 4 % slower) */
     constexpr bool PREFETCH = !LDSSCENE && !WIDE;
@@ -189,19 +190,33 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     const uint32_t nodeCount = sv.nodeCount;
 
     if (LDSSCENE) {
-        /* nodes (2 x float4 each) followed by the triangle positions (3 x float4 each) */
+        /* nodes (2 x float4 each), the null node, then the triangle positions (3 x float4 each).  The LDS copy of a node has
+         * the walk's own word 7 (ldsStep below): an inner node's first child as a plain index, a leaf's word complemented
+         * (>= 2^31), links clamped to nodeCount.  The null node (index nodeCount: skip and child both nodeCount) is where
+         * every lane that does not walk stands, so that a step leaves it where it is whatever its box test says. */
         const uint32_t n4 = 2 * nodeCount, t4 = 3 * sv.triCount;
-        for (uint32_t i = threadIdx.x; i < n4; i += WG)
-            ldsScene[i] = sv.nodes[i];
+        for (uint32_t i = threadIdx.x; i < n4; i += WG) {
+            float4 q = sv.nodes[i];
+            if (i & 1) {
+                const uint32_t skip = __float_as_uint(q.z), word = __float_as_uint(q.w);
+                q.z = __uint_as_float(skip < nodeCount ? skip : nodeCount);
+                const uint32_t child = word & NODE_INDEX_MASK;
+                q.w = __uint_as_float(word >= NODE_CHILD ? (child < nodeCount ? child : nodeCount) : ~word);
+            }
+            ldsScene[i] = q;
+        }
+        if (threadIdx.x < 2)
+            ldsScene[n4 + threadIdx.x] = threadIdx.x == 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f)
+                    : make_float4(0.0f, 0.0f, __uint_as_float(nodeCount), __uint_as_float(nodeCount));
         for (uint32_t i = threadIdx.x; i < t4; i += WG)
-            ldsScene[n4 + i] = sv.triGeom[i];
+            ldsScene[n4 + 2 + i] = sv.triGeom[i];
         if (args.materialsInLds) {
             /* the material record is what a hit's shading waits for first: fetched from LDS through a generic pointer */
             const uint32_t m4 = sv.materialCount * (uint32_t)(sizeof(wpt_material) / 16);
             const float4* from = reinterpret_cast<const float4*>(sv.materials);
             for (uint32_t i = threadIdx.x; i < m4; i += WG)
-                ldsScene[n4 + t4 + i] = from[i];
-            svInLds.materials = reinterpret_cast<const wpt_material*>(ldsScene + n4 + t4);
+                ldsScene[n4 + 2 + t4 + i] = from[i];
+            svInLds.materials = reinterpret_cast<const wpt_material*>(ldsScene + n4 + 2 + t4);
         }
     }
     __syncthreads();
@@ -213,7 +228,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     };
     auto tri4 = [&](uint32_t i) -> float4 {
         if constexpr (LDSSCENE)
-            return ldsScene[2 * nodeCount + i];
+            return ldsScene[2 * nodeCount + 2 + i];
         else
             return sv.triGeom[i];
     };
@@ -262,7 +277,9 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     int state = inBlock ? S_NEW : S_DONE;
     bool poolDry = false; /* wave-uniform */
     RayAux aux = rayAux(ps.d);
-    uint32_t node = 0, leafPrim = 0;
+    /* LDSSCENE: a lane that does not walk stands on the null node (index nodeCount), and a lane that waits for its leaf test
+     * keeps the leaf's index in leafNode (ldsStep below) */
+    uint32_t node = LDSSCENE ? nodeCount : 0u, leafPrim = 0, leafNode = 0;
     float amax = k_maxval;
     /* WIDE: the child whose turn is next (reference, entry distance) waits in registers, so that a step starts with its node's
      * fetch and not with a load from the stack; the others wait on the stack in the reference's order */
@@ -403,12 +420,30 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                     pn1 = node4(2 * node + 1);
                 }
             };
+            /* LDSSCENE: the same node step for every lane of the wave, in selects: no branch and no change of the exec mask.
+             * A lane that does not walk stands on the null node, whose child and skip link are itself, and stays there; a lane
+             * whose walk leaves the tree by a skip link arrives there too and keeps state NODE until the next look (below).  A lane
+             * that reaches a leaf goes to the null node as well and remembers the leaf; its test reads the leaf's word and skip
+             * link again.  Each walking lane performs the box test and the decisions of binaryStep on the same values. */
+            auto ldsStep = [&](auto nanCheck) {
+                const float4 n0 = node4(2 * node), n1 = node4(2 * node + 1);
+                const uint32_t skip = __float_as_uint(n1.z);
+                const uint32_t word = __float_as_uint(n1.w); /* the LDS copy's word: child index, or ~leaf word (>= 2^31) */
+                const bool hit = boxTest<decltype(nanCheck)::value>(nodeLo(n0, n1), nodeHi(n0, n1), ps.o, aux.inv, par.min_hit_distance, amax);
+                const bool toLeaf = hit && (int32_t)word < 0;
+                leafNode = toLeaf ? node : leafNode;
+                state = toLeaf ? (int)S_LEAF : state;
+                node = hit ? (toLeaf ? nodeCount : word) : skip;
+            };
             if (PREFETCH && state == S_NODE) {
                 pn0 = node4(2 * node);
                 pn1 = node4(2 * node + 1);
             }
             for (;;) {
                 sec<COUNT>(lc, SEC_LOOK_INNER);
+                /* LDSSCENE: a lane whose walk has left the tree in a node step takes its state after the walk here */
+                if (LDSSCENE && state == S_NODE && node >= nodeCount)
+                    state = endOfRayState();
                 const int nNode = __popcll(__ballot(state == S_NODE));
                 const int nLeaf = __popcll(__ballot(state == S_LEAF));
                 if (nNode + nLeaf < leaveBelow)
@@ -445,6 +480,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                          * it goes on (a leaf's subtree is the leaf itself) */
                         if (COUNT)
                             lc.leaves++;
+                        if constexpr (LDSSCENE) {
+                            /* the leaf ldsStep stopped at: its word (complemented in the LDS copy) and its skip link */
+                            const float4 n1 = node4(2 * leafNode + 1);
+                            leafPrim = ~__float_as_uint(n1.w);
+                            node = __float_as_uint(n1.z);
+                        }
                         Candidate c;
                         bool accepted;
                         if ((F & FEAT_SPHERES) && (leafPrim & PRIM_SPHERE)) {
@@ -482,6 +523,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                          * launches are given shadowWalksEnd = 0 and walk on, as the reference does: their numbers are its numbers.) */
                         if ((F & FEAT_ENVMAP) && args.shadowWalksEnd && accepted && ps.rayKind == RAY_NEE_ENV) {
                             state = S_NEEEND;
+                            if (LDSSCENE)
+                                node = nodeCount;
                         } else if (grown) {
                             aux.k |= RAY_WALK_BINARY;
                             node = 0;
@@ -552,6 +595,18 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                         if (__ballot(state == S_NODE && (aux.k & (RAY_MAY_NAN | RAY_WALK_BINARY))) != 0) {
                             if (state == S_NODE && (aux.k & (RAY_MAY_NAN | RAY_WALK_BINARY)))
                                 binaryStep();
+                        }
+                    } else if constexpr (LDSSCENE) {
+                        static_assert(!COUNT, "the LDS kernel has no counting build: ldsStep counts nothing");
+                        /* nanPossible is uniform and does not change within the block (no light-ray ends in this walk) */
+                        if (nanPossible) {
+#pragma unroll
+                            for (int step = 0; step < STEPS; step++)
+                                ldsStep(std::true_type());
+                        } else {
+#pragma unroll
+                            for (int step = 0; step < STEPS; step++)
+                                ldsStep(std::false_type());
                         }
                     } else {
 #pragma unroll
