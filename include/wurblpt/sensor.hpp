@@ -5,7 +5,11 @@
  */
 #pragma once
 
+#include <cmath>
 #include <limits>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "array.hpp"
 
@@ -42,6 +46,66 @@ public:
     virtual unsigned int height() const override { return _frame.dimension(1); }
     virtual ArrayContainer* pixelArray() override { return &_frame; }
     const Array<float>& result() const { return _frame; }
+};
+
+/* A transient film (light-in-flight rendering; a capability of this port, not of the reference): mcpt() renders the
+ * all-light frame and binCount() frames in one pass.  Bin k holds the light whose optical path length lies in
+ * [binEdges()[k], binEdges()[k + 1]), per channel, behind the distance-to-light gate; bin k is bit-identical to a SensorRGB
+ * render with minPathLen = edge k and maxPathLen = nextafterf(edge k + 1, -inf).  result() is the frame with the distance
+ * gate only.  The bins cost binCount() * width * height * 12 bytes. */
+class SensorRGBTransient final : public Sensor
+{
+private:
+    Array<float> _frame;
+    std::vector<float> _edges;
+    std::vector<Array<float>> _bins;
+
+    void init(unsigned int width, unsigned int height)
+    {
+        if (_edges.size() < 2)
+            throw std::invalid_argument("SensorRGBTransient: at least one bin");
+        for (size_t k = 0; k < _edges.size(); k++) {
+            const float e = _edges[k];
+            if (std::isnan(e) || (std::isinf(e) && !(k + 1 == _edges.size() && e > 0.0f)))
+                throw std::invalid_argument("SensorRGBTransient: bin edge " + std::to_string(k) + " is not finite (only the last may be +inf)");
+            if (k > 0 && !(e > _edges[k - 1]))
+                throw std::invalid_argument("SensorRGBTransient: bin edges must increase (edge " + std::to_string(k) + ")");
+        }
+        _bins.reserve(_edges.size() - 1);
+        for (size_t k = 0; k + 1 < _edges.size(); k++)
+            _bins.emplace_back(width, height, 3);
+    }
+
+public:
+    const float minDistToLight, maxDistToLight;
+
+    /* binCount bins of width binWidth from minPathLen: edge k = minPathLen + (float)k * binWidth, two float roundings */
+    SensorRGBTransient(unsigned int width, unsigned int height, float minPathLen, float binWidth, unsigned int binCount,
+            float minDistToLight = 0.0f, float maxDistToLight = std::numeric_limits<float>::max()) :
+        _frame(width, height, 3), minDistToLight(minDistToLight), maxDistToLight(maxDistToLight)
+    {
+        _edges.resize(size_t(binCount) + 1);
+        for (unsigned int k = 0; k <= binCount; k++) {
+            volatile float step = float(k) * binWidth; /* rounded on its own: no fused multiply-add */
+            _edges[k] = minPathLen + step;
+        }
+        init(width, height);
+    }
+    /* explicit edges: binCount + 1 increasing floats, all finite except that the last may be +inf */
+    SensorRGBTransient(unsigned int width, unsigned int height, const std::vector<float>& edges,
+            float minDistToLight = 0.0f, float maxDistToLight = std::numeric_limits<float>::max()) :
+        _frame(width, height, 3), _edges(edges), minDistToLight(minDistToLight), maxDistToLight(maxDistToLight)
+    {
+        init(width, height);
+    }
+    virtual unsigned int width() const override { return _frame.dimension(0); }
+    virtual unsigned int height() const override { return _frame.dimension(1); }
+    virtual ArrayContainer* pixelArray() override { return &_frame; }
+    unsigned int binCount() const { return _edges.size() - 1; }
+    const std::vector<float>& binEdges() const { return _edges; }
+    const Array<float>& result() const { return _frame; }
+    const Array<float>& bin(unsigned int k) const { return _bins.at(k); }
+    Array<float>& bin(unsigned int k) { return _bins.at(k); }
 };
 
 }

@@ -10,6 +10,7 @@
  */
 #pragma once
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -71,11 +72,18 @@ inline wpt_params makeParams(const Parameters& params, const SensorRGB& sensor)
     abort();
 }
 
+inline void mcptTransient(MPICoordinator& mpiCoordinator, SensorRGBTransient& sensor, const Camera& camera, const Scene& scene,
+        unsigned int samplesSqrt, float t0, float t1, const Parameters& params);
+
 inline void mcpt(MPICoordinator& mpiCoordinator, Sensor& sensor, const Camera& camera, const Scene& scene,
         unsigned int samplesSqrt, float t0 = 0.0f, float t1 = 0.0f, const Parameters& params = Parameters())
 {
     if (scene.bvhNeedsUpdate(t0, t1))
         mcptFatal("Scene::updateBVH(t0, t1) must run before mcpt()");
+    if (SensorRGBTransient* transient = dynamic_cast<SensorRGBTransient*>(&sensor)) {
+        mcptTransient(mpiCoordinator, *transient, camera, scene, samplesSqrt, t0, t1, params);
+        return;
+    }
     SensorRGB* rgb = dynamic_cast<SensorRGB*>(&sensor);
     if (!rgb)
         mcptFatal("only SensorRGB runs on the device path");
@@ -177,6 +185,119 @@ inline void mcpt(MPICoordinator& mpiCoordinator, Sensor& sensor, const Camera& c
     pixelArray->globalTagList().set("WURBLPT/DEVICE_COUNT", std::to_string(mpiCoordinator.devices().size()));
     pixelArray->globalTagList().set("WURBLPT/DEVICE_SECONDS",
             std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count()));
+}
+
+/* mcpt() for a SensorRGBTransient: the frame and every bin in one pass per block (wurblpt_hip.h: wpt_render_transient_block).
+ * Each worker renders the blocks it takes from the coordinator, several devices included, and writes their pixels of the frame
+ * and of every bin. */
+inline void mcptTransient(MPICoordinator& mpiCoordinator, SensorRGBTransient& sensor, const Camera& camera, const Scene& scene,
+        unsigned int samplesSqrt, float t0, float t1, const Parameters& params)
+{
+    wpt_camera cam;
+    if (!camera.describe(cam, t0))
+        mcptFatal("this camera cannot be described to the device path");
+    FlatScene flat;
+    std::string error;
+    if (!scene.flatten(flat, &error))
+        mcptFatal(error);
+    if (camera.animation) {
+        cam.animation = flat.addAnimation(camera.animation.get());
+        if (cam.animation < 0)
+            mcptFatal("only key frame animations (AnimationKeyframes) can go to the device");
+    }
+    const wpt_scene_desc desc = flat.desc();
+    SensorRGB gates(1, 1, sensor.minDistToLight, sensor.maxDistToLight); /* the frame: the distance gate only */
+    wpt_params p = makeParams(params, gates);
+    p.t0 = t0;
+    p.t1 = t1;
+    const unsigned int width = sensor.width();
+    const unsigned int height = sensor.height();
+    const unsigned int binCount = sensor.binCount();
+    const std::vector<float>& edges = sensor.binEdges();
+    ArrayContainer* pixelArray = sensor.pixelArray();
+
+    fprintf(stderr, "Number of hitables that are hot spots: %zu\n", scene.hotSpots().size());
+    fprintf(stderr, "Rendering %ux%u pixels with %u samples into the frame and %u path length bins.\n", width, height,
+            samplesSqrt * samplesSqrt, binCount);
+    if (wpt_device_count() <= 0)
+        mcptFatal(std::string("no HIP device: ") + wpt_last_error());
+
+    mpiCoordinator.init(width, height, static_cast<float*>(pixelArray->data()), pixelArray->componentCount());
+    std::vector<std::string> workerErrors(mpiCoordinator.devices().size());
+    const auto renderStart = std::chrono::steady_clock::now();
+    auto worker = [&](size_t w) {
+        int device = mpiCoordinator.devices()[w];
+        if (device >= 0 && wpt_select_device(device) != WPT_OK) {
+            workerErrors[w] = wpt_last_error();
+            return;
+        }
+        wpt_scene* dscene = nullptr;
+        if (wpt_scene_upload(&desc, &dscene) != WPT_OK) {
+            workerErrors[w] = wpt_last_error();
+            return;
+        }
+        std::vector<float> blockBins;
+        for (;;) {
+            unsigned int blockStart, blockSize;
+            mpiCoordinator.getBlock(&blockStart, &blockSize);
+            if (blockSize == 0)
+                break;
+            fprintf(stderr, "%s: device %d renders block of size %u starting at %u\n", mpiCoordinator.processId(), device, blockSize, blockStart);
+            blockBins.resize(size_t(binCount) * blockSize * 3);
+            if (wpt_render_transient_block(dscene, &cam, &p, edges.data(), binCount, width, height, samplesSqrt, blockStart, blockSize,
+                        mpiCoordinator.blockData(blockStart), blockBins.data()) != WPT_OK) {
+                workerErrors[w] = wpt_last_error();
+                break;
+            }
+            for (unsigned int k = 0; k < binCount; k++)
+                std::copy(blockBins.begin() + size_t(k) * blockSize * 3, blockBins.begin() + size_t(k + 1) * blockSize * 3,
+                        static_cast<float*>(sensor.bin(k).data()) + size_t(blockStart) * 3);
+            mpiCoordinator.submitBlock(blockStart, blockSize);
+        }
+        wpt_scene_free(dscene);
+    };
+    if (mpiCoordinator.devices().size() == 1) {
+        worker(0);
+    } else {
+        std::vector<std::thread> threads;
+        for (size_t w = 0; w < mpiCoordinator.devices().size(); w++)
+            threads.emplace_back(worker, w);
+        for (auto& t : threads)
+            t.join();
+    }
+    mpiCoordinator.finish();
+    for (const std::string& e : workerErrors)
+        if (!e.empty())
+            mcptFatal(e);
+
+    std::string deviceModel;
+    for (int device : mpiCoordinator.devices()) {
+        int current = device;
+        if (current < 0 && wpt_current_device(&current) != WPT_OK)
+            current = 0;
+        deviceModel += (deviceModel.empty() ? "" : "; ") + std::string(wpt_device_name(current));
+    }
+    const std::string seconds = std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count());
+    auto runTags = [&](ArrayContainer& a) {
+        a.globalTagList().set("WURBLPT/SAMPLES_PER_PIXEL", std::to_string(samplesSqrt * samplesSqrt));
+        a.globalTagList().set("WURBLPT/MAX_PATH_COMPONENTS", std::to_string(params.maxPathComponents));
+        a.globalTagList().set("WURBLPT/RUSSIAN_ROULETTE_THRESHOLD", std::to_string(params.rrThreshold));
+        a.globalTagList().set("WURBLPT/DEVICE_KERNEL", wpt_kernel_name());
+        a.globalTagList().set("WURBLPT/COMPILER", wpt_build_info());
+        a.globalTagList().set("WURBLPT/DEVICE_MODEL", deviceModel);
+        a.globalTagList().set("WURBLPT/DEVICE_COUNT", std::to_string(mpiCoordinator.devices().size()));
+        a.globalTagList().set("WURBLPT/DEVICE_SECONDS", seconds);
+    };
+    runTags(*pixelArray);
+    char edge[32];
+    for (unsigned int k = 0; k < binCount; k++) {
+        runTags(sensor.bin(k));
+        sensor.bin(k).globalTagList().set("WURBLPT/TRANSIENT_BIN", std::to_string(k));
+        snprintf(edge, sizeof(edge), "%.9g", edges[k]);
+        sensor.bin(k).globalTagList().set("WURBLPT/TRANSIENT_MIN_PATH_LEN", edge);
+        snprintf(edge, sizeof(edge), "%.9g", edges[k + 1]);
+        sensor.bin(k).globalTagList().set("WURBLPT/TRANSIENT_MAX_PATH_LEN", edge); /* exclusive */
+    }
 }
 
 inline void mcpt(Sensor& sensor, const Camera& camera, const Scene& scene, unsigned int samplesSqrt, float t0 = 0.0f,

@@ -359,6 +359,31 @@ wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera,
         const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt,
         uint32_t block_start, uint32_t block_size, float* block_rgb);
 
+/* ---- transient film (light-in-flight rendering) ----
+ * One launch renders the frame and bin_count planes: plane k holds the light whose optical path length lies in
+ * [edges[k], edges[k + 1]), per channel, behind the distance gate of `params` (its path-length gate applies to the frame
+ * only).  Plane k is bit-identical to the frame rendered with min_path_len = edges[k] and
+ * max_path_len = nextafterf(edges[k + 1], -INFINITY) (FLT_MAX for an infinite last edge); light outside
+ * [edges[0], edges[bin_count]) goes to no plane.  `edges_host`: bin_count + 1 increasing floats in host memory, all finite
+ * except that the last may be +INFINITY; 1 <= bin_count <= WPT_TRANSIENT_MAX_BINS.  A bad edge set is refused with
+ * WPT_ERR_INVALID_ARGUMENT before anything else is looked at.  The planes cost bin_count * width * height * 12 bytes. */
+#define WPT_TRANSIENT_MAX_BINS 4096u
+
+/* Asynchronous on `hip_stream`.  `frame_device` (may be NULL): the FULL frame as for wpt_render_block_device;
+ * `bins_device`: float[bin_count][height][width][3] in device memory, full frames, row 0 = bottom.  Only the block's
+ * pixels are written, in the frame and in every plane. */
+wpt_status wpt_render_transient_block_device(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const float* edges_host, uint32_t bin_count,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* frame_device, float* bins_device, void* hip_stream);
+
+/* Synchronous form with MPICoordinator::submitBlock semantics: `block_rgb` (may be NULL) receives block_size*3 floats,
+ * `block_bins` bin_count*block_size*3 floats (plane k's block_size*3 floats after plane k-1's), both in host memory. */
+wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const float* edges_host, uint32_t bin_count,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* block_rgb, float* block_bins);
+
 /* Waits for the device; WPT_ERR_HIP if a launch since the last call failed (the kernels have no waits that could run
  * out: every loop of theirs ends with its work). */
 wpt_status wpt_scene_check(wpt_scene* scene);

@@ -358,6 +358,74 @@ template<class PS> WPT_D void accumulateRadiance(const wpt_params& par, f3 opl, 
     ps.set3(SLOT_ACC, mk3(acc.x, acc.y, acc.z));
 }
 
+/* The transient film (FEAT_TRANSIENT kernels): binCount planes of float[3] per pixel; bin k takes the light whose optical
+ * path length lies in [edges[k], edges[k + 1]).  A lane owns its pixel for all its samples (pool and two passes included),
+ * so a plain read - add - write of the pixel's values in HBM keeps the order of its contributions and needs no atomics.
+ * Plane k, pixel `at`, channel c is bins[k * stride + 3 * at + c]; the launch zeroes the planes before and scales them by
+ * 1 / samples after (wpt_capi.hip), as finishPixel does with the frame's accumulator. */
+struct BinsView {
+    const float* edges;  /* binCount + 1 increasing floats in device memory; only the last may be +inf */
+    float* bins;
+    size_t stride;       /* floats from one plane to the next */
+    uint32_t binCount;
+    uint32_t width;      /* of the frame: a pixel's index is y * width + x */
+    float guessScale;    /* bins per unit of path length between the first and the last finite edge (0: no guess) */
+};
+
+/* the k with edges[k] <= x < edges[k + 1], or -1.  The guess from the uniform spacing is taken when the edges confirm it,
+ * otherwise a binary search over the edges decides: the answer is always the edge comparisons' */
+WPT_D int binOf(const BinsView& b, float x)
+{
+    const uint32_t K = b.binCount;
+    if (!(x >= b.edges[0] && x < b.edges[K]))
+        return -1;
+    const float g = __builtin_fminf((x - b.edges[0]) * b.guessScale, (float)(K - 1));
+    uint32_t k = (uint32_t)g; /* x - e0 >= 0 and a finite scale: g in [0, K - 1] */
+    if (!(b.edges[k] <= x && x < b.edges[k + 1])) {
+        uint32_t lo = 0, hi = K; /* edges[lo] <= x < edges[hi] */
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (b.edges[mid] <= x)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        k = lo;
+    }
+    return (int)k;
+}
+
+/* Sensor::accumulateRadiance of the launch: the frame's accumulator as above and, in FEAT_TRANSIENT kernels, the bins --
+ * behind the same distance gate, by each channel's own path length (the path-length gate of `par` is the frame's only).
+ * Where the three channels' lengths are equal (everything but dispersive glass) the bin is looked up once. */
+template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, const BinsView& bv, f3 opl, float distanceToLight, f4 radiance, PS& ps)
+{
+    accumulateRadiance(par, opl, distanceToLight, radiance, ps);
+    if constexpr ((F & FEAT_TRANSIENT) != 0) {
+        if (!(distanceToLight >= par.min_dist_to_light && distanceToLight <= par.max_dist_to_light))
+            return;
+        const uint32_t pxy = ps.getW(SLOT_SRDIR);
+        float* const px = bv.bins + 3 * ((size_t)(pxy >> 16) * bv.width + (pxy & 0xffffu));
+        const int kx = binOf(bv, opl.x);
+        if (opl.y == opl.x && opl.z == opl.x) {
+            if (kx >= 0) {
+                float* const p = px + (size_t)kx * bv.stride;
+                p[0] += radiance.x;
+                p[1] += radiance.y;
+                p[2] += radiance.z;
+            }
+        } else {
+            const int ky = binOf(bv, opl.y), kz = binOf(bv, opl.z);
+            if (kx >= 0)
+                px[(size_t)kx * bv.stride] += radiance.x;
+            if (ky >= 0)
+                px[(size_t)ky * bv.stride + 1] += radiance.y;
+            if (kz >= 0)
+                px[(size_t)kz * bv.stride + 2] += radiance.z;
+        }
+    }
+}
+
 /* wurblpt.hpp:254-273: continue along the scattered direction (ps.o already is the hit position, the ray's
  * refractive index the one to continue with), Russian roulette.  nextAtt / srDir / pathComponent are the
  * path's values, handed over by the caller who has them at hand; prng is the caller's copy of the generator
@@ -485,14 +553,15 @@ WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
  * What that needs of THIS hit -- the factor and the chosen hot spot (SLOT_NEE), the optical path length and the refractive index --
  * waits in the two slots the single kernel uses for the continuation (SLOT_NEXTATT, SLOT_SRDIR x y z), which are free here. */
 template<uint32_t F, bool COUNT, class Tri4, class PS, bool MERGED = false>
-WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& ps, const Candidate& best, LaneCounters& lc, int waitBelow = 0)
+WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& ps, const Candidate& best, LaneCounters& lc, int waitBelow = 0,
+        const BinsView& bins = BinsView{})
 {
     const bool haveEnv = (F & FEAT_ENVMAP) && sv.envType != WPT_ENV_NONE;
     sec<COUNT>(lc, SEC_MISS, best.prim == NO_HIT);
     if (best.prim == NO_HIT) {
         if (haveEnv) {
             f4 rad = mul(ps.get4(SLOT_ATT), envL(sv, ps.d));
-            accumulateRadiance(par, mk3(k_maxval, k_maxval, k_maxval), k_maxval, rad, ps);
+            accumulate<F>(par, bins, mk3(k_maxval, k_maxval, k_maxval), k_maxval, rad, ps);
         }
         return NEXT_NEW;
     }
@@ -518,7 +587,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
     const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
-    if ((F & ~(FEAT_GGX | FEAT_GLASS)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
+    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
          * once (nothing has been written yet): the next round then runs it for two rounds' worth
@@ -564,7 +633,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     const f4 att = ps.get4(SLOT_ATT);
     {
         f4 rad = mul(att, materialEmitted<F>(sv, m, h));
-        accumulateRadiance(par, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps);
+        accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps);
     }
     section(2);
     if (sr.type == SCATTER_NONE) {
@@ -685,7 +754,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
 /* the next-event ray's result (wurblpt.hpp:208-218: only the CHOSEN hot spot as nearest hit
  * counts; :240-250: the environment counts if nothing was hit), then the path continues */
 template<uint32_t F, class Tri4, class PS>
-WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& ps, const Candidate& best)
+WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& ps, const Candidate& best, const BinsView& bins = BinsView{})
 {
     const Slot oplSlot = ps.get(SLOT_OPL);
     if (ps.rayKind == RAY_NEE_LIGHT) {
@@ -696,13 +765,13 @@ WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS&
             f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh));
             const f4 ri = ps.get4(SLOT_RI);
             f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, mk3(ri.x, ri.y, ri.z)));
-            accumulateRadiance(par, oplLight, lh.a, rad, ps);
+            accumulate<F>(par, bins, oplLight, lh.a, rad, ps);
         }
     } else if (F & FEAT_ENVMAP) {
         if (best.prim == NO_HIT) {
             const Slot nee = ps.get(SLOT_NEE);
             f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), envL(sv, ps.d));
-            accumulateRadiance(par, mk3(k_maxval, k_maxval, k_maxval), k_maxval, rad, ps);
+            accumulate<F>(par, bins, mk3(k_maxval, k_maxval, k_maxval), k_maxval, rad, ps);
         }
     }
     const f4 nextAtt = ps.get4(SLOT_NEXTATT);

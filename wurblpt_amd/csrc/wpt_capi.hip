@@ -882,9 +882,9 @@ wpt_status wpt_scene_get_envmap_tables(const wpt_scene* scene, float* M, int32_t
 static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         uint32_t band_pixels, uint32_t band_first, uint32_t band_stride,
-        float* frame_device, wpt_counters* counters_device, void* hip_stream)
+        float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr)
 {
-    if (!scene || !camera || !params || !frame_device)
+    if (!scene || !camera || !params || !(frame_device || transient))
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
         return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
@@ -911,6 +911,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.frame = frame_device;
     args.counters = counters_device;
     args.schedStats = g_schedStats;
+    args.bins = transient ? *transient : wptk::BinsView{};
     args.fuse = (g_variant & 0x20u) ? 0u : 1u; /* variant bit 0x20: separate SHADE / NEE-END / NEW rounds (the older scheduler) */
 
     /* a wave covers an 8x8 pixel tile when the block consists of whole groups of 8 rows */
@@ -959,7 +960,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * number of streams never share one. */
     /* Wavefront form (wpt_wavefront.inc.h): trace and shade as two kernels that hand rays through HBM.  Not for counting
      * launches and moving scenes (those instantiations exist for the single kernel only). */
-    const bool wfExists = !count && !anim;
+    const bool wfExists = !count && !anim && !transient; /* (a transient film is always rendered by the single kernel) */
     /* The library's own choice (measured): launches of 2^21 lanes and more whose scene has measured BRDFs --
      * long shading that pays for being sorted by kind of material, and enough lanes to fill the trace and the shade kernel one
      * after the other (tools/wf_threshold_probe.py, 16 spp, single kernel / wavefront: 115.5 / 100.7 Msamples/s at 2^20 lanes,
@@ -1007,10 +1008,26 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.orderCount = nullptr;
     /* the wide walk where the scene has that form (wpt_set_walk before the upload): product launches of the kernels that fetch
      * the scene from HBM; counting launches and moving scenes walk the binary tree */
-    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds); /* (the kernel with the scene in LDS walks the binary tree) */
+    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient; /* (the kernel with the scene in LDS walks the binary tree) */
     g_kernelName.store(wide ? "wpt_pathtrace, wide walk" : nullptr, std::memory_order_relaxed);
+    /* the transient film: the LDS kernel for the Cornell class, the all-features kernel for other scenes at rest, the moving-scene
+     * kernels for moving scenes and for measured BRDFs */
+    const bool transientLds = transient && basic && lds && !anim && !rgl;
+    if (transient)
+        g_kernelName.store(transientLds ? "wpt_pathtrace, transient, scene in LDS"
+                : rgl ? "wpt_pathtrace, transient, measured BRDFs"
+                : anim ? "wpt_pathtrace, transient, all features, moving scenes" : "wpt_pathtrace, transient, all features", std::memory_order_relaxed);
     auto launch = [&](const wptk::KernelArgs& a) {
-        if (anim) {
+        if (transient) {
+            if (transientLds)
+                launchBasicLdsTransient(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+            else if (rgl)
+                launchFullRglAnimTransient(a, grid, stream);
+            else if (anim)
+                launchFullAnimTransient(a, grid, stream);
+            else
+                launchFullTransient(a, grid, stream);
+        } else if (anim) {
             /* its own instantiation, like the measured BRDFs */
             if (need & FEAT_RGL) {
                 if (count)
@@ -1163,6 +1180,144 @@ wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera, const wp
             st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
     }
     (void)hipFree(dBlock);
+    return st;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* the transient film's planes after the launch: plane value = 1 / samples * accumulated value (SensorRGB::finishPixel) for the
+ * block's pixels of every plane */
+__global__ void wpt_transient_finish_kernel(float* bins, size_t stride, uint32_t blockStart, uint32_t blockSize, uint32_t binCount, float invSamples)
+{
+    const uint64_t perPlane = uint64_t(blockSize) * 3, n = perPlane * binCount;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        float* p = bins + (i / perPlane) * stride + size_t(blockStart) * 3 + i % perPlane;
+        *p = invSamples * *p;
+    }
+}
+
+/* refuses a bad edge set; fills what the kernels need of a good one but the device copy of the edges */
+wpt_status transientEdges(const float* edges, uint32_t binCount, wptk::BinsView& bv)
+{
+    if (!edges)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "transient film: bin edges are NULL");
+    if (binCount == 0 || binCount > WPT_TRANSIENT_MAX_BINS)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "transient film: bin count must lie in 1 .. " + std::to_string(WPT_TRANSIENT_MAX_BINS));
+    for (uint32_t k = 0; k <= binCount; k++) {
+        if (std::isnan(edges[k]))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "transient film: bin edge " + std::to_string(k) + " is NaN");
+        if (std::isinf(edges[k]) && !(k == binCount && edges[k] > 0.0f))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "transient film: bin edge " + std::to_string(k) + " is infinite (only the last may be +inf)");
+        if (k > 0 && !(edges[k] > edges[k - 1]))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "transient film: bin edges must increase (edge " + std::to_string(k) + ")");
+    }
+    /* the kernels' first guess of a bin: uniform spacing between the first and the last finite edge */
+    const uint32_t lastFinite = std::isinf(edges[binCount]) ? binCount - 1 : binCount;
+    float scale = lastFinite > 0 ? float(lastFinite) / (edges[lastFinite] - edges[0]) : 0.0f;
+    bv = wptk::BinsView{};
+    bv.binCount = binCount;
+    bv.guessScale = std::isfinite(scale) ? scale : 0.0f;
+    return WPT_OK;
+}
+
+/* one transient launch: the planes' block is zeroed, rendered into and scaled, all in stream order; `bins` is plane 0's
+ * pixel 0 with `stride` floats between planes (a full frame's, or a block's behind a biased pointer) */
+wpt_status transientLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const float* edges, uint32_t binCount,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* frame, float* bins,
+        size_t stride, hipStream_t stream)
+{
+    wptk::BinsView bv;
+    const wpt_status checked = transientEdges(edges, binCount, bv);
+    if (checked != WPT_OK)
+        return checked;
+    if (!scene || !camera || !params || !bins)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
+    if (uint64_t(width) * height > 0xffffffffull || uint64_t(block_start) + block_size > uint64_t(width) * height)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
+    if (block_size == 0)
+        return WPT_OK;
+    float* dEdges = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dEdges), (size_t(binCount) + 1) * sizeof(float), stream));
+    hipError_t e = hipMemcpyAsync(dEdges, edges, (size_t(binCount) + 1) * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess)
+        e = hipMemset2DAsync(bins + size_t(block_start) * 3, stride * sizeof(float), 0, size_t(block_size) * 3 * sizeof(float), binCount, stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(dEdges, stream);
+        return fail(WPT_ERR_HIP, std::string("transient film: ") + hipGetErrorString(e));
+    }
+    bv.edges = dEdges;
+    bv.bins = bins;
+    bv.stride = stride;
+    bv.width = width;
+    wpt_status st = renderLaunch(scene, camera, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0, frame, nullptr,
+            stream, &bv);
+    if (st == WPT_OK) {
+        const uint64_t n = uint64_t(block_size) * 3 * binCount;
+        const uint32_t blocks = uint32_t(std::min<uint64_t>((n + 255) / 256, 65536));
+        hipLaunchKernelGGL(wpt_transient_finish_kernel, dim3(blocks), dim3(256), 0, stream, bins, stride, block_start, block_size, binCount,
+                1.0f / float(samples_sqrt * samples_sqrt));
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("transient film: ") + hipGetErrorString(e));
+    }
+    (void)hipFreeAsync(dEdges, stream);
+    return st;
+}
+
+} /* namespace */
+
+extern "C" {
+
+wpt_status wpt_render_transient_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
+        uint32_t block_size, float* frame_device, float* bins_device, void* hip_stream)
+{
+    return transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
+            frame_device, bins_device, size_t(width) * height * 3, static_cast<hipStream_t>(hip_stream));
+}
+
+wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
+        uint32_t block_size, float* block_rgb, float* block_bins)
+{
+    wptk::BinsView bv;
+    const wpt_status checked = transientEdges(edges_host, bin_count, bv);
+    if (checked != WPT_OK)
+        return checked;
+    if (!block_bins)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "block_bins is NULL");
+    if (block_size == 0)
+        return WPT_OK;
+    /* device memory for the block only, behind pointers biased so that pixel `block_start` lands at offset 0 */
+    const size_t blockFloats = size_t(block_size) * 3;
+    float *dBlock = nullptr, *dBins = nullptr;
+    if (block_rgb)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), blockFloats * sizeof(float)));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBins), blockFloats * bin_count * sizeof(float));
+    wpt_status st = e == hipSuccess ? WPT_OK : fail(WPT_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (st == WPT_OK)
+        st = transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
+                dBlock ? dBlock - size_t(block_start) * 3 : nullptr, dBins - size_t(block_start) * 3, blockFloats, nullptr);
+    if (st == WPT_OK)
+        st = wpt_scene_check(scene);
+    if (st == WPT_OK && block_rgb) {
+        e = hipMemcpy(block_rgb, dBlock, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    if (st == WPT_OK) {
+        e = hipMemcpy(block_bins, dBins, blockFloats * bin_count * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    if (dBlock)
+        (void)hipFree(dBlock);
+    if (dBins)
+        (void)hipFree(dBins);
     return st;
 }
 

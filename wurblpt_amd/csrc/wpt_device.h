@@ -454,7 +454,8 @@ enum {
     FEAT_GLASS = 64,     /* MaterialGlass, MaterialMirror */
     FEAT_SPHERES = 128,  /* HitableSphere leaves and sphere hot spots */
     FEAT_RGL = 256,      /* MaterialRGL, measured BRDFs (wpt_rgl.h) */
-    FEAT_ANIM = 512      /* exposure interval t0 != t1 and / or animated instances (wpt_anim.h) */
+    FEAT_ANIM = 512,     /* exposure interval t0 != t1 and / or animated instances (wpt_anim.h) */
+    FEAT_TRANSIENT = 1024 /* transient film: contributions are also binned by optical path length (wpt_blocks.h, BinsView) */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */

@@ -1,0 +1,13 @@
+/* wpt_k_basic_lds_transient.hip -- instantiates wpt_pathtrace<FEAT_BASIC | FEAT_TRANSIENT, false, true>: the transient film for
+ * scenes of the basic feature set small enough for LDS (the Cornell class) */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchBasicLdsTransient(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream)
+{
+    launchMaybePooled(wpt_pathtrace<FEAT_BASIC | FEAT_TRANSIENT, false, true, 4>, args, grid, COLD_BYTES + sceneLdsBytes, stream);
+}
+
+}

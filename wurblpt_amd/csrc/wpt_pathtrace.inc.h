@@ -100,6 +100,7 @@ struct KernelArgs {
     uint32_t materialsInLds; /* scene in LDS: the material records are there too */
     wpt_counters* counters;
     unsigned long long* schedStats; /* COUNT builds: 16 scheduler statistics, or NULL */
+    BinsView bins; /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there) */
 };
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
@@ -455,7 +456,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                     const int nNee = __popcll(__ballot(state == S_NEEEND));
                     if (nNee >= NEE_IN_WALK) {
                         if (state == S_NEEEND)
-                            afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best));
+                            afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best, args.bins));
                         if (state == S_START) {
                             beginRay();
                             if (PREFETCH) {
@@ -628,7 +629,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                 sched[6] += cShade;
             }
             if (state == S_SHADE) /* tracePath, one path component (wurblpt.hpp:131-252) */
-                afterBlock(blockShade<F, COUNT>(sv, par, tri4, ps, best, lc, cTrav != 0 ? (int)args.waitBelow : 0));
+                afterBlock(blockShade<F, COUNT>(sv, par, tri4, ps, best, lc, cTrav != 0 ? (int)args.waitBelow : 0, args.bins));
             if (COUNT)
                 sched[12] += (unsigned long long)(clock64() - tBlock);
         }
@@ -641,7 +642,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             sec<COUNT>(lc, SEC_NEE_END, state == S_NEEEND);
             sec<COUNT>(lc, SEC_NEE_END_LIGHT, state == S_NEEEND && ps.rayKind == RAY_NEE_LIGHT && best.prim == ps.getW(SLOT_NEE));
             if (state == S_NEEEND) /* the next-event ray's contribution, then the path continues */
-                afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best));
+                afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best, args.bins));
             if (COUNT)
                 sched[13] += (unsigned long long)(clock64() - tBlock);
         }
@@ -664,7 +665,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                         args.carry[2 * at] = ps.base[SLOT_PRNG * WG];
                         args.carry[2 * at + 1] = ps.base[SLOT_ACC * WG];
                         args.cost[at] = (uint32_t)clock64() - args.cost[at];
-                    } else {
+                    } else if (!(F & FEAT_TRANSIENT) || args.frame) {
                         /* SensorRGB::finishPixel (sensor_rgb.hpp:82-87) */
                         const Slot acc = ps.get(SLOT_ACC);
                         float* out = args.frame + 3 * at;
@@ -765,6 +766,11 @@ void launchFullAnim(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullAnimCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnim(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnimCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* the transient film (FEAT_TRANSIENT, args.bins): Cornell class with the scene in LDS, all features (at rest, moving), measured BRDFs */
+void launchBasicLdsTransient(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchFullTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullRglAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
 
 } /* namespace wptk */
 

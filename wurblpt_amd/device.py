@@ -21,7 +21,8 @@ WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN = 1, 2,
 EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_scene_upload", "wpt_scene_free", "wpt_scene_check",
            "wpt_postproc_to_srgb", "wpt_postproc_max_luminance", "wpt_postproc_uniform_rational_quantization",
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
-           "wpt_render_block_device", "wpt_render_block", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_block_device", "wpt_render_block",
+           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -53,6 +54,11 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params),
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.wpt_render_transient_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
+                                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wpt_render_transient_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
+                                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
         L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.wpt_set_walk.argtypes = [C.c_uint32]
@@ -68,6 +74,25 @@ def lib():
 def _check(status):
     if status != _abi.WPT_OK:
         raise RuntimeError("wurblpt_hip: %s (status %d)" % (lib().wpt_last_error().decode(), status))
+
+
+def uniform_edges(start, width, count):
+    """Edges of `count` bins of one width from `start`: e_k = start + (float)k * width, each operation rounded to float32
+    (no fused multiply-add), as SensorRGBTransient computes them.  Raises ValueError when they do not increase."""
+    import numpy as np
+    k = np.arange(count + 1, dtype=np.float32)
+    edges = np.float32(start) + k * np.float32(width)
+    if count < 1 or not np.all(np.isfinite(edges)) or not np.all(edges[1:] > edges[:-1]):
+        raise ValueError("uniform_edges(%r, %r, %r): the edges do not increase" % (start, width, count))
+    return edges
+
+
+def _edges_array(edges):
+    """float32 copy of a bin edge sequence (count + 1 values) for the C ABI"""
+    import numpy as np
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32))
+    assert e.ndim == 1 and e.size >= 2, "bin edges: at least two values"
+    return e
 
 
 def device_count():
@@ -145,6 +170,55 @@ class DeviceScene:
             names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
             cnt = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
         return frame.cpu().numpy(), cnt
+
+    def render_transient_into(self, frame, bins, samples_sqrt, edges, block=None, params=None, stream=None, width=None, height=None):
+        """Asynchronously renders pixels [start, start+size) of the frame and of the transient film in one launch.
+        `frame`: CUDA float32 tensor [h, w, 3] or None; `bins`: CUDA float32 tensor [K, h, w, 3] (full frames);
+        `edges`: K + 1 increasing floats (the last may be inf).  Bin k is the light whose optical path length lies in
+        [edges[k], edges[k + 1]), per channel, behind the distance gate of `params`."""
+        from . import host
+        w = width or self.host.width
+        h = height or self.host.height
+        e = _edges_array(edges)
+        K = e.size - 1
+        assert bins.is_cuda and bins.is_contiguous() and bins.dtype.is_floating_point and bins.element_size() == 4 and bins.numel() == K * w * h * 3
+        if frame is not None:
+            assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
+        p = params if params is not None else host.default_params()
+        start, size = block if block is not None else (0, w * h)
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
+        _check(lib().wpt_render_transient_block_device(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K,
+                                                        w, h, samples_sqrt, start, size, fptr, C.c_void_p(bins.data_ptr()), sptr))
+
+    def render_transient(self, samples_sqrt, edges, block=None, params=None, width=None, height=None):
+        """Synchronous convenience: returns (frame [h, w, 3], bins [K, h, w, 3]) as numpy arrays."""
+        import torch
+        w = width or self.host.width
+        h = height or self.host.height
+        K = _edges_array(edges).size - 1
+        frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        bins = torch.zeros((K, h, w, 3), dtype=torch.float32, device="cuda")
+        self.render_transient_into(frame, bins, samples_sqrt, edges, block, params, torch.cuda.current_stream(), w, h)
+        torch.cuda.synchronize()
+        self.check()
+        return frame.cpu().numpy(), bins.cpu().numpy()
+
+    def render_transient_host(self, samples_sqrt, edges, block, params=None, width=None, height=None):
+        """wpt_render_transient_block: submitBlock semantics; returns (block rgb [size, 3], block bins [K, size, 3])."""
+        import numpy as np
+        from . import host
+        w = width or self.host.width
+        h = height or self.host.height
+        e = _edges_array(edges)
+        K = e.size - 1
+        p = params if params is not None else host.default_params()
+        start, size = block
+        rgb = np.zeros((size, 3), dtype=np.float32)
+        bins = np.zeros((K, size, 3), dtype=np.float32)
+        _check(lib().wpt_render_transient_block(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K, w, h,
+                                                samples_sqrt, start, size, C.c_void_p(rgb.ctypes.data), C.c_void_p(bins.ctypes.data)))
+        return rgb, bins
 
     def render_block_host(self, samples_sqrt, block, params=None, width=None, height=None):
         """wpt_render_block: MPICoordinator::submitBlock semantics, host buffer of size*3 floats."""

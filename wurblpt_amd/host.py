@@ -125,7 +125,8 @@ def set_camera_mode(scene, surround_mode=0, stereoscopic_distance=0.0):
 
 def cornell(width, height, tall_box_material=0, short_object_material=0):
     """Cornell box of wurblpt-cornellbox.cpp: tall box 0 = white / 1 = GGX metal,
-    short box 0 = white / 2 = glass."""
+    short box 0 = white / 2 = glass / 3 = glass with a refractive index per channel (chromatic dispersion: the channels'
+    optical path lengths differ)."""
     h = lib().wpt_host_cornell(tall_box_material, 0, short_object_material, width, height)
     return HostScene(h, width, height, "cornell(tall=%d,short=%d)" % (tall_box_material, short_object_material))
 

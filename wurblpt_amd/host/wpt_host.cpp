@@ -60,7 +60,7 @@ void addQuadN(Scene& scene, const Material* material, const float (&p)[4][3], fl
 }
 
 /* wurblpt-cornellbox.cpp:44-227; shortObjectType 0 (box) only, materials 0 = white,
- * tall box 1 = GGX metal, short box 2 = glass */
+ * tall box 1 = GGX metal, short box 2 = glass, 3 = glass with chromatic dispersion (not in the reference application) */
 bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, int shortObjectMaterialType, std::string& error)
 {
     if (shortObjectType != 0 || shortObjectMaterialType == 1) {
@@ -75,6 +75,8 @@ bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, in
     Material* glass = scene.take(new MaterialGlass(vec3(0.2f), 1.5f));
     Material* tall = (tallBoxMaterialType == 0 ? white : metal);
     Material* shortM = (shortObjectMaterialType == 0 ? white : glass);
+    if (shortObjectMaterialType == 3) /* dispersive glass: a refractive index per channel, so the channels' paths part */
+        shortM = scene.take(new MaterialGlass(vec4(0.2f), vec4(1.46f, 1.5f, 1.54f, 1.5f)));
 
     { /* left wall */
         const float p[4][3] = { { -1.01f, 0.0f, 0.99f }, { -0.99f, 0.0f, -1.04f }, { -1.02f, 1.99f, -1.04f }, { -1.02f, 1.99f, 0.99f } };
