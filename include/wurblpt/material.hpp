@@ -2,7 +2,7 @@
  * material.hpp -- host-side material descriptions.
  *
  * Same classes and constructor signatures as the reference (material.hpp:158-334,
- * material_lambertian.hpp, light_diffuse.hpp, material_mirror.hpp, material_ggx.hpp,
+ * material_lambertian.hpp, light_diffuse.hpp, light_spot.hpp, material_mirror.hpp, material_ggx.hpp,
  * material_glass.hpp, material_modphong.hpp).  The reference evaluates materials through
  * virtual scatter()/scatterToDirection()/emitted(); here each class describes itself as a
  * tagged wpt_material record that the HIP kernel evaluates.  A Material subclass that the
@@ -112,6 +112,29 @@ public:
     {
         out = wptEmptyMaterial(WPT_MAT_LIGHT_DIFFUSE);
         wptSet(out.v[0], _emit);
+        return setTex(out, 0, _tex, ctx) && setNormalTex(out, ctx);
+    }
+};
+
+/* light_spot.hpp:33-62: emits like LightDiffuse, but only towards directions within half the opening angle of the
+ * surface normal.  cos(openingAngle / 2) is computed here, in float, as the reference computes it. */
+class LightSpot final : public Material
+{
+private:
+    const float _cosHalfOpeningAngle;
+    const vec4 _emit;
+    const Texture* _tex;
+
+public:
+    LightSpot(float openingAngle, const vec3& emit, const Texture* tex = nullptr) :
+        _cosHalfOpeningAngle(cosf(0.5f * openingAngle)), _emit(emit, average(emit)), _tex(tex)
+    {
+    }
+    virtual bool describe(wpt_material& out, FlattenContext& ctx) const override
+    {
+        out = wptEmptyMaterial(WPT_MAT_LIGHT_SPOT);
+        wptSet(out.v[0], _emit);
+        out.f[0] = _cosHalfOpeningAngle;
         return setTex(out, 0, _tex, ctx) && setNormalTex(out, ctx);
     }
 };

@@ -142,7 +142,8 @@ enum {
     WPT_MAT_GLASS = 5,         /* material_glass.hpp */
     WPT_MAT_MODPHONG = 6,      /* material_modphong.hpp */
     WPT_MAT_TWOSIDED = 7,      /* material.hpp:273-334 */
-    WPT_MAT_RGL = 8            /* material_rgl.hpp:46-102, measured BRDF (powitacq_rgb) */
+    WPT_MAT_RGL = 8,           /* material_rgl.hpp:46-102, measured BRDF (powitacq_rgb) */
+    WPT_MAT_LIGHT_SPOT = 9     /* light_spot.hpp */
 };
 enum {
     WPT_MATF_HAVE_NIR = 1,
@@ -161,6 +162,7 @@ enum {
  *                 tex[0]=diffuse tex[1]=specular tex[2]=shininess tex[3]=opacity tex[4]=emissive
  *  TWOSIDED       tex[0]=front material index, tex[1]=back material index
  *  RGL            tex[0]=index into wpt_scene_desc::rgl_brdfs
+ *  LIGHT_SPOT     v[0]=emit (rgb, average) f[0]=cos(openingAngle / 2)   tex[0]=emit
  * Texture indices are -1 when absent. */
 typedef struct wpt_material {
     uint32_t type;

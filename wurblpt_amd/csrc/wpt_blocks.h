@@ -614,7 +614,8 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_SCATTER_LAMBERT, m.type == WPT_MAT_LAMBERTIAN);
     sec<COUNT>(lc, SEC_SCATTER_GGX, m.type == WPT_MAT_GGX);
     sec<COUNT>(lc, SEC_SCATTER_GLASS, m.type == WPT_MAT_GLASS || m.type == WPT_MAT_MIRROR);
-    sec<COUNT>(lc, SEC_SCATTER_OTHER, m.type != WPT_MAT_LAMBERTIAN && m.type != WPT_MAT_GGX && m.type != WPT_MAT_GLASS && m.type != WPT_MAT_MIRROR && m.type != WPT_MAT_LIGHT_DIFFUSE);
+    sec<COUNT>(lc, SEC_SCATTER_OTHER, m.type != WPT_MAT_LAMBERTIAN && m.type != WPT_MAT_GGX && m.type != WPT_MAT_GLASS && m.type != WPT_MAT_MIRROR && m.type != WPT_MAT_LIGHT_DIFFUSE
+            && !((F & FEAT_SPOT) && m.type == WPT_MAT_LIGHT_SPOT));
     sec<COUNT>(lc, SEC_EMISSION);
     Prng prng = loadPrng(ps);
 #ifdef WPT_MATERIAL_CACHE
@@ -632,7 +633,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     section(1);
     const f4 att = ps.get4(SLOT_ATT);
     {
-        f4 rad = mul(att, materialEmitted<F>(sv, m, h));
+        f4 rad = mul(att, materialEmitted<F>(sv, m, h, ray.d));
         accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps);
     }
     section(2);
@@ -762,7 +763,7 @@ WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS&
         if (best.prim == nee.w) {
             Hit lh = finishHit<F>(sv, best, ps.o, ps.d, ps.time, tri4);
             const wpt_material& lm = resolveMaterial<F>(sv, lh.material, lh);
-            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh));
+            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh, ps.d));
             const f4 ri = ps.get4(SLOT_RI);
             f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, mk3(ri.x, ri.y, ri.z)));
             accumulate<F>(par, bins, oplLight, lh.a, rad, ps);
@@ -799,7 +800,7 @@ WPT_D void blockNeeResult(const SceneView& sv, const wpt_params& par, Tri4 tri4,
         if (neeBest.prim == nee.w) {
             Hit lh = finishHit<F>(sv, neeBest, ps.neeO, ps.neeD, ps.time, tri4);
             const wpt_material& lm = resolveMaterial<F>(sv, lh.material, lh);
-            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh));
+            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh, ps.neeD));
             const Slot opl = ps.get(SLOT_NEXTATT), ri = ps.get(SLOT_SRDIR);
             f3 oplLight = add(mk3(opl.x, opl.y, opl.z), scl(lh.a, mk3(ri.x, ri.y, ri.z)));
             accumulateRadiance(par, oplLight, lh.a, rad, ps);

@@ -212,6 +212,8 @@ uint32_t sceneFeatures(const wpt_scene_desc* d)
             f |= FEAT_GGX;
         if (m.type == WPT_MAT_GLASS || m.type == WPT_MAT_MIRROR)
             f |= FEAT_GLASS;
+        if (m.type == WPT_MAT_LIGHT_SPOT)
+            f |= FEAT_SPOT;
         bool tex = m.normal_tex >= 0;
         if (m.type != WPT_MAT_TWOSIDED)
             for (int k = 0; k < 5; k++)
@@ -285,7 +287,7 @@ wpt_status validate(const wpt_scene_desc* d)
     }
     for (uint32_t i = 0; i < d->material_count; i++) {
         const wpt_material& m = d->materials[i];
-        if (m.type > WPT_MAT_RGL)
+        if (m.type > WPT_MAT_LIGHT_SPOT)
             return fail(WPT_ERR_UNSUPPORTED, "material type is not known to the kernel");
         if (m.type == WPT_MAT_RGL) {
             if (m.tex[0] < 0 || uint32_t(m.tex[0]) >= d->rgl_count)

@@ -455,7 +455,8 @@ enum {
     FEAT_SPHERES = 128,  /* HitableSphere leaves and sphere hot spots */
     FEAT_RGL = 256,      /* MaterialRGL, measured BRDFs (wpt_rgl.h) */
     FEAT_ANIM = 512,     /* exposure interval t0 != t1 and / or animated instances (wpt_anim.h) */
-    FEAT_TRANSIENT = 1024 /* transient film: contributions are also binned by optical path length (wpt_blocks.h, BinsView) */
+    FEAT_TRANSIENT = 1024, /* transient film: contributions are also binned by optical path length (wpt_blocks.h, BinsView) */
+    FEAT_SPOT = 2048     /* LightSpot: emission inside a cone around the normal */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */
@@ -1534,12 +1535,16 @@ template<uint32_t F> WPT_D void materialEval(const SceneView& sv, const wpt_mate
     }
 }
 
-/* Material::emitted */
-template<uint32_t F> WPT_D f4 materialEmitted(const SceneView& sv, const wpt_material& m, const Hit& h)
+/* Material::emitted of a ray along `dir` that found the hit `h` (`h` resolved through resolveMaterial) */
+template<uint32_t F> WPT_D f4 materialEmitted(const SceneView& sv, const wpt_material& m, const Hit& h, f3 dir)
 {
-    if (m.type == WPT_MAT_LIGHT_DIFFUSE) { /* light_diffuse.hpp:50-61 */
+    /* light_spot.hpp:46-61: LightDiffuse's emission where the ray arrives within the half opening angle of the normal, 0
+     * elsewhere (the record's f[0] is cos(openingAngle / 2), computed on the host) */
+    const bool spot = (F & FEAT_SPOT) && m.type == WPT_MAT_LIGHT_SPOT;
+    if (m.type == WPT_MAT_LIGHT_DIFFUSE || spot) { /* light_diffuse.hpp:50-61 */
         f4 e = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (!h.backside) {
+        const bool inCone = !spot || dot(h.n, neg(dir)) >= m.f[0];
+        if (!h.backside && inCone) {
             e = ld4(m.v[0]);
             if ((F & FEAT_TEXTURES) && m.tex[0] >= 0) {
                 f4 c = textureValue(sv, m.tex[0], h.tc);

@@ -734,7 +734,7 @@ inline void launchMaybePooled(Kernel kernel, const KernelArgs& args, dim3 grid, 
 }
 
 constexpr uint32_t FEAT_BASIC = FEAT_GGX | FEAT_GLASS;
-constexpr uint32_t FEAT_ALL = FEAT_TEXTURES | FEAT_MODPHONG | FEAT_ENVMAP | FEAT_LENS | FEAT_TWOSIDED | FEAT_GGX | FEAT_GLASS | FEAT_SPHERES;
+constexpr uint32_t FEAT_ALL = FEAT_TEXTURES | FEAT_MODPHONG | FEAT_ENVMAP | FEAT_LENS | FEAT_TWOSIDED | FEAT_GGX | FEAT_GLASS | FEAT_SPHERES | FEAT_SPOT;
 
 /* getGroundTruth (wpt_k_groundtruth.hip): array[k] is the device array of GroundTruth bit k or NULL */
 struct GroundTruthArgs {

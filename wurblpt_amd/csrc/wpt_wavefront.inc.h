@@ -135,6 +135,7 @@ template<bool SPHERES> WPT_D uint32_t shadeKind(const SceneView& sv, uint32_t wo
         m = sv.materials + (backside ? m->tex[1] : m->tex[0]);
     switch (m->type) {
     case WPT_MAT_LIGHT_DIFFUSE: return WF_B_LIGHT;
+    case WPT_MAT_LIGHT_SPOT: return WF_B_LIGHT;
     case WPT_MAT_LAMBERTIAN: return WF_B_LAMBERT;
     case WPT_MAT_MODPHONG: return WF_B_MODPHONG;
     case WPT_MAT_GGX: return WF_B_GGX;

@@ -199,6 +199,17 @@ def spheres(width, height, variant=0):
     return HostScene(h, width, height, "spheres(variant=%d)" % variant)
 
 
+def spot_scene(width, height, variant=0):
+    """Scenes lit by LightSpots: 0 = the Cornell box (white boxes) with the spot ceiling light of wurblpt-cornellbox.cpp
+    (MaterialTwoSided(LightSpot(radians(30), vec3(4)), MaterialLambertian(vec3(0)))), 1 = a stage (floor, back wall, a
+    sphere) under coloured spots, one with a checker-textured emission and one a sphere, 2 = the Cornell box with GGX tall
+    box, glass short box and the spot ceiling light."""
+    L = lib()
+    L.wpt_host_spot_scene.restype = C.c_void_p
+    L.wpt_host_spot_scene.argtypes = [C.c_int, C.c_uint, C.c_uint]
+    return HostScene(L.wpt_host_spot_scene(variant, width, height), width, height, "spot_scene(variant=%d)" % variant)
+
+
 def rgl_fixture(name):
     """path of a synthetic measured-BRDF file committed under tests/golden (iso / aniso)"""
     return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "synthetic_%s.bsdf" % name)

@@ -61,7 +61,8 @@ void addQuadN(Scene& scene, const Material* material, const float (&p)[4][3], fl
 
 /* wurblpt-cornellbox.cpp:44-227; shortObjectType 0 (box) only, materials 0 = white,
  * tall box 1 = GGX metal, short box 2 = glass, 3 = glass with chromatic dispersion (not in the reference application) */
-bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, int shortObjectMaterialType, std::string& error)
+bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, int shortObjectMaterialType, std::string& error,
+        bool spotLight = false)
 {
     if (shortObjectType != 0 || shortObjectMaterialType == 1) {
         error = "cornell: only the box short object with white or glass material is built here";
@@ -70,7 +71,10 @@ bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, in
     Material* white = scene.take(new MaterialLambertian(vec3(0.725f, 0.71f, 0.68f)));
     Material* red = scene.take(new MaterialLambertian(vec3(0.63f, 0.065f, 0.05f)));
     Material* green = scene.take(new MaterialLambertian(vec3(0.14f, 0.45f, 0.091f)));
-    Material* light = scene.take(new LightDiffuse(vec3(4.0f)));
+    /* the spot light is the application's third light variant (wurblpt-cornellbox.cpp:61-63) */
+    Material* light = spotLight
+        ? scene.take(new MaterialTwoSided(scene.take(new LightSpot(radians(30.0f), vec3(4.0f))), scene.take(new MaterialLambertian(vec3(0.0f)))))
+        : scene.take(new LightDiffuse(vec3(4.0f)));
     Material* metal = scene.take(new MaterialGGX(vec3(1.0f), vec2(0.04f)));
     Material* glass = scene.take(new MaterialGlass(vec3(0.2f), 1.5f));
     Material* tall = (tallBoxMaterialType == 0 ? white : metal);
@@ -193,6 +197,30 @@ void buildRandomTriangles(Scene& scene, unsigned int n, unsigned int seed, bool 
     scene.take(new MeshInstance(scene.take(generateQuad()), light, T), HotSpot);
 }
 
+/* A small stage lit by coloured LightSpots (light_spot.hpp), all of them hot spots: a floor with a white sphere on it and a
+ * back wall; a red spot and a tilted green one that reaches the wall, a white spot whose emission is a checker texture (a
+ * gobo on the lamp's face) and a spherical lamp whose every surface point is a spot around its own normal. */
+void buildStage(Scene& scene)
+{
+    Material* white = scene.take(new MaterialLambertian(vec3(0.7f)));
+    Material* grey = scene.take(new MaterialLambertian(vec3(0.45f, 0.45f, 0.5f)));
+    Texture* gobo = scene.take(new TextureChecker(vec3(1.0f), vec3(0.1f), 4, 4));
+    Material* red = scene.take(new LightSpot(radians(25.0f), vec3(8.0f, 1.5f, 1.0f)));
+    Material* green = scene.take(new LightSpot(radians(30.0f), vec3(1.5f, 8.0f, 1.5f)));
+    Material* patterned = scene.take(new LightSpot(radians(40.0f), vec3(6.0f), gobo));
+    Material* amber = scene.take(new LightSpot(radians(50.0f), vec3(6.0f, 4.0f, 1.5f)));
+    const quat toFloor = toQuat(radians(-90.0f), vec3(1.0f, 0.0f, 0.0f));
+    const quat down = toQuat(radians(90.0f), vec3(1.0f, 0.0f, 0.0f));
+    const quat downAndBack = toQuat(radians(120.0f), vec3(1.0f, 0.0f, 0.0f)); /* normal (0, -0.87, -0.5) */
+    scene.take(new MeshInstance(scene.take(generateQuad()), white, Transformation(vec3(0.0f), toFloor, vec3(3.0f, 2.0f, 1.0f))));
+    scene.take(new MeshInstance(scene.take(generateQuad()), grey, Transformation(vec3(0.0f, 1.5f, -2.0f), quat::null(), vec3(3.0f, 1.5f, 1.0f))));
+    scene.take(new Sphere(vec3(-1.8f, 0.3f, 0.3f), 0.3f, white));
+    scene.take(new MeshInstance(scene.take(generateQuad()), red, Transformation(vec3(-1.8f, 2.4f, 0.3f), down, vec3(0.15f))), HotSpot);
+    scene.take(new MeshInstance(scene.take(generateQuad()), green, Transformation(vec3(-0.6f, 2.4f, 0.2f), downAndBack, vec3(0.15f))), HotSpot);
+    scene.take(new MeshInstance(scene.take(generateQuad()), patterned, Transformation(vec3(0.6f, 2.4f, 0.4f), down, vec3(0.2f))), HotSpot);
+    scene.take(new Sphere(vec3(1.8f, 2.2f, 0.2f), 0.12f, amber), HotSpot);
+}
+
 wpt_host_scene* finishSceneOf(wpt_host_scene* hs, Scene& scene, unsigned int width, unsigned int height, float vfovRadians,
         const vec3& from, const vec3& at, float aperture, float focusDist)
 {
@@ -277,6 +305,29 @@ wpt_host_scene* wpt_host_cornell(int tallBoxMaterial, int shortObjectType, int s
         return nullptr;
     }
     return finishScene(hs, width, height, radians(50.0f), vec3(0.0f, 1.0f, 3.2f), vec3(0.0f, 1.0f, -1.0f));
+}
+
+/* Scenes lit by LightSpots: 0 = the Cornell box (white boxes) with the application's spot ceiling light
+ * (wurblpt-cornellbox.cpp:61-63), 1 = a stage (buildStage), 2 = the Cornell box with GGX metal tall box, glass short box
+ * and the spot ceiling light */
+wpt_host_scene* wpt_host_spot_scene(int variant, unsigned int width, unsigned int height)
+{
+    wpt_host_scene* hs = new wpt_host_scene;
+    if (variant == 0 || variant == 2) {
+        if (!buildCornell(hs->scene, variant == 2 ? 1 : 0, 0, variant == 2 ? 2 : 0, hs->error, true)) {
+            fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
+            delete hs;
+            return nullptr;
+        }
+        return finishScene(hs, width, height, radians(50.0f), vec3(0.0f, 1.0f, 3.2f), vec3(0.0f, 1.0f, -1.0f));
+    }
+    if (variant == 1) {
+        buildStage(hs->scene);
+        return finishScene(hs, width, height, radians(45.0f), vec3(0.0f, 1.5f, 6.0f), vec3(0.0f, 0.9f, 0.0f));
+    }
+    fprintf(stderr, "wpt_host: spot scene variant %d is not known\n", variant);
+    delete hs;
+    return nullptr;
 }
 
 wpt_host_scene* wpt_host_random_triangles(unsigned int n, unsigned int seed, int withTexcoords, unsigned int width,
