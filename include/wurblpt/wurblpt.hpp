@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <chrono>
 #include <string>
 #include <thread>
@@ -185,6 +186,83 @@ inline void mcpt(MPICoordinator& mpiCoordinator, Sensor& sensor, const Camera& c
     pixelArray->globalTagList().set("WURBLPT/DEVICE_COUNT", std::to_string(mpiCoordinator.devices().size()));
     pixelArray->globalTagList().set("WURBLPT/DEVICE_SECONDS",
             std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count()));
+}
+
+/* mcpt() for a batch of views: sensor i is rendered from camera i, all of them in one launch on one device (wurblpt_hip.h:
+ * wpt_render_views).  Each sensor's frame is bit for bit what mcpt(sensor, camera i, ...) writes, and carries the same tags.
+ * One wpt_params serves the batch, so the sensors must agree in size and in their four gates; that, and one sensor per camera,
+ * is checked before any device work (std::invalid_argument).  Several devices and MPI ranks are not served. */
+inline void mcpt(const std::vector<SensorRGB*>& sensors, const std::vector<Camera>& cameras, const Scene& scene,
+        unsigned int samplesSqrt, float t0 = 0.0f, float t1 = 0.0f, const Parameters& params = Parameters())
+{
+    if (sensors.empty() || sensors.size() != cameras.size())
+        throw std::invalid_argument("mcpt: a batch of views needs one sensor per camera, and at least one of each");
+    for (const SensorRGB* s : sensors) {
+        if (!s)
+            throw std::invalid_argument("mcpt: a sensor of the batch is NULL");
+        const SensorRGB& s0 = *sensors[0];
+        if (s->width() != s0.width() || s->height() != s0.height())
+            throw std::invalid_argument("mcpt: the sensors of a batch of views must have one size");
+        if (s->minDistToLight != s0.minDistToLight || s->maxDistToLight != s0.maxDistToLight || s->minPathLen != s0.minPathLen
+                || s->maxPathLen != s0.maxPathLen)
+            throw std::invalid_argument("mcpt: the sensors of a batch of views must have the same distance and path length gates");
+    }
+    if (scene.bvhNeedsUpdate(t0, t1))
+        mcptFatal("Scene::updateBVH(t0, t1) must run before mcpt()");
+    FlatScene flat;
+    std::string error;
+    if (!scene.flatten(flat, &error))
+        mcptFatal(error);
+    const uint32_t viewCount = uint32_t(cameras.size());
+    std::vector<wpt_camera> cams(viewCount);
+    for (uint32_t v = 0; v < viewCount; v++) {
+        if (!cameras[v].describe(cams[v], t0))
+            mcptFatal("this camera cannot be described to the device path");
+        if (cameras[v].animation) {
+            /* each camera's key frames join the scene's pool */
+            cams[v].animation = flat.addAnimation(cameras[v].animation.get());
+            if (cams[v].animation < 0)
+                mcptFatal("only key frame animations (AnimationKeyframes) can go to the device");
+        }
+    }
+    const wpt_scene_desc desc = flat.desc();
+    wpt_params p = makeParams(params, *sensors[0]);
+    p.t0 = t0;
+    p.t1 = t1;
+    const unsigned int width = sensors[0]->width();
+    const unsigned int height = sensors[0]->height();
+
+    fprintf(stderr, "Number of hitables that are hot spots: %zu\n", scene.hotSpots().size());
+    fprintf(stderr, "Rendering %u views of %ux%u pixels with %u samples.\n", viewCount, width, height, samplesSqrt * samplesSqrt);
+    if (wpt_device_count() <= 0)
+        mcptFatal(std::string("no HIP device: ") + wpt_last_error());
+    const auto renderStart = std::chrono::steady_clock::now();
+    wpt_scene* dscene = nullptr;
+    if (wpt_scene_upload(&desc, &dscene) != WPT_OK)
+        mcptFatal(wpt_last_error());
+    const size_t frameFloats = size_t(width) * height * 3;
+    std::vector<float> frames(frameFloats * viewCount);
+    const wpt_status st = wpt_render_views(dscene, cams.data(), viewCount, &p, width, height, samplesSqrt, frames.data());
+    wpt_scene_free(dscene);
+    if (st != WPT_OK)
+        mcptFatal(wpt_last_error());
+
+    int device = 0;
+    if (wpt_current_device(&device) != WPT_OK)
+        device = 0;
+    const std::string seconds = std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count());
+    for (uint32_t v = 0; v < viewCount; v++) {
+        ArrayContainer* a = sensors[v]->pixelArray();
+        std::copy(frames.begin() + v * frameFloats, frames.begin() + (v + 1) * frameFloats, static_cast<float*>(a->data()));
+        a->globalTagList().set("WURBLPT/SAMPLES_PER_PIXEL", std::to_string(samplesSqrt * samplesSqrt));
+        a->globalTagList().set("WURBLPT/MAX_PATH_COMPONENTS", std::to_string(params.maxPathComponents));
+        a->globalTagList().set("WURBLPT/RUSSIAN_ROULETTE_THRESHOLD", std::to_string(params.rrThreshold));
+        a->globalTagList().set("WURBLPT/DEVICE_KERNEL", wpt_kernel_name());
+        a->globalTagList().set("WURBLPT/COMPILER", wpt_build_info());
+        a->globalTagList().set("WURBLPT/DEVICE_MODEL", wpt_device_name(device));
+        a->globalTagList().set("WURBLPT/DEVICE_COUNT", "1");
+        a->globalTagList().set("WURBLPT/DEVICE_SECONDS", seconds);
+    }
 }
 
 /* mcpt() for a SensorRGBTransient: the frame and every bin in one pass per block (wurblpt_hip.h: wpt_render_transient_block).

@@ -386,6 +386,26 @@ wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         float* block_rgb, float* block_bins);
 
+/* ---- a batch of views ----
+ * One launch renders view_count frames of one scene: frame v from cameras_host[v], with one parameter set, one frame size and one
+ * sample count for all.  The cameras may differ in anything (pose, frustum, thin lens, distortion, surround or stereo mode,
+ * animation).  Frame v is bit-identical to the plain render of camera v (wpt_render_block_device over the whole frame): a
+ * pixel's generator is seeded from its index in its own frame.  The batch is rendered by the single kernel (never in the
+ * wavefront form) for the union of the scene's and all cameras' features.  Refused with WPT_ERR_INVALID_ARGUMENT before a
+ * device is needed: view_count == 0, NULL cameras or frames, a camera animation index below -1, and
+ * view_count * width * height > WPT_VIEWS_MAX_PIXELS; then, with the scene at hand, an animation index outside its array. */
+#define WPT_VIEWS_MAX_PIXELS 0x7fffffffu
+
+/* Asynchronous on `hip_stream`.  `frames_device`: float[view_count][height][width][3] in device memory, full frames, row 0 =
+ * bottom.  `counters_device` (may be NULL): ONE wpt_counters that receives the sum over all views (added to). */
+wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count,
+        const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        float* frames_device, wpt_counters* counters_device, void* hip_stream);
+
+/* Synchronous form: `frames_host` as above, in host memory. */
+wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count,
+        const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host);
+
 /* Waits for the device; WPT_ERR_HIP if a launch since the last call failed (the kernels have no waits that could run
  * out: every loop of theirs ends with its work). */
 wpt_status wpt_scene_check(wpt_scene* scene);

@@ -448,10 +448,18 @@ template<class PS> WPT_D int advancePath(const wpt_params& par, PS& ps, f4 nextA
     return NEXT_TRACE;
 }
 
-/* wurblpt.hpp:348-360 + Camera::getRay (camera.hpp:123-185), pinhole or thin lens */
-template<uint32_t F, class PS>
-WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
+/* wurblpt.hpp:348-360 + Camera::getRay (camera.hpp:123-185), pinhole or thin lens, from camera `cam`.  UNIFORM: `cam` is the
+ * same for every lane of the wave (the launch's camera, or the one view a whole wave of a batch is on), and its frustum and
+ * pose are taken as scalars (here()); otherwise each lane reads its own camera's words. */
+template<uint32_t F, bool UNIFORM, class PS>
+WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const SceneView& sv)
 {
+    auto uni = [](float x) {
+        if constexpr (UNIFORM)
+            return here(x);
+        else
+            return x;
+    };
     const uint32_t stratum = ps.getW(SLOT_ACC);
     const uint32_t i = stratum & 0xffffu, j = stratum >> 16; /* sampleIndex % samplesSqrt, sampleIndex / samplesSqrt */
     if (j >= fa.samplesSqrt)
@@ -473,20 +481,20 @@ WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
     v *= fa.invHeight;
     /* Camera::getRay (camera.hpp:123-185) */
     float stereoscopicShift = 0.0f;
-    if ((F & FEAT_LENS) && fa.cam.stereoscopic_distance > 0.0f) {
+    if ((F & FEAT_LENS) && cam.stereoscopic_distance > 0.0f) {
         v *= 2.0f; /* left view in the upper half, right view in the lower half */
         if (v < 1.0f) {
-            stereoscopicShift = -0.5f * fa.cam.stereoscopic_distance;
+            stereoscopicShift = -0.5f * cam.stereoscopic_distance;
         } else {
             v -= 1.0f;
-            stereoscopicShift = +0.5f * fa.cam.stereoscopic_distance;
+            stereoscopicShift = +0.5f * cam.stereoscopic_distance;
         }
     }
     f3 O, D;
-    if ((F & FEAT_LENS) && fa.cam.surround_mode != WPT_SURROUND_OFF) {
+    if ((F & FEAT_LENS) && cam.surround_mode != WPT_SURROUND_OFF) {
         /* direction from longitude and latitude; the optics are ignored */
         float lon = (2.0f * u - 1.0f) * k_pi;
-        if (fa.cam.surround_mode == WPT_SURROUND_180)
+        if (cam.surround_mode == WPT_SURROUND_180)
             lon *= 0.5f;
         const float lat = (v - 0.5f) * k_pi;
         const float clat = wptm::cosf_(lat), slat = wptm::sinf_(lat), clon = wptm::cosf_(lon), slon = wptm::sinf_(lon);
@@ -494,14 +502,14 @@ WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
         O = sclr(mk3(-clon, 0.0f, -slon), stereoscopicShift);
     } else {
         /* the samples lie in the distorted output image: rays are made from the undistorted coordinates */
-        if ((F & FEAT_LENS) && fa.cam.distortion_type != WPT_DISTORTION_NONE)
-            wptlens::undistort(fa.cam, u, v, fa.width, fa.height); /* a real call; the coefficients travel by value */
-        f3 P = mk3(mixr(here(fa.cam.l), here(fa.cam.r), u), mixr(here(fa.cam.b), here(fa.cam.t), v), -1.0f);
+        if ((F & FEAT_LENS) && cam.distortion_type != WPT_DISTORTION_NONE)
+            wptlens::undistort(cam, u, v, fa.width, fa.height); /* a real call; the coefficients travel by value */
+        f3 P = mk3(mixr(uni(cam.l), uni(cam.r), u), mixr(uni(cam.b), uni(cam.t), v), -1.0f);
         O = mk3(0.0f, 0.0f, 0.0f);
-        if ((F & FEAT_LENS) && fa.cam.lens_radius > 0.0f) {
-            P = sclr(P, fa.cam.focus_dist);
+        if ((F & FEAT_LENS) && cam.lens_radius > 0.0f) {
+            P = sclr(P, cam.focus_dist);
             f2 d = inUnitDisk(in01x2(prng));
-            O = mk3(fa.cam.lens_radius * d.x, fa.cam.lens_radius * d.y, 0.0f);
+            O = mk3(cam.lens_radius * d.x, cam.lens_radius * d.y, 0.0f);
         }
         D = sub(P, O);
         O = add(O, mk3(stereoscopicShift, 0.0f, 0.0f));
@@ -511,23 +519,23 @@ WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
         const float t = fa.par.t0 + in01(prng) * (fa.par.t1 - fa.par.t0);
         ps.time = t;
         ps.animCached = -1; /* AnimationCache::init(r.time) */
-        if (fa.cam.animation >= 0) {
+        if (cam.animation >= 0) {
             /* (the scene view comes by reference: a POINTER to it, as this function once took, made the compiler keep a private
              * copy of all kernel arguments in scratch memory -- 880 bytes per lane in the ground truth kernel, 670 - 930 in the
              * path tracing kernels for moving scenes) */
-            const wptanim::Trs T = animationAt(sv, fa.cam.animation, t);
+            const wptanim::Trs T = animationAt(sv, cam.animation, t);
             ps.o = add(ld3(T.t), quatRotate(T.q, mul(O, ld3(T.s))));
             ps.d = normalize(quatRotate(T.q, D));
         } else {
-            ps.o = add(ld3(fa.cam.translation), quatRotate(fa.cam.rotation, mul(O, ld3(fa.cam.scaling))));
-            ps.d = normalize(quatRotate(fa.cam.rotation, D));
+            ps.o = add(ld3(cam.translation), quatRotate(cam.rotation, mul(O, ld3(cam.scaling))));
+            ps.d = normalize(quatRotate(cam.rotation, D));
         }
     } else {
         if (F & FEAT_ANIM)
             ps.time = fa.par.t0;
-        const float rotation[4] = { here(fa.cam.rotation[0]), here(fa.cam.rotation[1]), here(fa.cam.rotation[2]), here(fa.cam.rotation[3]) };
-        const f3 translation = mk3(here(fa.cam.translation[0]), here(fa.cam.translation[1]), here(fa.cam.translation[2]));
-        const f3 scaling = mk3(here(fa.cam.scaling[0]), here(fa.cam.scaling[1]), here(fa.cam.scaling[2]));
+        const float rotation[4] = { uni(cam.rotation[0]), uni(cam.rotation[1]), uni(cam.rotation[2]), uni(cam.rotation[3]) };
+        const f3 translation = mk3(uni(cam.translation[0]), uni(cam.translation[1]), uni(cam.translation[2]));
+        const f3 scaling = mk3(uni(cam.scaling[0]), uni(cam.scaling[1]), uni(cam.scaling[2]));
         ps.o = add(translation, quatRotate(rotation, mul(O, scaling)));
         ps.d = normalize(quatRotate(rotation, D));
     }
@@ -542,6 +550,12 @@ WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
     ps.setW(SLOT_ACC, i + 1 < fa.samplesSqrt ? stratum + 1 : (j + 1) << 16);
     ps.rayKind = RAY_PATH;
     return NEXT_TRACE;
+}
+
+template<uint32_t F, class PS>
+WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
+{
+    return blockNewFrom<F, true>(fa, fa.cam, ps, sv);
 }
 
 /* tracePath, one path component (wurblpt.hpp:131-252); `best` is the path ray's result.

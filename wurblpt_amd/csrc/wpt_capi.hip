@@ -884,13 +884,17 @@ wpt_status wpt_scene_get_envmap_tables(const wpt_scene* scene, float* M, int32_t
 static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         uint32_t band_pixels, uint32_t band_first, uint32_t band_stride,
-        float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr)
+        float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr,
+        const wptk::ViewsView* views = nullptr)
 {
     if (!scene || !camera || !params || !(frame_device || transient))
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
         return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    if (uint64_t(width) * height > 0xffffffffull || uint64_t(block_start) + (band_stride ? 0u : block_size) > uint64_t(width) * height)
+    /* a batch of views: `camera` is the first of views->viewCount host cameras, the block all their pixels (wpt_render_views_device) */
+    const uint32_t cameraCount = views ? views->viewCount : 1u;
+    if (uint64_t(width) * height > 0xffffffffull
+            || uint64_t(block_start) + (band_stride ? 0u : block_size) > uint64_t(width) * height * cameraCount)
         return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
     if (block_size == 0)
         return WPT_OK;
@@ -913,20 +917,33 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.frame = frame_device;
     args.counters = counters_device;
     args.schedStats = g_schedStats;
-    args.bins = transient ? *transient : wptk::BinsView{};
+    if (views)
+        args.views = *views;
+    else
+        args.bins = transient ? *transient : wptk::BinsView{};
     args.fuse = (g_variant & 0x20u) ? 0u : 1u; /* variant bit 0x20: separate SHADE / NEE-END / NEW rounds (the older scheduler) */
 
     /* a wave covers an 8x8 pixel tile when the block consists of whole groups of 8 rows */
     args.tiled = (width % 8 == 0 && block_start % width == 0 && block_size % (8 * width) == 0
             && (band_stride == 0 || band_pixels % (8 * width) == 0)) ? 1u : 0u;
-    uint32_t need = scene->features | ((camera->lens_radius > 0.0f || camera->distortion_type != WPT_DISTORTION_NONE
-                || camera->surround_mode != WPT_SURROUND_OFF || camera->stereoscopic_distance > 0.0f) ? FEAT_LENS : 0u);
-    if (camera->surround_mode > WPT_SURROUND_360)
-        return fail(WPT_ERR_UNSUPPORTED, "camera surround mode is not known to the kernel");
-    if (camera->distortion_type > WPT_DISTORTION_OPENCV)
-        return fail(WPT_ERR_UNSUPPORTED, "lens distortion model is not known to the kernel");
-    if (camera->animation >= int32_t(scene->animationCount))
-        return fail(WPT_ERR_INVALID_ARGUMENT, "camera refers to an animation outside the scene's array");
+    if (views) /* 8x8 tiles within each view's frame */
+        args.tiled = (width % 8 == 0 && height % 8 == 0) ? 1u : 0u;
+    /* a batch takes the union of the scene's features and every camera's */
+    uint32_t need = scene->features;
+    for (uint32_t v = 0; v < cameraCount; v++) {
+        const wpt_camera* c = camera + v;
+        need |= (c->lens_radius > 0.0f || c->distortion_type != WPT_DISTORTION_NONE || c->surround_mode != WPT_SURROUND_OFF
+                || c->stereoscopic_distance > 0.0f) ? FEAT_LENS : 0u;
+        if (c->surround_mode > WPT_SURROUND_360)
+            return fail(WPT_ERR_UNSUPPORTED, "camera surround mode is not known to the kernel");
+        if (c->distortion_type > WPT_DISTORTION_OPENCV)
+            return fail(WPT_ERR_UNSUPPORTED, "lens distortion model is not known to the kernel");
+        if (c->animation >= int32_t(scene->animationCount))
+            return fail(WPT_ERR_INVALID_ARGUMENT, views ? "camera " + std::to_string(v) + " refers to an animation outside the scene's array"
+                    : std::string("camera refers to an animation outside the scene's array"));
+        if (views && c->animation >= 0) /* an animated camera selects the moving-scene kernels */
+            need |= FEAT_ANIM;
+    }
     /* an exposure interval changes every path (each camera ray draws its time), moving instances need the time too */
     if (params->t0 != params->t1)
         need |= FEAT_ANIM;
@@ -962,7 +979,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * number of streams never share one. */
     /* Wavefront form (wpt_wavefront.inc.h): trace and shade as two kernels that hand rays through HBM.  Not for counting
      * launches and moving scenes (those instantiations exist for the single kernel only). */
-    const bool wfExists = !count && !anim && !transient; /* (a transient film is always rendered by the single kernel) */
+    const bool wfExists = !count && !anim && !transient && !views; /* (a transient film and a batch of views are always rendered by the single kernel) */
     /* The library's own choice (measured): launches of 2^21 lanes and more whose scene has measured BRDFs --
      * long shading that pays for being sorted by kind of material, and enough lanes to fill the trace and the shade kernel one
      * after the other (tools/wf_threshold_probe.py, 16 spp, single kernel / wavefront: 115.5 / 100.7 Msamples/s at 2^20 lanes,
@@ -1010,7 +1027,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.orderCount = nullptr;
     /* the wide walk where the scene has that form (wpt_set_walk before the upload): product launches of the kernels that fetch
      * the scene from HBM; counting launches and moving scenes walk the binary tree */
-    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient; /* (the kernel with the scene in LDS walks the binary tree) */
+    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient && !views; /* (the kernel with the scene in LDS walks the binary tree) */
     g_kernelName.store(wide ? "wpt_pathtrace, wide walk" : nullptr, std::memory_order_relaxed);
     /* the transient film: the LDS kernel for the Cornell class, the all-features kernel for other scenes at rest, the moving-scene
      * kernels for moving scenes and for measured BRDFs */
@@ -1019,8 +1036,27 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         g_kernelName.store(transientLds ? "wpt_pathtrace, transient, scene in LDS"
                 : rgl ? "wpt_pathtrace, transient, measured BRDFs"
                 : anim ? "wpt_pathtrace, transient, all features, moving scenes" : "wpt_pathtrace, transient, all features", std::memory_order_relaxed);
+    /* a batch of views: the kernel of its scene kind as for one frame; measured BRDFs take the moving-scene instantiation */
+    const bool viewsLds = views && basic && lds && !anim && !rgl && !count;
+    if (views)
+        g_kernelName.store(viewsLds ? "wpt_pathtrace, views, scene in LDS"
+                : rgl ? (count ? "wpt_pathtrace, views, measured BRDFs, counting" : "wpt_pathtrace, views, measured BRDFs")
+                : anim ? (count ? "wpt_pathtrace, views, all features, moving scenes, counting" : "wpt_pathtrace, views, all features, moving scenes")
+                : basic ? (count ? "wpt_pathtrace, views, basic, counting" : "wpt_pathtrace, views, basic")
+                : count ? "wpt_pathtrace, views, all features, counting" : "wpt_pathtrace, views, all features", std::memory_order_relaxed);
     auto launch = [&](const wptk::KernelArgs& a) {
-        if (transient) {
+        if (views) {
+            if (viewsLds)
+                launchBasicLdsViews(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+            else if (rgl)
+                count ? launchFullRglAnimCountViews(a, grid, stream) : launchFullRglAnimViews(a, grid, stream);
+            else if (anim)
+                count ? launchFullAnimCountViews(a, grid, stream) : launchFullAnimViews(a, grid, stream);
+            else if (basic)
+                count ? launchBasicCountViews(a, grid, stream) : launchBasicViews(a, grid, stream);
+            else
+                count ? launchFullCountViews(a, grid, stream) : launchFullViews(a, grid, stream);
+        } else if (transient) {
             if (transientLds)
                 launchBasicLdsTransient(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
@@ -1072,7 +1108,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * 938 against 954). */
     const uint64_t lanesAtOnce = uint64_t(scene->cuCount) * 4u * WG;
     const bool sceneInLds = basic && lds && !anim && !rgl;
-    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !sceneInLds && samples_sqrt >= 8
+    /* (not for a batch of views: the carry, cost and order buffers are indexed by the pixel of one frame) */
+    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !sceneInLds && !views && samples_sqrt >= 8
             && uint64_t(block_size) >= 2u * lanesAtOnce && uint64_t(block_size) <= 64u * lanesAtOnce;
     float4* carry = nullptr;
     uint32_t *cost = nullptr, *order = nullptr, *work = nullptr;
@@ -1320,6 +1357,88 @@ wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera
         (void)hipFree(dBlock);
     if (dBins)
         (void)hipFree(dBins);
+    return st;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* what a batch of views is refused for before anything needs the scene or a device */
+wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void* frames, uint32_t width, uint32_t height)
+{
+    if (viewCount == 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "views: view_count is 0");
+    if (!cameras)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "views: cameras are NULL");
+    if (!frames)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "views: frames are NULL");
+    for (uint32_t v = 0; v < viewCount; v++)
+        if (cameras[v].animation < -1)
+            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
+    /* the kernels index the batch's pixels, and hand them out from the pixel pool, in 32 bits */
+    if (uint64_t(viewCount) * width * height > WPT_VIEWS_MAX_PIXELS)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "views: view_count * width * height exceeds " + std::to_string(WPT_VIEWS_MAX_PIXELS) + " pixels");
+    return WPT_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device, void* hip_stream)
+{
+    const wpt_status checked = viewsCheck(cameras_host, view_count, frames_device, width, height);
+    if (checked != WPT_OK)
+        return checked;
+    if (!scene || !params)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t v = 0; v < view_count; v++)
+        if (cameras_host[v].animation >= int32_t(scene->animationCount))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
+    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    /* the cameras go to device memory once per batch, in stream order */
+    const size_t camBytes = size_t(view_count) * sizeof(wpt_camera);
+    wpt_camera* dCams = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dCams), camBytes, stream));
+    const hipError_t e = hipMemcpyAsync(dCams, cameras_host, camBytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(dCams, stream);
+        return fail(WPT_ERR_HIP, std::string("views: ") + hipGetErrorString(e));
+    }
+    wptk::ViewsView vv;
+    vv.cams = dCams;
+    vv.viewPixels = width * height;
+    vv.viewCount = view_count;
+    const wpt_status st = renderLaunch(scene, cameras_host, params, width, height, samples_sqrt, 0, view_count * width * height, 0, 0, 0,
+            frames_device, counters_device, hip_stream, nullptr, &vv);
+    (void)hipFreeAsync(dCams, stream);
+    return st;
+}
+
+wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
+{
+    const wpt_status checked = viewsCheck(cameras_host, view_count, frames_host, width, height);
+    if (checked != WPT_OK)
+        return checked;
+    if (!scene)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const size_t bytes = size_t(view_count) * width * height * 3 * sizeof(float);
+    float* dFrames = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dFrames), bytes));
+    wpt_status st = wpt_render_views_device(scene, cameras_host, view_count, params, width, height, samples_sqrt, dFrames, nullptr, nullptr);
+    if (st == WPT_OK)
+        st = wpt_scene_check(scene);
+    if (st == WPT_OK) {
+        const hipError_t e = hipMemcpy(frames_host, dFrames, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(dFrames);
     return st;
 }
 

@@ -1,0 +1,12 @@
+/* wpt_k_full_count_views.hip -- instantiates wpt_pathtrace<FEAT_ALL | FEAT_VIEWS, true, false>: a batch of views of a scene at rest, with work counters */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchFullCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream)
+{
+    hipLaunchKernelGGL((wpt_pathtrace<FEAT_ALL | FEAT_VIEWS, true, false, 2>), grid, dim3(WG), COLD_BYTES, stream, args);
+}
+
+}

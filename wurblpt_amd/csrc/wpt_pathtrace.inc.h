@@ -64,6 +64,14 @@ constexpr uint32_t LDS_SCENE_MAX_BYTES = 20 * 1024;
 constexpr uint32_t LDS_BYTES_PER_WORKGROUP_AT_FOUR = 160 * 1024 / 4;
 /* the material records are copied to LDS quadword by quadword and read there through a generic pointer */
 static_assert(sizeof(wpt_material) % 16 == 0 && alignof(wpt_material) <= 16, "wpt_material must be a whole number of quadwords");
+/* A batch of views (FEAT_VIEWS kernels): the launch's lane indices g in [0, viewCount * viewPixels) are view g / viewPixels,
+ * pixel g % viewPixels of that view's frame; view v is rendered from cams[v] into frame + v * viewPixels * 3.  A pixel's
+ * generator is seeded from its index in its own frame, so view v is the plain render of cams[v] bit for bit. */
+struct ViewsView {
+    const wpt_camera* cams; /* viewCount cameras in device memory */
+    uint32_t viewPixels;    /* width * height */
+    uint32_t viewCount;
+};
 struct KernelArgs {
     SceneView sv;
     wpt_camera cam;
@@ -100,7 +108,10 @@ struct KernelArgs {
     uint32_t materialsInLds; /* scene in LDS: the material records are there too */
     wpt_counters* counters;
     unsigned long long* schedStats; /* COUNT builds: 16 scheduler statistics, or NULL */
-    BinsView bins; /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there) */
+    union { /* (no launch has both: the kernels of either feature are instantiated without the other) */
+        BinsView bins;   /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there) */
+        ViewsView views; /* FEAT_VIEWS kernels: the batch's cameras; frame holds viewCount full frames, blockSize is all their pixels */
+    };
 };
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
@@ -160,6 +171,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 {
     static_assert(!WIDE || (!LDSSCENE && !COUNT), "the wide walk: product kernels that fetch the scene from HBM (counting launches walk like the reference)");
     static_assert(!LDSSCENE || !(F & FEAT_SPHERES), "the LDS copy of the tree tells leaves (complemented word) from inner nodes by the sign bit: triangle leaves only");
+    static_assert(!((F & FEAT_VIEWS) && (F & FEAT_TRANSIENT)), "a batch of views has no transient film (they share KernelArgs' union)");
+    constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
     /* node prefetch: for scenes in HBM (Sponza-class frame 3 % faster); not from LDS, where the fetch is short and the
      * registers that hold the node ahead lengthen every step (Cornell 4 % slower) */
     constexpr bool PREFETCH = !LDSSCENE && !WIDE;
@@ -250,6 +263,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     /* ---- per-lane state: the pixel's path (wpt_blocks.h; its cold words in LDS) and the traversal registers ---- */
     PathLds<WG> ps;
     ps.base = ldsCold + threadIdx.x;
+    /* VIEWS: the view of the lane's pixel (the pixel's x | y << 16 fills SLOT_SRDIR.w); a register of its own */
+    uint32_t view = 0;
     /* the lane takes the pixel behind index `at` of the launch; false: there is none */
     auto startPixel = [&](uint32_t at) -> bool {
         uint32_t pixel = args.blockStart;
@@ -258,6 +273,11 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             have = at < laneLimit;
             if (have)
                 pixel = args.order[at];
+        } else if constexpr (VIEWS) {
+            /* the view, then the pixel of its frame (8x8 tiles within each view where the launch is tiled) */
+            have = at < args.blockSize;
+            view = have ? at / args.views.viewPixels : 0u;
+            pixelOf(at - view * args.views.viewPixels, pixel);
         } else {
             have = pixelOf(at, pixel);
         }
@@ -656,11 +676,25 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             sec<COUNT>(lc, SEC_NEW_SAMPLE, state == S_NEW);
             if (state == S_NEW) { /* the pixel's next sample (wurblpt.hpp:348-360), or nothing more */
                 const bool passEnds = firstPass && (ps.getW(SLOT_ACC) >> 16) >= args.rowStop;
-                const int next = passEnds ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv);
+                int next;
+                if constexpr (VIEWS) {
+                    /* Camera::getRay from the lane's own view: scalar reads of one camera where the lanes here are all on
+                     * one view (a wave in the middle of a view), each lane's own camera where they are not */
+                    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
+                    if (passEnds)
+                        next = NEXT_DONE;
+                    else if (__ballot(view != first) == 0)
+                        next = blockNewFrom<F, true>(fa, args.views.cams[first], ps, sv);
+                    else
+                        next = blockNewFrom<F, false>(fa, args.views.cams[view], ps, sv);
+                } else {
+                    next = passEnds ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv);
+                }
                 sec<COUNT>(lc, SEC_PIXEL_DONE, next == NEXT_DONE);
                 if (next == NEXT_DONE) {
                     const uint32_t pxy = ps.getW(SLOT_SRDIR);
-                    const size_t at = (size_t)(pxy >> 16) * args.width + (pxy & 0xffffu);
+                    /* VIEWS: the pixel's index in the batch's frames */
+                    const size_t at = (VIEWS ? (size_t)view * args.views.viewPixels : 0u) + (size_t)(pxy >> 16) * args.width + (pxy & 0xffffu);
                     if (firstPass) {
                         args.carry[2 * at] = ps.base[SLOT_PRNG * WG];
                         args.carry[2 * at + 1] = ps.base[SLOT_ACC * WG];
@@ -771,6 +805,17 @@ void launchBasicLdsTransient(const KernelArgs& args, dim3 grid, size_t sceneLdsB
 void launchFullTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* a batch of views (FEAT_VIEWS, args.views): every scene kind of the single kernel, product and counting builds; measured BRDFs
+ * take the moving-scene instantiation whether the scene moves or not */
+void launchBasicLdsViews(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchBasicViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchBasicCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullRglAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullRglAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
 
 } /* namespace wptk */
 

@@ -22,7 +22,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_postproc_to_srgb", "wpt_postproc_max_luminance", "wpt_postproc_uniform_rational_quantization",
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
            "wpt_render_block_device", "wpt_render_block",
-           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -59,6 +59,10 @@ def lib():
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_transient_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.wpt_render_views_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
+                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
+                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
         L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.wpt_set_walk.argtypes = [C.c_uint32]
@@ -219,6 +223,38 @@ class DeviceScene:
         _check(lib().wpt_render_transient_block(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K, w, h,
                                                 samples_sqrt, start, size, C.c_void_p(rgb.ctypes.data), C.c_void_p(bins.ctypes.data)))
         return rgb, bins
+
+    def render_views_into(self, frames, cameras, samples_sqrt, params=None, counters=None, stream=None):
+        """Asynchronously renders a batch of views in one launch: frame v of `frames`, a CUDA float32 tensor [V, h, w, 3], from
+        cameras[v] (_abi.Camera records, e.g. host.camera_looking_at).  One parameter set, frame size and sample count serve all
+        views; frame v is bit for bit the plain render of cameras[v].  `counters`: optional CUDA int64 tensor [6] that the sum
+        over all views is added to."""
+        from . import host
+        V = len(cameras)
+        assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point and frames.element_size() == 4
+        assert frames.dim() == 4 and frames.shape[0] == V and frames.shape[3] == 3, "frames: [V, h, w, 3]"
+        h, w = int(frames.shape[1]), int(frames.shape[2])
+        cams = (_abi.Camera * max(V, 1))(*cameras)
+        p = params if params is not None else host.default_params()
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
+        _check(lib().wpt_render_views_device(self._handle, cams, V, C.byref(p), w, h, samples_sqrt, C.c_void_p(frames.data_ptr()),
+                                             cptr, sptr))
+
+    def render_views(self, samples_sqrt, cameras, params=None, with_counters=False, width=None, height=None):
+        """Synchronous convenience: returns the frames as a CUDA tensor [V, h, w, 3] (and the counters dict with_counters)."""
+        import torch
+        w = width or self.host.width
+        h = height or self.host.height
+        frames = torch.zeros((len(cameras), h, w, 3), dtype=torch.float32, device="cuda")
+        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
+        self.render_views_into(frames, cameras, samples_sqrt, params, counters, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        self.check()
+        if with_counters:
+            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
+            return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
+        return frames
 
     def render_block_host(self, samples_sqrt, block, params=None, width=None, height=None):
         """wpt_render_block: MPICoordinator::submitBlock semantics, host buffer of size*3 floats."""

@@ -123,6 +123,29 @@ def set_camera_mode(scene, surround_mode=0, stereoscopic_distance=0.0):
     L.wpt_host_scene_set_camera_mode(scene._handle_for_camera, surround_mode, stereoscopic_distance)
 
 
+def lookat(eye, target, up=(0.0, 1.0, 0.0)):
+    """Transformation::fromLookAt(eye, target, up) as wpt_host_lookat gives it: 35 float32 -- translation (3), rotation
+    quaternion x y z w (4), scaling (3), then toMat4 (16) and toNormalMatrix (9)."""
+    L = lib()
+    L.wpt_host_lookat.argtypes = [C.c_void_p] * 4
+    L.wpt_host_lookat.restype = None
+    e, t, u = (np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(3)) for x in (eye, target, up))
+    out = np.zeros(35, dtype=np.float32)
+    L.wpt_host_lookat(C.c_void_p(e.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(u.ctypes.data), C.c_void_p(out.ctypes.data))
+    return out
+
+
+def camera_looking_at(scene, eye, target, up=(0.0, 1.0, 0.0)):
+    """A copy of the scene's camera (frustum, lens, distortion, mode, animation) placed at `eye` looking at `target`: its
+    translation, rotation and scaling are those of lookat(eye, target, up).  For DeviceScene.render_views."""
+    cam = _abi.Camera.from_buffer_copy(scene.camera.contents)
+    T = lookat(eye, target, up)
+    cam.translation[:] = [float(x) for x in T[0:3]]
+    cam.rotation[:] = [float(x) for x in T[3:7]]
+    cam.scaling[:] = [float(x) for x in T[7:10]]
+    return cam
+
+
 def cornell(width, height, tall_box_material=0, short_object_material=0):
     """Cornell box of wurblpt-cornellbox.cpp: tall box 0 = white / 1 = GGX metal,
     short box 0 = white / 2 = glass / 3 = glass with a refractive index per channel (chromatic dispersion: the channels'
