@@ -11,6 +11,8 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -263,6 +265,128 @@ inline void mcpt(const std::vector<SensorRGB*>& sensors, const std::vector<Camer
         a->globalTagList().set("WURBLPT/DEVICE_COUNT", "1");
         a->globalTagList().set("WURBLPT/DEVICE_SECONDS", seconds);
     }
+}
+
+/* mcpt() with a sample-count map (adaptive sampling, wurblpt_hip.h: wpt_render_adaptive_block), on one device.
+ * samplesSqrt holds n_p for every pixel, [height][width] with row 0 at the bottom like the frame: pixel p gets n_p^2 samples
+ * and is bit for bit what mcpt(sensor, ..., n_p, ...) writes; a pixel with n_p = 0 is not rendered and keeps the value the
+ * sensor held.  `moments` (may be NULL) receives the moment film, width x height x 3: per channel, 1 / n_p^2 times the sum over
+ * the samples of the square of what each sample added; a pixel with n_p = 0 keeps its entries where `moments` already has the
+ * frame's size (otherwise it is made anew, with zeros).  A map of the wrong size is refused before any device work
+ * (std::invalid_argument).  The tags are the plain render's, but WURBLPT/SAMPLES_PER_PIXEL is "adaptive" and
+ * WURBLPT/SAMPLES_TOTAL is the sum of n_p^2. */
+inline void mcpt(SensorRGB& sensor, const Camera& camera, const Scene& scene, const std::vector<uint16_t>& samplesSqrt,
+        float t0 = 0.0f, float t1 = 0.0f, const Parameters& params = Parameters(), Array<float>* moments = nullptr)
+{
+    const unsigned int width = sensor.width();
+    const unsigned int height = sensor.height();
+    if (samplesSqrt.size() != size_t(width) * height)
+        throw std::invalid_argument("mcpt: the sample-count map must hold one count per pixel (width * height)");
+    if (scene.bvhNeedsUpdate(t0, t1))
+        mcptFatal("Scene::updateBVH(t0, t1) must run before mcpt()");
+    wpt_camera cam;
+    if (!camera.describe(cam, t0))
+        mcptFatal("this camera cannot be described to the device path");
+    FlatScene flat;
+    std::string error;
+    if (!scene.flatten(flat, &error))
+        mcptFatal(error);
+    if (camera.animation) {
+        cam.animation = flat.addAnimation(camera.animation.get());
+        if (cam.animation < 0)
+            mcptFatal("only key frame animations (AnimationKeyframes) can go to the device");
+    }
+    const wpt_scene_desc desc = flat.desc();
+    wpt_params p = makeParams(params, sensor);
+    p.t0 = t0;
+    p.t1 = t1;
+    uint64_t total = 0;
+    for (uint16_t n : samplesSqrt)
+        total += uint64_t(n) * n;
+
+    fprintf(stderr, "Number of hitables that are hot spots: %zu\n", scene.hotSpots().size());
+    fprintf(stderr, "Rendering %ux%u pixels with %llu samples in all (adaptive).\n", width, height, static_cast<unsigned long long>(total));
+    if (wpt_device_count() <= 0)
+        mcptFatal(std::string("no HIP device: ") + wpt_last_error());
+    if (moments && (moments->dimension(0) != width || moments->dimension(1) != height || moments->componentCount() != 3))
+        *moments = Array<float>(width, height, 3);
+    ArrayContainer* a = sensor.pixelArray();
+    const auto renderStart = std::chrono::steady_clock::now();
+    wpt_scene* dscene = nullptr;
+    if (wpt_scene_upload(&desc, &dscene) != WPT_OK)
+        mcptFatal(wpt_last_error());
+    const wpt_status st = wpt_render_adaptive_block(dscene, &cam, &p, width, height, samplesSqrt.data(), 0, width * height,
+            static_cast<float*>(a->data()), moments ? static_cast<float*>(moments->data()) : nullptr);
+    wpt_scene_free(dscene);
+    if (st != WPT_OK)
+        mcptFatal(wpt_last_error());
+
+    int device = 0;
+    if (wpt_current_device(&device) != WPT_OK)
+        device = 0;
+    a->globalTagList().set("WURBLPT/SAMPLES_PER_PIXEL", "adaptive");
+    a->globalTagList().set("WURBLPT/SAMPLES_TOTAL", std::to_string(total));
+    a->globalTagList().set("WURBLPT/MAX_PATH_COMPONENTS", std::to_string(params.maxPathComponents));
+    a->globalTagList().set("WURBLPT/RUSSIAN_ROULETTE_THRESHOLD", std::to_string(params.rrThreshold));
+    a->globalTagList().set("WURBLPT/DEVICE_KERNEL", wpt_kernel_name());
+    a->globalTagList().set("WURBLPT/COMPILER", wpt_build_info());
+    a->globalTagList().set("WURBLPT/DEVICE_MODEL", wpt_device_name(device));
+    a->globalTagList().set("WURBLPT/DEVICE_COUNT", "1");
+    a->globalTagList().set("WURBLPT/DEVICE_SECONDS",
+            std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count()));
+}
+
+/* A sample-count map for mcpt() with a map, from a pilot render with pilotSamplesSqrt^2 samples (>= 2, so that a variance can
+ * be estimated) and its moment film: for every pixel, in float64,
+ *   N0 = pilot^2;  var_c = max(m_c - f_c^2, 0) * (N0 / (N0 - 1))  (the pixel's sample variance);
+ *   need = max over c of var_c / (relError^2 * max(|f_c|, floor)^2);
+ *   n = clamp(ceil(sqrt(need)), minSqrt, maxSqrt),
+ * so that the standard error of the mean, sqrt(var_c / n^2), is about relError times the value (or times `floor` where the value
+ * is smaller).  A pixel with a non-finite input, or a non-finite `need`, gets maxSqrt.  Refused (std::invalid_argument): a pilot
+ * below 2, arrays that differ in size or are not three channels, relError not > 0, floor not >= 0, minSqrt > maxSqrt or
+ * maxSqrt > 65535.  wurblpt_amd.device.samples_sqrt_for_error is the same formula. */
+inline std::vector<uint16_t> samplesSqrtForError(const Array<float>& frame, const Array<float>& moments, unsigned int pilotSamplesSqrt,
+        double relError, unsigned int minSqrt, unsigned int maxSqrt, double floor)
+{
+    if (pilotSamplesSqrt < 2)
+        throw std::invalid_argument("samplesSqrtForError: the pilot needs pilotSamplesSqrt >= 2");
+    if (frame.dimension(0) != moments.dimension(0) || frame.dimension(1) != moments.dimension(1) || frame.componentCount() != 3
+            || moments.componentCount() != 3)
+        throw std::invalid_argument("samplesSqrtForError: frame and moments must be arrays of one size with three channels");
+    if (!(relError > 0.0) || !(floor >= 0.0) || minSqrt > maxSqrt || maxSqrt > 65535)
+        throw std::invalid_argument("samplesSqrtForError: needs relError > 0, floor >= 0 and minSqrt <= maxSqrt <= 65535");
+    const double N0 = double(pilotSamplesSqrt) * double(pilotSamplesSqrt);
+    const double scale = N0 / (N0 - 1.0);
+    const double r2 = relError * relError;
+    const size_t pixels = frame.elementCount();
+    std::vector<uint16_t> map(pixels);
+    for (size_t i = 0; i < pixels; i++) {
+        const float* f = frame[i];
+        const float* m = moments[i];
+        bool finite = true;
+        double need = 0.0;
+        for (int c = 0; c < 3 && finite; c++) {
+            const double fc = f[c], mc = m[c];
+            if (!std::isfinite(fc) || !std::isfinite(mc)) {
+                finite = false;
+                break;
+            }
+            const double var = std::max(mc - fc * fc, 0.0) * scale;
+            const double d = std::max(std::fabs(fc), floor);
+            const double q = var / (r2 * (d * d));
+            if (!std::isfinite(q))
+                finite = false;
+            else if (c == 0 || q > need)
+                need = q;
+        }
+        unsigned int n = maxSqrt;
+        if (finite) {
+            const double s = std::ceil(std::sqrt(need));
+            n = s < double(minSqrt) ? minSqrt : s > double(maxSqrt) ? maxSqrt : static_cast<unsigned int>(s);
+        }
+        map[i] = static_cast<uint16_t>(n);
+    }
+    return map;
 }
 
 /* mcpt() for a SensorRGBTransient: the frame and every bin in one pass per block (wurblpt_hip.h: wpt_render_transient_block).

@@ -406,6 +406,33 @@ wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_h
 wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count,
         const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host);
 
+/* ---- adaptive sampling ----
+ * A sample-count map gives every pixel its own count: uint16_t n_p per pixel, [height][width], row 0 = bottom.  A pixel with
+ * n_p > 0 is rendered with n_p^2 samples (strata s % n_p, s / n_p) and its value is bit-identical to the plain render with
+ * samples_sqrt = n_p; a pixel with n_p = 0 is not rendered, and its entries in the frame and the moment film are not written
+ * (a region of interest rendered into an existing frame is a map with zeros outside it).  Every 16-bit value is valid.
+ * The moment film (may be NULL): float[height][width][3]; entry c of pixel p is 1 / n_p^2 times the fp32 sum, in sample order,
+ * of S_k,c * S_k,c, where S_k,c is the fp32 sum of what sample k added to channel c of the pixel's accumulator (behind the
+ * distance and path-length gates).  At n_p = 1 it is frame * frame bit for bit; asking for it changes no bit of the frame.
+ * The variance of the pixel's mean is estimated by (moment - frame^2) * N / (N - 1) / N with N = n_p^2.
+ * Rendered by the single kernel in one pass (never in the wavefront form), the costly pixels handed out first.  Refused with
+ * WPT_ERR_INVALID_ARGUMENT before a device is needed: a NULL map or frame, a width or height of 0 or above 65535, and a block
+ * outside the frame. */
+
+/* Asynchronous on `hip_stream`.  `samples_sqrt_device`, `frame_device` and `moments_device` are FULL frames in device
+ * memory; only the block's pixels with n_p > 0 are written. */
+wpt_status wpt_render_adaptive_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_device /* [height][width] */,
+        uint32_t block_start, uint32_t block_size, float* frame_device, float* moments_device /* may be NULL */,
+        void* hip_stream);
+
+/* Synchronous form with MPICoordinator::submitBlock semantics: `samples_sqrt_host` is the FULL map in host memory,
+ * `block_rgb` and `block_moments` (may be NULL) block_size*3 floats each in host memory.  The entries of pixels with n_p = 0
+ * are left as the caller had them. */
+wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_host /* [height][width] */,
+        uint32_t block_start, uint32_t block_size, float* block_rgb, float* block_moments /* may be NULL */);
+
 /* Waits for the device; WPT_ERR_HIP if a launch since the last call failed (the kernels have no waits that could run
  * out: every loop of theirs ends with its work). */
 wpt_status wpt_scene_check(wpt_scene* scene);

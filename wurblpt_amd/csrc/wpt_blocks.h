@@ -120,6 +120,12 @@ template<int STRIDE> struct PathLds : PathHot {
     WPT_D void setW(int k, uint32_t w) { reinterpret_cast<uint32_t*>(base + k * STRIDE)[3] = w; }
 };
 
+/* FEAT_ADAPTIVE kernels: the cold words in LDS as above, and in registers what the current sample has added to the
+ * accumulator so far (S, three channels), for the moment film (wpt_pathtrace.inc.h, AdaptiveView) */
+template<int STRIDE> struct PathLdsSum : PathLds<STRIDE> {
+    f3 sampleSum;
+};
+
 /* cold words in registers (one ray per lane: the ground truth kernel) */
 struct PathRegs : PathHot {
     Slot slot[SLOT_COUNT];
@@ -400,6 +406,28 @@ WPT_D int binOf(const BinsView& b, float x)
  * Where the three channels' lengths are equal (everything but dispersive glass) the bin is looked up once. */
 template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, const BinsView& bv, f3 opl, float distanceToLight, f4 radiance, PS& ps)
 {
+    if constexpr ((F & FEAT_ADAPTIVE) != 0) {
+        /* accumulateRadiance, each addition made to the sample's own sum as well (PathLdsSum), behind the same gates */
+        if (!(distanceToLight >= par.min_dist_to_light && distanceToLight <= par.max_dist_to_light))
+            return;
+        Slot acc = ps.get(SLOT_ACC);
+        f3 s = ps.sampleSum;
+        if (opl.x >= par.min_path_len && opl.x <= par.max_path_len) {
+            acc.x += radiance.x;
+            s.x += radiance.x;
+        }
+        if (opl.y >= par.min_path_len && opl.y <= par.max_path_len) {
+            acc.y += radiance.y;
+            s.y += radiance.y;
+        }
+        if (opl.z >= par.min_path_len && opl.z <= par.max_path_len) {
+            acc.z += radiance.z;
+            s.z += radiance.z;
+        }
+        ps.set3(SLOT_ACC, mk3(acc.x, acc.y, acc.z));
+        ps.sampleSum = s;
+        return;
+    }
     accumulateRadiance(par, opl, distanceToLight, radiance, ps);
     if constexpr ((F & FEAT_TRANSIENT) != 0) {
         if (!(distanceToLight >= par.min_dist_to_light && distanceToLight <= par.max_dist_to_light))
@@ -601,7 +629,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
     const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
-    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
+    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
          * once (nothing has been written yet): the next round then runs it for two rounds' worth

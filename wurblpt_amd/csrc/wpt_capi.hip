@@ -885,7 +885,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         uint32_t band_pixels, uint32_t band_first, uint32_t band_stride,
         float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr,
-        const wptk::ViewsView* views = nullptr)
+        const wptk::ViewsView* views = nullptr, const wptk::AdaptiveView* adaptive = nullptr)
 {
     if (!scene || !camera || !params || !(frame_device || transient))
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -919,6 +919,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.schedStats = g_schedStats;
     if (views)
         args.views = *views;
+    else if (adaptive)
+        args.adaptive = *adaptive;
     else
         args.bins = transient ? *transient : wptk::BinsView{};
     args.fuse = (g_variant & 0x20u) ? 0u : 1u; /* variant bit 0x20: separate SHADE / NEE-END / NEW rounds (the older scheduler) */
@@ -979,7 +981,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * number of streams never share one. */
     /* Wavefront form (wpt_wavefront.inc.h): trace and shade as two kernels that hand rays through HBM.  Not for counting
      * launches and moving scenes (those instantiations exist for the single kernel only). */
-    const bool wfExists = !count && !anim && !transient && !views; /* (a transient film and a batch of views are always rendered by the single kernel) */
+    const bool wfExists = !count && !anim && !transient && !views && !adaptive; /* (a transient film, a batch of views and an adaptive launch are always rendered by the single kernel) */
     /* The library's own choice (measured): launches of 2^21 lanes and more whose scene has measured BRDFs --
      * long shading that pays for being sorted by kind of material, and enough lanes to fill the trace and the shade kernel one
      * after the other (tools/wf_threshold_probe.py, 16 spp, single kernel / wavefront: 115.5 / 100.7 Msamples/s at 2^20 lanes,
@@ -1027,7 +1029,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.orderCount = nullptr;
     /* the wide walk where the scene has that form (wpt_set_walk before the upload): product launches of the kernels that fetch
      * the scene from HBM; counting launches and moving scenes walk the binary tree */
-    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient && !views; /* (the kernel with the scene in LDS walks the binary tree) */
+    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient && !views && !adaptive; /* (the kernel with the scene in LDS walks the binary tree) */
     g_kernelName.store(wide ? "wpt_pathtrace, wide walk" : nullptr, std::memory_order_relaxed);
     /* the transient film: the LDS kernel for the Cornell class, the all-features kernel for other scenes at rest, the moving-scene
      * kernels for moving scenes and for measured BRDFs */
@@ -1044,8 +1046,26 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 : anim ? (count ? "wpt_pathtrace, views, all features, moving scenes, counting" : "wpt_pathtrace, views, all features, moving scenes")
                 : basic ? (count ? "wpt_pathtrace, views, basic, counting" : "wpt_pathtrace, views, basic")
                 : count ? "wpt_pathtrace, views, all features, counting" : "wpt_pathtrace, views, all features", std::memory_order_relaxed);
+    /* adaptive sampling: the kernel of its scene kind as for one frame; measured BRDFs take the moving-scene instantiation */
+    const bool adaptiveLds = adaptive && basic && lds && !anim && !rgl;
+    if (adaptive)
+        g_kernelName.store(adaptiveLds ? "wpt_pathtrace, adaptive, scene in LDS"
+                : rgl ? "wpt_pathtrace, adaptive, measured BRDFs"
+                : anim ? "wpt_pathtrace, adaptive, all features, moving scenes"
+                : basic ? "wpt_pathtrace, adaptive, basic" : "wpt_pathtrace, adaptive, all features", std::memory_order_relaxed);
     auto launch = [&](const wptk::KernelArgs& a) {
-        if (views) {
+        if (adaptive) {
+            if (adaptiveLds)
+                launchBasicLdsAdaptive(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+            else if (rgl)
+                launchFullRglAnimAdaptive(a, grid, stream);
+            else if (anim)
+                launchFullAnimAdaptive(a, grid, stream);
+            else if (basic)
+                launchBasicAdaptive(a, grid, stream);
+            else
+                launchFullAdaptive(a, grid, stream);
+        } else if (views) {
             if (viewsLds)
                 launchBasicLdsViews(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
@@ -1109,7 +1129,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     const uint64_t lanesAtOnce = uint64_t(scene->cuCount) * 4u * WG;
     const bool sceneInLds = basic && lds && !anim && !rgl;
     /* (not for a batch of views: the carry, cost and order buffers are indexed by the pixel of one frame) */
-    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !sceneInLds && !views && samples_sqrt >= 8
+    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !sceneInLds && !views && !adaptive && samples_sqrt >= 8
             && uint64_t(block_size) >= 2u * lanesAtOnce && uint64_t(block_size) <= 64u * lanesAtOnce;
     float4* carry = nullptr;
     uint32_t *cost = nullptr, *order = nullptr, *work = nullptr;
@@ -1136,9 +1156,29 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             (void)hipGetLastError();
         }
     }
+    /* Adaptive sampling: one pass that hands out the costly pixels first -- the order of the second pass above, built from
+     * the sample counts n^2 instead of a first pass's times (variant bit 0x40: the plain order).  Any scene kind: a pixel's
+     * work is known before the launch here.  The order changes which lane renders a pixel when, never a bit of it. */
+    if (adaptive && pool != nullptr && !(g_variant & 0x40u)) {
+        if (hipMallocAsync(reinterpret_cast<void**>(&cost), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
+                && hipMallocAsync(reinterpret_cast<void**>(&order), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
+                && hipMallocAsync(reinterpret_cast<void**>(&work), (3 * wptk::ORDER_BUCKETS + 1) * sizeof(uint32_t), stream) == hipSuccess) {
+            wptk::KernelArgs measure = args;
+            measure.cost = cost - block_start; /* indexed by the frame's pixel: the block's pixels land in the allocation */
+            wptk::launchAdaptiveCost(measure, stream);
+            wptk::launchOrderBuild(measure, order, work, stream);
+            wptk::KernelArgs ordered = args;
+            ordered.order = order;
+            ordered.orderCount = work + 3 * wptk::ORDER_BUCKETS;
+            launch(ordered);
+            passesDone = true;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
     if (!passesDone)
         launch(args);
-    g_lastPasses.store(passesDone ? 2u : 1u, std::memory_order_relaxed);
+    g_lastPasses.store(passesDone && !adaptive ? 2u : 1u, std::memory_order_relaxed);
     const hipError_t launched = hipGetLastError();
     for (void* p : { static_cast<void*>(pool), static_cast<void*>(carry), static_cast<void*>(cost), static_cast<void*>(order), static_cast<void*>(work) })
         if (p)
@@ -1439,6 +1479,88 @@ wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, ui
             st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
     }
     (void)hipFree(dFrames);
+    return st;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* what an adaptive render is refused for before anything needs the scene or a device (every 16-bit count is valid) */
+wpt_status adaptiveCheck(uint32_t width, uint32_t height, const void* map, uint32_t blockStart, uint32_t blockSize, const void* frame)
+{
+    if (!map)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: the sample-count map is NULL");
+    if (!frame)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: the frame is NULL");
+    if (width == 0 || height == 0 || width > 65535 || height > 65535)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: width and height must lie in 1 .. 65535");
+    if (uint64_t(blockStart) + blockSize > uint64_t(width) * height)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: pixel block lies outside the frame");
+    return WPT_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+wpt_status wpt_render_adaptive_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_device, uint32_t block_start, uint32_t block_size,
+        float* frame_device, float* moments_device, void* hip_stream)
+{
+    const wpt_status checked = adaptiveCheck(width, height, samples_sqrt_device, block_start, block_size, frame_device);
+    if (checked != WPT_OK)
+        return checked;
+    wptk::AdaptiveView av;
+    av.samplesSqrt = samples_sqrt_device;
+    av.moments = moments_device;
+    /* (the launch's own samples_sqrt is unused by the adaptive kernels: 1 passes renderLaunch's checks) */
+    return renderLaunch(scene, camera, params, width, height, 1, block_start, block_size, 0, 0, 0, frame_device, nullptr, hip_stream,
+            nullptr, nullptr, &av);
+}
+
+wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_host, uint32_t block_start, uint32_t block_size,
+        float* block_rgb, float* block_moments)
+{
+    const wpt_status checked = adaptiveCheck(width, height, samples_sqrt_host, block_start, block_size, block_rgb);
+    if (checked != WPT_OK)
+        return checked;
+    if (block_size == 0)
+        return WPT_OK;
+    /* device memory for the block only, behind pointers biased so that pixel `block_start` lands at offset 0; the caller's
+     * values go there first, so that the pixels with n = 0 come back as they were */
+    const size_t blockFloats = size_t(block_size) * 3;
+    uint16_t* dMap = nullptr;
+    float *dBlock = nullptr, *dMoments = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dMap), size_t(block_size) * sizeof(uint16_t));
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&dBlock), blockFloats * sizeof(float));
+    if (e == hipSuccess && block_moments)
+        e = hipMalloc(reinterpret_cast<void**>(&dMoments), blockFloats * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMemcpy(dMap, samples_sqrt_host + block_start, size_t(block_size) * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dBlock, block_rgb, blockFloats * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && block_moments)
+        e = hipMemcpy(dMoments, block_moments, blockFloats * sizeof(float), hipMemcpyHostToDevice);
+    wpt_status st = e == hipSuccess ? WPT_OK
+            : fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("adaptive: ") + hipGetErrorString(e));
+    if (st == WPT_OK)
+        st = wpt_render_adaptive_block_device(scene, camera, params, width, height, dMap - block_start, block_start, block_size,
+                dBlock - size_t(block_start) * 3, dMoments ? dMoments - size_t(block_start) * 3 : nullptr, nullptr);
+    if (st == WPT_OK)
+        st = wpt_scene_check(scene);
+    if (st == WPT_OK) {
+        e = hipMemcpy(block_rgb, dBlock, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && block_moments)
+            e = hipMemcpy(block_moments, dMoments, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    for (void* p : { static_cast<void*>(dMap), static_cast<void*>(dBlock), static_cast<void*>(dMoments) })
+        if (p)
+            (void)hipFree(p);
     return st;
 }
 

@@ -457,7 +457,8 @@ enum {
     FEAT_ANIM = 512,     /* exposure interval t0 != t1 and / or animated instances (wpt_anim.h) */
     FEAT_TRANSIENT = 1024, /* transient film: contributions are also binned by optical path length (wpt_blocks.h, BinsView) */
     FEAT_SPOT = 2048,    /* LightSpot: emission inside a cone around the normal */
-    FEAT_VIEWS = 4096    /* a batch of views: every lane takes its camera from an array (wpt_pathtrace.inc.h, ViewsView) */
+    FEAT_VIEWS = 4096,   /* a batch of views: every lane takes its camera from an array (wpt_pathtrace.inc.h, ViewsView) */
+    FEAT_ADAPTIVE = 8192 /* adaptive sampling: every lane takes its pixel's sample count from a map (wpt_pathtrace.inc.h, AdaptiveView) */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */

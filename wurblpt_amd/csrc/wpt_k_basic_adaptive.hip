@@ -1,0 +1,12 @@
+/* wpt_k_basic_adaptive.hip -- instantiates wpt_pathtrace<FEAT_BASIC | FEAT_ADAPTIVE, false, false>: adaptive sampling of a scene of the basic feature set in HBM */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchBasicAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream)
+{
+    launchMaybePooled(wpt_pathtrace<FEAT_BASIC | FEAT_ADAPTIVE, false, false, 4>, args, grid, COLD_BYTES, stream);
+}
+
+}

@@ -1,0 +1,13 @@
+/* wpt_k_full_anim_adaptive.hip -- instantiates wpt_pathtrace<FEAT_ALL | FEAT_ANIM | FEAT_ADAPTIVE, false, false>: adaptive sampling with an exposure interval or animated
+ * instances */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchFullAnimAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream)
+{
+    launchMaybePooled(wpt_pathtrace<FEAT_ALL | FEAT_ANIM | FEAT_ADAPTIVE, false, false, 2>, args, grid, COLD_BYTES, stream);
+}
+
+}

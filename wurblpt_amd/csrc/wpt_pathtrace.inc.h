@@ -72,6 +72,15 @@ struct ViewsView {
     uint32_t viewPixels;    /* width * height */
     uint32_t viewCount;
 };
+/* Adaptive sampling (FEAT_ADAPTIVE kernels): pixel p is rendered with n_p^2 samples, n_p = samplesSqrt[p], with the strata,
+ * 1 / n_p and 1 / n_p^2 of the plain render at samplesSqrt = n_p, so that its value is that render's bit for bit; a pixel with
+ * n_p = 0 is not rendered and nothing of it is written.  moments (or NULL): per pixel and channel, 1 / n_p^2 times the fp32 sum
+ * over the samples, in their order, of S * S, where S is what the sample added to that channel of the accumulator.  M is
+ * read-added-written in HBM at each sample's end (a lane owns its pixel: no atomics), S is kept in registers (PathLdsSum). */
+struct AdaptiveView {
+    const uint16_t* samplesSqrt; /* [height][width] in device memory */
+    float* moments;              /* [height][width][3] in device memory, or NULL */
+};
 struct KernelArgs {
     SceneView sv;
     wpt_camera cam;
@@ -111,8 +120,12 @@ struct KernelArgs {
     union { /* (no launch has both: the kernels of either feature are instantiated without the other) */
         BinsView bins;   /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there) */
         ViewsView views; /* FEAT_VIEWS kernels: the batch's cameras; frame holds viewCount full frames, blockSize is all their pixels */
+        AdaptiveView adaptive; /* FEAT_ADAPTIVE kernels: the sample-count map and the moment film; samplesSqrt above is unused */
     };
 };
+/* the adaptive member must not change the union's size or the layout of what follows it: the existing kernels' code objects
+ * stay as they were */
+static_assert(sizeof(AdaptiveView) <= sizeof(BinsView) && alignof(AdaptiveView) <= alignof(BinsView), "AdaptiveView must fit in BinsView's place");
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
 WPT_D bool lanePixel(const KernelArgs& args, uint32_t gid, uint32_t& pixel)
@@ -172,7 +185,10 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     static_assert(!WIDE || (!LDSSCENE && !COUNT), "the wide walk: product kernels that fetch the scene from HBM (counting launches walk like the reference)");
     static_assert(!LDSSCENE || !(F & FEAT_SPHERES), "the LDS copy of the tree tells leaves (complemented word) from inner nodes by the sign bit: triangle leaves only");
     static_assert(!((F & FEAT_VIEWS) && (F & FEAT_TRANSIENT)), "a batch of views has no transient film (they share KernelArgs' union)");
+    static_assert(!((F & FEAT_ADAPTIVE) && (F & (FEAT_VIEWS | FEAT_TRANSIENT))), "adaptive sampling has no views and no transient film (they share KernelArgs' union)");
+    static_assert(!((F & FEAT_ADAPTIVE) && COUNT), "adaptive sampling has no counting build");
     constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
+    constexpr bool ADAPTIVE = (F & FEAT_ADAPTIVE) != 0;
     /* node prefetch: for scenes in HBM (Sponza-class frame 3 % faster); not from LDS, where the fetch is short and the
      * registers that hold the node ahead lengthen every step (Cornell 4 % slower) */
     constexpr bool PREFETCH = !LDSSCENE && !WIDE;
@@ -248,7 +264,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     };
 
     auto pixelOf = [&](uint32_t gid, uint32_t& pixel) -> bool { return lanePixel(args, gid, pixel); };
-    const bool firstPass = args.rowStop < args.samplesSqrt;
+    const bool firstPass = !ADAPTIVE && args.rowStop < args.samplesSqrt; /* (an adaptive launch is one pass) */
     const uint32_t laneLimit = args.order ? *args.orderCount : args.blockSize; /* indices a lane may take */
     FrameArgs fa;
     fa.cam = args.cam;
@@ -261,10 +277,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     fa.invSamplesSqrt = args.invSamplesSqrt;
 
     /* ---- per-lane state: the pixel's path (wpt_blocks.h; its cold words in LDS) and the traversal registers ---- */
-    PathLds<WG> ps;
+    std::conditional_t<ADAPTIVE, PathLdsSum<WG>, PathLds<WG>> ps;
     ps.base = ldsCold + threadIdx.x;
     /* VIEWS: the view of the lane's pixel (the pixel's x | y << 16 fills SLOT_SRDIR.w); a register of its own */
     uint32_t view = 0;
+    /* ADAPTIVE: the sample count n of the lane's pixel (0: not rendered), a register of its own; never wave-uniform */
+    uint32_t laneSqrt = 0;
     /* the lane takes the pixel behind index `at` of the launch; false: there is none */
     auto startPixel = [&](uint32_t at) -> bool {
         uint32_t pixel = args.blockStart;
@@ -282,7 +300,17 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             have = pixelOf(at, pixel);
         }
         pathStateInit(ps, pixel, pixel % args.width, pixel / args.width);
-        if (have && args.order) {
+        if constexpr (ADAPTIVE) {
+            laneSqrt = have ? (uint32_t)args.adaptive.samplesSqrt[pixel] : 0u;
+            ps.sampleSum = mk3(0.0f, 0.0f, 0.0f);
+            if (laneSqrt > 0 && args.adaptive.moments) { /* M = 0 */
+                float* m = args.adaptive.moments + 3 * (size_t)pixel;
+                m[0] = 0.0f;
+                m[1] = 0.0f;
+                m[2] = 0.0f;
+            }
+        }
+        if (!ADAPTIVE && have && args.order) {
             /* where the first pass stopped */
             ps.base[SLOT_PRNG * WG] = args.carry[2 * (size_t)pixel];
             ps.base[SLOT_ACC * WG] = args.carry[2 * (size_t)pixel + 1];
@@ -677,7 +705,23 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             if (state == S_NEW) { /* the pixel's next sample (wurblpt.hpp:348-360), or nothing more */
                 const bool passEnds = firstPass && (ps.getW(SLOT_ACC) >> 16) >= args.rowStop;
                 int next;
-                if constexpr (VIEWS) {
+                if constexpr (ADAPTIVE) {
+                    /* a sample has ended unless the pixel is at its first stratum: M += S * S, then S = 0 */
+                    const f3 s = ps.sampleSum;
+                    if (args.adaptive.moments && ps.getW(SLOT_ACC) != 0) {
+                        const uint32_t pxy = ps.getW(SLOT_SRDIR);
+                        float* m = args.adaptive.moments + 3 * ((size_t)(pxy >> 16) * args.width + (pxy & 0xffffu));
+                        m[0] = m[0] + s.x * s.x;
+                        m[1] = m[1] + s.y * s.y;
+                        m[2] = m[2] + s.z * s.z;
+                    }
+                    ps.sampleSum = mk3(0.0f, 0.0f, 0.0f);
+                    /* the lane's own sample count: 1.0f / (float)n divided here is the host's division bit for bit */
+                    FrameArgs fl = fa;
+                    fl.samplesSqrt = laneSqrt;
+                    fl.invSamplesSqrt = 1.0f / (float)laneSqrt;
+                    next = blockNew<F>(fl, ps, sv);
+                } else if constexpr (VIEWS) {
                     /* Camera::getRay from the lane's own view: scalar reads of one camera where the lanes here are all on
                      * one view (a wave in the middle of a view), each lane's own camera where they are not */
                     const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
@@ -699,6 +743,23 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                         args.carry[2 * at] = ps.base[SLOT_PRNG * WG];
                         args.carry[2 * at + 1] = ps.base[SLOT_ACC * WG];
                         args.cost[at] = (uint32_t)clock64() - args.cost[at];
+                    } else if (ADAPTIVE) {
+                        /* finishPixel with the pixel's own 1 / n^2 (the unsigned product converted, as mcpt() does); a pixel
+                         * with n = 0 keeps what its entries held */
+                        if (laneSqrt > 0) {
+                            const float invSamples = 1.0f / (float)(laneSqrt * laneSqrt);
+                            const Slot acc = ps.get(SLOT_ACC);
+                            float* out = args.frame + 3 * at;
+                            out[0] = invSamples * acc.x;
+                            out[1] = invSamples * acc.y;
+                            out[2] = invSamples * acc.z;
+                            if (args.adaptive.moments) {
+                                float* m = args.adaptive.moments + 3 * at;
+                                m[0] = invSamples * m[0];
+                                m[1] = invSamples * m[1];
+                                m[2] = invSamples * m[2];
+                            }
+                        }
                     } else if (!(F & FEAT_TRANSIENT) || args.frame) {
                         /* SensorRGB::finishPixel (sensor_rgb.hpp:82-87) */
                         const Slot acc = ps.get(SLOT_ACC);
@@ -816,6 +877,15 @@ void launchFullAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* adaptive sampling (FEAT_ADAPTIVE, args.adaptive): every scene kind of the single kernel, one pass, no counting builds;
+ * measured BRDFs take the moving-scene instantiation whether the scene moves or not */
+void launchBasicLdsAdaptive(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchBasicAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAnimAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullRglAnimAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* wpt_k_adaptive_cost.hip: args.cost[p] = n_p^2 for the block's pixels, the order's measure of an adaptive launch */
+void launchAdaptiveCost(const KernelArgs& args, hipStream_t stream);
 
 } /* namespace wptk */
 

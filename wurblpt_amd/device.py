@@ -22,7 +22,8 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_postproc_to_srgb", "wpt_postproc_max_luminance", "wpt_postproc_uniform_rational_quantization",
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
            "wpt_render_block_device", "wpt_render_block",
-           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
+           "wpt_render_adaptive_block_device", "wpt_render_adaptive_block", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -63,6 +64,10 @@ def lib():
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.wpt_render_adaptive_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
+                                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wpt_render_adaptive_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
         L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.wpt_set_walk.argtypes = [C.c_uint32]
@@ -97,6 +102,69 @@ def _edges_array(edges):
     e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32))
     assert e.ndim == 1 and e.size >= 2, "bin edges: at least two values"
     return e
+
+
+def _map_int(samples_sqrt):
+    """the integer values of a sample-count map, checked to lie in [0, 65535]"""
+    import numpy as np
+    a = samples_sqrt.detach().cpu().numpy() if hasattr(samples_sqrt, "detach") else np.asarray(samples_sqrt)
+    if a.dtype.kind not in "iub":
+        raise TypeError("the sample-count map must hold integers, not %s" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 65535):
+        raise ValueError("the sample-count map's values must lie in [0, 65535]")
+    return a
+
+
+def _map_u16_device(samples_sqrt):
+    """the map as 16-bit words in a CUDA tensor (uint16 bits), made on torch's current stream.  A host map has been checked by
+    _map_int already and is uploaded; a CUDA map of torch.uint16 is used as it is (every value is valid: no check, no host round
+    trip); any other CUDA integer map is checked on the device, and only the one flag of that check is read back."""
+    import numpy as np
+    import torch
+    if not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
+        a = np.ascontiguousarray(np.asarray(samples_sqrt).astype(np.uint16))
+        return torch.from_numpy(a.view(np.int16)).to("cuda")
+    t = samples_sqrt.detach()
+    if t.dtype == torch.uint16:
+        return t.contiguous()
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise TypeError("the sample-count map must hold integers, not %s" % t.dtype)
+    t = t.to(torch.int32)
+    if bool(((t < 0) | (t > 65535)).any()):
+        raise ValueError("the sample-count map's values must lie in [0, 65535]")
+    return torch.where(t >= 32768, t - 65536, t).to(torch.int16).contiguous()
+
+
+def samples_sqrt_for_error(frame, moments, pilot_samples_sqrt, rel_error, min_sqrt, max_sqrt, floor):
+    """A sample-count map (numpy uint16 [h, w]) from a pilot render with pilot_samples_sqrt^2 samples and its moment film:
+    per pixel, in float64, N0 = pilot^2; var_c = max(m_c - f_c^2, 0) * (N0 / (N0 - 1));
+    need = max over c of var_c / (rel_error^2 * max(|f_c|, floor)^2); n = clamp(ceil(sqrt(need)), min_sqrt, max_sqrt).
+    A pixel with a non-finite input or need gets max_sqrt.  The C++ samplesSqrtForError (include/wurblpt/wurblpt.hpp), value
+    for value; its refusals are ValueError here."""
+    import numpy as np
+    f = frame.detach().cpu().numpy() if hasattr(frame, "detach") else np.asarray(frame)
+    m = moments.detach().cpu().numpy() if hasattr(moments, "detach") else np.asarray(moments)
+    if int(pilot_samples_sqrt) < 2:
+        raise ValueError("samples_sqrt_for_error: the pilot needs pilot_samples_sqrt >= 2")
+    if f.shape != m.shape or f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError("samples_sqrt_for_error: frame and moments must be arrays [h, w, 3] of one shape")
+    rel_error, floor = float(rel_error), float(floor)
+    if not rel_error > 0.0 or not floor >= 0.0 or not 0 <= int(min_sqrt) <= int(max_sqrt) <= 65535:
+        raise ValueError("samples_sqrt_for_error: needs rel_error > 0, floor >= 0 and min_sqrt <= max_sqrt <= 65535")
+    f = f.astype(np.float64)
+    m = m.astype(np.float64)
+    n0 = float(pilot_samples_sqrt) * float(pilot_samples_sqrt)
+    scale = n0 / (n0 - 1.0)
+    r2 = rel_error * rel_error
+    with np.errstate(all="ignore"):
+        var = np.maximum(m - f * f, 0.0) * scale
+        d = np.maximum(np.abs(f), floor)
+        q = var / (r2 * (d * d))
+    finite = np.isfinite(f).all(axis=2) & np.isfinite(m).all(axis=2) & np.isfinite(q).all(axis=2)
+    need = np.where(finite[..., None], q, 0.0).max(axis=2)
+    n = np.clip(np.ceil(np.sqrt(need)), float(min_sqrt), float(max_sqrt))
+    n[~finite] = max_sqrt
+    return n.astype(np.uint16)
 
 
 def device_count():
@@ -255,6 +323,66 @@ class DeviceScene:
             names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
             return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
         return frames
+
+    def render_adaptive_into(self, frame, samples_sqrt, moments=None, block=None, params=None, stream=None):
+        """Renders pixels [start, start+size) with a sample-count map on `stream` (None: torch's current stream): pixel p with
+        n_p^2 samples, bit for bit the plain render at samples_sqrt = n_p; pixels with n_p = 0 are not rendered and their
+        entries not written.  `samples_sqrt`: integer map [h, w] with values in [0, 65535] (any integer tensor or array);
+        `frame` and `moments` (optional: the moment film, 1 / n_p^2 times the sum of the squares of what each sample added):
+        CUDA float32 [h, w, 3].  The launch is ordered behind the work on torch's current stream, so inputs made there are
+        ready.  Asynchronous for a CUDA map of torch.uint16; a CUDA map of another integer type is range-checked on the
+        device, which reads one flag back (a sync of the current stream); a host map is checked on the host and uploaded."""
+        import torch
+        from . import host
+        if not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
+            _map_int(samples_sqrt)
+        assert len(samples_sqrt.shape) == 2, "samples_sqrt: [h, w]"
+        h, w = int(samples_sqrt.shape[0]), int(samples_sqrt.shape[1])
+        assert frame.is_cuda and frame.is_contiguous() and frame.dtype.is_floating_point and frame.element_size() == 4 and frame.numel() == w * h * 3
+        if moments is not None:
+            assert moments.is_cuda and moments.is_contiguous() and moments.dtype.is_floating_point and moments.element_size() == 4
+            assert moments.numel() == w * h * 3
+        current = torch.cuda.current_stream()
+        launch = stream if stream is not None else current
+        # the 16-bit map is made on the current stream (where the caller's map was written); the launch stream waits for it
+        m16 = _map_u16_device(samples_sqrt)
+        if launch != current:
+            launch.wait_stream(current)
+            m16.record_stream(launch)                   # freed only after the launch stream's use
+        p = params if params is not None else host.default_params()
+        start, size = block if block is not None else (0, w * h)
+        mptr = C.c_void_p(moments.data_ptr()) if moments is not None else None
+        _check(lib().wpt_render_adaptive_block_device(self._handle, self.host.camera, C.byref(p), w, h, C.c_void_p(m16.data_ptr()),
+                                                       start, size, C.c_void_p(frame.data_ptr()), mptr, C.c_void_p(launch.cuda_stream)))
+
+    def render_adaptive(self, samples_sqrt, with_moments=False, block=None, params=None):
+        """Synchronous convenience: returns the frame as a new CUDA tensor [h, w, 3] (zeros where n_p = 0), and with_moments
+        the moment film as well: (frame, moments)."""
+        import torch
+        h, w = int(samples_sqrt.shape[0]), int(samples_sqrt.shape[1])
+        frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        moments = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if with_moments else None
+        self.render_adaptive_into(frame, samples_sqrt, moments, block, params, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        self.check()
+        return (frame, moments) if with_moments else frame
+
+    def render_adaptive_host(self, samples_sqrt, block, block_rgb, block_moments=None, params=None):
+        """wpt_render_adaptive_block: submitBlock semantics.  `block_rgb` and `block_moments` (or None): numpy float32
+        [size, 3], written in place for the block's pixels with n_p > 0 and left as they are elsewhere."""
+        import numpy as np
+        from . import host
+        a = _map_int(samples_sqrt)
+        h, w = a.shape
+        m = np.ascontiguousarray(a.astype(np.uint16))
+        p = params if params is not None else host.default_params()
+        start, size = block
+        for b in (block_rgb, block_moments):
+            assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.size == size * 3)
+        _check(lib().wpt_render_adaptive_block(self._handle, self.host.camera, C.byref(p), w, h, C.c_void_p(m.ctypes.data), start, size,
+                                               C.c_void_p(block_rgb.ctypes.data),
+                                               C.c_void_p(block_moments.ctypes.data) if block_moments is not None else None))
+        return block_rgb, block_moments
 
     def render_block_host(self, samples_sqrt, block, params=None, width=None, height=None):
         """wpt_render_block: MPICoordinator::submitBlock semantics, host buffer of size*3 floats."""
