@@ -9,7 +9,10 @@ path hands out the whole frame as one block, mpi.hpp:241-254).  N > 1: one proce
 its bands in one call into a zero-initialised full frame on its GPU and the frames are summed onto rank 0 with one RCCL
 reduce (the bands are disjoint, so the sum is exact).  The frame is fixed, so scaling is "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run does what that line's figure needs and no
+more: it builds and uploads the scene, renders the warm-up steps, times the steps, writes --dump-outputs and prints the line
+(metric, value, unit, ms_per_step, ...).  --dump-outputs writes the secondary workloads' frames as well (below); a plain run
+renders each of them once, untimed, for that.  With --full the line also carries
   roofline      the bound that binds the path-tracing kernel: scenes that fit LDS never touch HBM while they traverse,
                 so their line is priced against the vector pipes (bound "valu": executed lane-operations per second
                 from the committed PMC pass x the live sample rate, against 1024 SIMD-32 at 2.4 GHz); scenes in HBM
@@ -18,8 +21,9 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
                 committed PMC pass was taken with the library that is running.
   cpu_baseline  the CPU restatement (oracle/, "port") timed on this box's host cores on a block of the same frame
   parity        that block of the GPU's frame against the oracle's, bit for bit
-  secondary     (N = 1) the same measurement of the Sponza-class workload (BASELINE configs[2]), whose scene is fetched
-                from HBM: value, ms_per_step, roofline, cpu_baseline, parity
+  secondary     (N = 1, default workload) the same measurement of the workloads whose scene is fetched from HBM (BASELINE
+                configs[2], [3] and [4]): value, ms_per_step, roofline, cpu_baseline, parity
+and for N > 1 the comparison of the reduced frame with a single launch (frame_equals_single_launch) and rows of the oracle.
 With --obj FILE.obj --envmap FILE.hdr the Sponza-class workload renders the real files the way wurblpt-sponza.cpp:46-71,145-148
 sets its scene up instead of the procedural stand-in.
 """
@@ -260,38 +264,40 @@ def roofline_of(name, scene, cnt, spp, count_sqrt, avg_ms, avg_samples, n_launch
     return roofline
 
 
-def measure_one_gpu(name, w, scene, dscene, steps, warmup, cpu_seconds, lib_id, torch, device, host, barrier=None, walk_flags=0, count_sqrt=None):
-    """W untimed + K timed renders of the workload's frame on this GPU (one render call each), the counted pass for the
-    roofline, the CPU baseline on a block of the same frame and the parity of that block."""
+def measure_one_gpu(name, w, scene, dscene, steps, warmup, cpu_seconds, lib_id, torch, device, host, barrier=None, walk_flags=0, count_sqrt=None,
+                    full=False):
+    """W untimed + K timed renders of the workload's frame on this GPU (one render call each); with `full` also the counted
+    pass for the roofline, and with cpu_seconds > 0 the CPU baseline on a block of the same frame and the parity of that block."""
     width, height, ssqrt = w["width"], w["height"], w["samples_sqrt"]
     spp, pixels = ssqrt * ssqrt, width * height
     params = host.default_params()
     frame = torch.zeros((height, width, 3), dtype=torch.float32, device="cuda")
     stream = torch.cuda.current_stream()
-    # counted pass (untimed): work per sample for the roofline's algorithmic bytes; the counting build renders the timed
-    # frame, sample for sample (secondary workloads with hundreds of samples per pixel: the same pixels with count_sqrt^2
-    # samples each -- the first strata rows of the same sequences; the line says so in roofline.counted_on)
-    csq = min(ssqrt, count_sqrt) if count_sqrt else ssqrt
-    counters = torch.zeros(6, dtype=torch.int64, device="cuda")
-    dscene.render_block_into(frame, csq, None, params, counters, stream)
-    torch.cuda.synchronize()
-    names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
-    cnt = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
-    walked = None
-    if int(scene.d.envmap.type) != 0:
-        # What the product kernel walks: the walk of a light ray towards the environment ends at its first accepted hit (the
-        # answer it is traced for is known there), the reference's goes on.  The counted pass above counts the reference's walk
-        # (its numbers are the oracle's, and the algorithmic bytes are the reference's by definition); this one counts the
-        # product's, so that the line says both.
-        device.lib().wpt_set_walk(walk_flags | device.WALK_COUNT_PRODUCT)
-        try:
-            counters.zero_()
-            dscene.render_block_into(frame, csq, None, params, counters, stream)
-            torch.cuda.synchronize()
-            walked = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
-        finally:
-            device.lib().wpt_set_walk(walk_flags)
-    frame.zero_()
+    if full:
+        # counted pass (untimed): work per sample for the roofline's algorithmic bytes; the counting build renders the timed
+        # frame, sample for sample (secondary workloads with hundreds of samples per pixel: the same pixels with count_sqrt^2
+        # samples each -- the first strata rows of the same sequences; the line says so in roofline.counted_on)
+        csq = min(ssqrt, count_sqrt) if count_sqrt else ssqrt
+        counters = torch.zeros(6, dtype=torch.int64, device="cuda")
+        dscene.render_block_into(frame, csq, None, params, counters, stream)
+        torch.cuda.synchronize()
+        names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
+        cnt = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
+        walked = None
+        if int(scene.d.envmap.type) != 0:
+            # What the product kernel walks: the walk of a light ray towards the environment ends at its first accepted hit (the
+            # answer it is traced for is known there), the reference's goes on.  The counted pass above counts the reference's walk
+            # (its numbers are the oracle's, and the algorithmic bytes are the reference's by definition); this one counts the
+            # product's, so that the line says both.
+            device.lib().wpt_set_walk(walk_flags | device.WALK_COUNT_PRODUCT)
+            try:
+                counters.zero_()
+                dscene.render_block_into(frame, csq, None, params, counters, stream)
+                torch.cuda.synchronize()
+                walked = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
+            finally:
+                device.lib().wpt_set_walk(walk_flags)
+        frame.zero_()
     events = []
 
     def step(timed):
@@ -311,15 +317,16 @@ def measure_one_gpu(name, w, scene, dscene, steps, warmup, cpu_seconds, lib_id, 
         step(True)
     sync()
     elapsed = time.perf_counter() - t0
-    ms = [a.elapsed_time(b) for a, b in events]
-    avg_ms = sum(ms) / max(1, len(ms))
-    basis = ("algorithmic bytes of one launch / its duration (HIP events on the launch's stream); a launch is one render call: "
-             "kernel_launches_per_launch launches of the kernel(s), whose durations add up to it")
     out = {
         "value": float(pixels) * spp * steps / elapsed / 1e6, "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup,
-        "roofline": roofline_of(name, scene, cnt, spp, csq, avg_ms, float(pixels) * spp, len(ms), basis, lib_id, device, walked=walked),
         "frame_finite": bool(torch.isfinite(frame).all().item()),
     }
+    if full:
+        ms = [a.elapsed_time(b) for a, b in events]
+        avg_ms = sum(ms) / max(1, len(ms))
+        basis = ("algorithmic bytes of one launch / its duration (HIP events on the launch's stream); a launch is one render call: "
+                 "kernel_launches_per_launch launches of the kernel(s), whose durations add up to it")
+        out["roofline"] = roofline_of(name, scene, cnt, spp, csq, avg_ms, float(pixels) * spp, len(ms), basis, lib_id, device, walked=walked)
     if cpu_seconds > 0:
         record, oracle_frame, start, block = cpu_baseline(scene, w, cpu_seconds)
         out["cpu_baseline"] = record
@@ -334,6 +341,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cornell_1024x1024_1024spp_ggx_glass", choices=sorted(WORKLOADS))
     ap.add_argument("--samples-sqrt", type=int, default=0, help="override spp (debug only; changes the workload name)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the counted pass and the roofline, the CPU baseline "
+                         "and the parity of a block of the frame, the secondary workloads (N = 1, default workload), the comparison with a "
+                         "single launch and rows of the oracle (N > 1); the options that shape these take effect with --full only, "
+                         "but for --no-secondary / --skip-secondary, which also choose the frames --dump-outputs writes")
     ap.add_argument("--count-sqrt", type=int, default=0, help="counted pass (work per sample for the roofline) on the same pixels with this samples_sqrt instead of the frame's (roofline.counted_on says so); 0 = the frame's own")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -351,8 +363,8 @@ def main():
     ap.add_argument("--dynamic-blocks", action="store_true",
                     help="N > 1: hand blocks out from a shared counter as MPICoordinator does (default: block i to rank i mod N)")
     ap.add_argument("--verify", action="store_true",
-                    help="after the timed steps rank 0 renders the frame once more in a single launch and compares (bit for bit); on by default when N > 1")
-    ap.add_argument("--no-verify", action="store_true", help="N > 1: skip that comparison and the oracle rows")
+                    help="after the timed steps rank 0 renders the frame once more in a single launch and compares (bit for bit); on by default with --full when N > 1")
+    ap.add_argument("--no-verify", action="store_true", help="N > 1, --full: skip that comparison and the oracle rows")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant / scheduler tuning word for wpt_set_launch_config (experiments)")
     ap.add_argument("--wavefront", type=int, default=0, help="wpt_set_wavefront mode: 0 = the library decides, 1 = wavefront kernels wherever they exist, 2 = never")
     ap.add_argument("--wide-walk", action="store_true", help="wpt_set_walk(WPT_WALK_WIDE): scenes fetched from HBM are walked over the tree collapsed by one level (experiments)")
@@ -360,7 +372,8 @@ def main():
     ap.add_argument("--top-nodes", type=int, default=-1, help="BVH nodes stored level by level in front of the array (wpt_set_top_nodes; experiments)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the frame of each workload's last timed step to DIR/<workload>.npy (float32; frames over "
-                         "%d pixels as a fixed, seeded sample of that many), for output-by-output comparison of two builds" % DUMP_MAX_PIXELS)
+                         "%d pixels as a fixed, seeded sample of that many), for output-by-output comparison of two builds; the "
+                         "secondary workloads' frames too (N = 1, default workload), rendered once without --full" % DUMP_MAX_PIXELS)
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -440,7 +453,7 @@ def main():
     lib_id = library_identity()
     dscene = device.DeviceScene(scene)
     params = host.default_params()
-    cpu_seconds = 0.0 if args.no_cpu_baseline else args.cpu_seconds
+    cpu_seconds = args.cpu_seconds if args.full and not args.no_cpu_baseline else 0.0
     config = {"workload": name, "width": width, "height": height, "spp": spp, "triangles": int(scene.d.tri_count), "bvh_nodes": int(scene.d.node_count)}
 
     def barrier():
@@ -451,24 +464,26 @@ def main():
     sharded = distributed or args.force_blocks > 0
     if not sharded:
         # ---- N = 1: one render call per step ----
-        m, frame = measure_one_gpu(name, w, scene, dscene, args.steps, args.warmup, cpu_seconds, lib_id, torch, device, host, barrier, walk_flags, count_sqrt=args.count_sqrt or None)
+        m, frame = measure_one_gpu(name, w, scene, dscene, args.steps, args.warmup, cpu_seconds, lib_id, torch, device, host, barrier, walk_flags,
+                                   count_sqrt=args.count_sqrt or None, full=args.full)
         if args.dump_outputs:
             dump_frame(args.dump_outputs, name, frame)
-        verified = None
         out = {
             "metric": "Msamples/s", "value": m["value"], "unit": "Msamples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": dict(config, parallelism="1 launch"), "roofline": m["roofline"], "frame_finite": m["frame_finite"],
+            "config": dict(config, parallelism="1 launch"), "frame_finite": m["frame_finite"],
             "scene_build_s": t_build, "library": lib_id,
         }
-        for k in ("cpu_baseline", "parity"):
+        for k in ("roofline", "cpu_baseline", "parity"):
             if k in m:
                 out[k] = m[k]
-        if not args.no_secondary and args.workload == "cornell_1024x1024_1024spp_ggx_glass" and not args.samples_sqrt:
+        if (args.full or args.dump_outputs) and not args.no_secondary and args.workload == "cornell_1024x1024_1024spp_ggx_glass" and not args.samples_sqrt:
             # the workloads whose scene is fetched from HBM under the same clock (the primary one lives in LDS): BASELINE
-            # configs[2], [3] and [4], each with its own roofline, CPU baseline and parity
+            # configs[2], [3] and [4], each with its own roofline, CPU baseline and parity (--full); a plain run renders
+            # each frame once, untimed, for --dump-outputs alone
             del dscene, frame
-            out["secondary"] = []
+            if args.full:
+                out["secondary"] = []
             for sname0, ssteps, swarm, scount in SECONDARIES:
                 if sname0 in args.skip_secondary:
                     continue
@@ -477,14 +492,20 @@ def main():
                 sscene = build_scene(sw)
                 t2 = time.perf_counter() - t2
                 sd = device.DeviceScene(sscene)
-                sm, sframe = measure_one_gpu(sname, sw, sscene, sd, ssteps if sname0 != SECONDARY else args.secondary_steps, swarm, min(cpu_seconds, 8.0), lib_id,
-                                             torch, device, host, walk_flags=walk_flags, count_sqrt=scount)
+                if args.full:
+                    sm, sframe = measure_one_gpu(sname, sw, sscene, sd, ssteps if sname0 != SECONDARY else args.secondary_steps, swarm, min(cpu_seconds, 8.0),
+                                                 lib_id, torch, device, host, walk_flags=walk_flags, count_sqrt=scount, full=True)
+                    sm.update(workload=sname, unit="Msamples/s", scene_build_s=t2,
+                              config={"workload": sname, "width": sw["width"], "height": sw["height"], "spp": sw["samples_sqrt"] ** 2,
+                                      "triangles": int(sscene.d.tri_count), "bvh_nodes": int(sscene.d.node_count), "parallelism": "1 launch"})
+                    out["secondary"].append(sm)
+                else:
+                    # a render call writes every pixel of its block, so one call leaves the frame the last timed step would
+                    sframe = torch.zeros((sw["height"], sw["width"], 3), dtype=torch.float32, device="cuda")
+                    sd.render_block_into(sframe, sw["samples_sqrt"], None, params, None, torch.cuda.current_stream())
+                    torch.cuda.synchronize()
                 if args.dump_outputs:
                     dump_frame(args.dump_outputs, sname, sframe)
-                sm.update(workload=sname, unit="Msamples/s", scene_build_s=t2,
-                          config={"workload": sname, "width": sw["width"], "height": sw["height"], "spp": sw["samples_sqrt"] ** 2,
-                                  "triangles": int(sscene.d.tri_count), "bvh_nodes": int(sscene.d.node_count), "parallelism": "1 launch"})
-                out["secondary"].append(sm)
                 del sd, sframe, sscene
                 torch.cuda.empty_cache()
         print(json.dumps(out), flush=True)
@@ -493,10 +514,11 @@ def main():
     # ---- N > 1 (or its rehearsal on one GPU): the frame is shared out ----
     frame = torch.zeros((height, width, 3), dtype=torch.float32, device="cuda")
     main_stream = torch.cuda.current_stream()
-    counters = torch.zeros(6, dtype=torch.int64, device="cuda")
-    dscene.render_block_into(frame, ssqrt, None, params, counters, main_stream)  # counted pass (untimed), the whole frame
-    torch.cuda.synchronize()
-    cnt = dict(zip(("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters"), [int(x) for x in counters.cpu().tolist()]))
+    if args.full:
+        counters = torch.zeros(6, dtype=torch.int64, device="cuda")
+        dscene.render_block_into(frame, ssqrt, None, params, counters, main_stream)  # counted pass (untimed), the whole frame
+        torch.cuda.synchronize()
+        cnt = dict(zip(("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters"), [int(x) for x in counters.cpu().tolist()]))
     kernel_ms = []   # (event, event, samples) per render call on this rank, timed steps only
     reduce_ms = []   # host-timed seconds of the frame reduce per timed step
     from wurblpt_amd import blocks
@@ -570,7 +592,7 @@ def main():
         dump_frame(args.dump_outputs, name, frame)  # rank 0 holds the reduced frame of the last step
     verified = None
     parity = None
-    if (args.verify or (distributed and not args.no_verify)) and rank == 0:
+    if (args.verify or (distributed and args.full and not args.no_verify)) and rank == 0:
         # the sharded frame (rank 0 holds the sum of all ranks' bands) against one launch over all pixels
         whole = torch.zeros_like(frame)
         dscene.render_block_into(whole, ssqrt, None, params, None, main_stream)
@@ -584,19 +606,6 @@ def main():
             parity = parity_of(frame.cpu().numpy(), oframe, ostart, opixels, width)
     if rank == 0:
         total_samples = float(pixels) * spp * args.steps
-        avg_ms = sum(m for m, _ in launches) / max(1, len(launches))
-        avg_samples = sum(s for _, s in launches) / max(1, len(launches))
-        basis = ("algorithmic bytes of one launch / its duration (HIP events on the launch's stream); a launch is one render call: "
-                 "kernel_launches_per_launch launches of the kernel(s), whose durations add up to it")
-        if launches and (args.dynamic_blocks or not distributed):
-            # this rank's launches overlap on its streams: price its whole share against the timed region instead
-            avg_ms = elapsed * 1e3
-            avg_samples = sum(s for _, s in launches)
-            basis = "algorithmic bytes of rank 0's %d overlapping launches / the timed region" % len(launches)
-        roofline = roofline_of(name, scene, cnt, spp, ssqrt, avg_ms, avg_samples, len(launches), basis, lib_id, device,
-                               with_pmc=(True if world == 1 else "per_sample"))
-        if world > 1:
-            roofline["note"] = roofline.get("note", "") + "; rank 0's launch over its share of the frame, per-sample counters from the one-GPU PMC pass of the whole frame"
         out = {
             "metric": "Msamples/s", "value": total_samples / elapsed / 1e6, "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -606,7 +615,6 @@ def main():
                 "pixel blocks of %d from a shared counter over %d GPUs (%d streams each) + RCCL reduce" % (block_size, world, args.streams)
                 if (args.dynamic_blocks or not distributed) else
                 "bands of %d rows, band i to rank i mod %d, one launch per GPU + RCCL reduce" % (band_rows, world))),
-            "roofline": roofline,
             "frame_finite": ok,
             # what a step's time is made of, per rank: the rank's render call(s), then the reduce; the step ends with the slowest rank
             "per_rank": per_rank,
@@ -615,6 +623,21 @@ def main():
             # the barrier the other ranks wait at before they map it
             "scene_build_s": t_build, "library": lib_id, "cpu_baseline": None,
         }
+        if args.full:
+            avg_ms = sum(m for m, _ in launches) / max(1, len(launches))
+            avg_samples = sum(s for _, s in launches) / max(1, len(launches))
+            basis = ("algorithmic bytes of one launch / its duration (HIP events on the launch's stream); a launch is one render call: "
+                     "kernel_launches_per_launch launches of the kernel(s), whose durations add up to it")
+            if launches and (args.dynamic_blocks or not distributed):
+                # this rank's launches overlap on its streams: price its whole share against the timed region instead
+                avg_ms = elapsed * 1e3
+                avg_samples = sum(s for _, s in launches)
+                basis = "algorithmic bytes of rank 0's %d overlapping launches / the timed region" % len(launches)
+            out["roofline"] = roofline_of(name, scene, cnt, spp, ssqrt, avg_ms, avg_samples, len(launches), basis, lib_id, device,
+                                          with_pmc=(True if world == 1 else "per_sample"))
+            if world > 1:
+                out["roofline"]["note"] = (out["roofline"].get("note", "") + "; rank 0's launch over its share of the frame, per-sample "
+                                           "counters from the one-GPU PMC pass of the whole frame")
         if verified is not None:
             out["frame_equals_single_launch"] = verified
         if parity is not None:

@@ -1,8 +1,8 @@
 """The N > 1 path of bench.py with RCCL underneath, on the one GPU of a test box: torch.distributed.run starts ONE rank and
 bench.py --force-distributed takes the code path of N ranks -- init_process_group("nccl", device_id=...), one builder per node
 (scene file in /dev/shm), this rank's interleaved bands in one launch (wpt_render_bands_device), blocks.reduce_frame on the
-device tensor (an RCCL reduce over a one-rank communicator), blocks.rank_stats (an RCCL all_gather), the comparison with a single
-launch and rows of the oracle.  MPICoordinator semantics (mpi.hpp:215-288: getBlock / submitBlock) as bands + one reduce."""
+device tensor (an RCCL reduce over a one-rank communicator), blocks.rank_stats (an RCCL all_gather), and with --full the comparison
+with a single launch and rows of the oracle.  MPICoordinator semantics (mpi.hpp:215-288: getBlock / submitBlock) as bands + one reduce."""
 import json
 import os
 import socket
@@ -31,7 +31,7 @@ def test_one_rank_under_the_launcher_runs_the_nccl_path(workload, extra):
     env.pop("WPT_BENCH_DEVICE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-distributed", "--steps", "2", "--warmup", "1",
-           "--workload", workload, "--cpu-seconds", "3"] + extra
+           "--workload", workload, "--full", "--cpu-seconds", "3"] + extra
     r = subprocess.run(cmd, capture_output=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout.decode()[-2000:] + r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
