@@ -520,11 +520,16 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
  *                           counters, count the product's shortened walks instead
  *   WPT_WALK_TRIANGLES_AS_GIVEN  scenes uploaded from now on keep their triangle records in the caller's order (measurements; by
  *                           default the records are stored in the order of their leaves in the tree, so that a subtree's
- *                           triangles share cache lines) */
+ *                           triangles share cache lines)
+ *   WPT_WALK_SELECT_CORNERS  plain product launches of the kernel with the scene in LDS keep the triangle test that selects the
+ *                           corners' components by the ray's axes (A/B runs and tests; by default such a launch holds the
+ *                           corners in LDS in all three rotations of (x, y, z), where that still leaves four workgroups per
+ *                           compute unit, and a test reads them in its ray's order: wpt_kernel_form) */
 #define WPT_WALK_WIDE 1u
 #define WPT_WALK_FULL_SHADOW 2u
 #define WPT_WALK_COUNT_PRODUCT 4u
 #define WPT_WALK_TRIANGLES_AS_GIVEN 8u
+#define WPT_WALK_SELECT_CORNERS 16u
 wpt_status wpt_set_walk(uint32_t flags);
 /* Which form of the path tracer renders frames whose scene is fetched from HBM (results do not depend on it):
  * mode 0 = the library decides per launch (default), 1 = the wavefront form wherever it exists (trace and shade as two
@@ -555,6 +560,9 @@ wpt_status wpt_set_scheduler_stats(unsigned long long* stats_device);
 
 /* Kernel family of the process's most recent render call (for profile matching). */
 const char* wpt_kernel_name(void);
+/* The form of that family's kernel the most recent render call launched, where a family has more than one: "rotated corners" for
+ * the kernel with the scene in LDS that holds the corners in all three rotations (WPT_WALK_SELECT_CORNERS above), otherwise "". */
+const char* wpt_kernel_form(void);
 /* What the reference records about a run for the CPU (wurblpt.hpp:393-400,425-435: COMPILER, CPU_MODEL), for the device:
  * marketing name and architecture of HIP device `device` ("AMD Instinct MI355X (gfx950:...)", or "" if there is none), and
  * the compiler and options the kernels were built with.  The strings live until the next call from the same thread. */

@@ -257,6 +257,24 @@ WPT_D float hotSpotPdfValue(float4 g0, float4 g1, float4 g2, f3 org, f3 dir, con
     return value;
 }
 
+/* the same for corners and origin in the order of the direction's kz (FEAT_ROTATED kernels; triangleTestRotated); `face` and
+ * `dir` are in world order */
+WPT_D float hotSpotPdfValueRotated(float4 g0, float4 g1, float4 g2, f3 orgR, f3 dir, const RayAux& h, float4 face)
+{
+    Candidate c;
+    float value = 0.0f;
+    if (triangleTestRotated(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), orgR, h.Sx, h.Sy, h.inv.x,
+            (uint32_t)h.k & (uint32_t)RAY_FLIP, 0.0f, k_maxval, c)) {
+        float cosine = __builtin_fabsf(dot(mk3(face.x, face.y, face.z), neg(dir)));
+        float distance_squared = c.a * c.a;
+        value = distance_squared / (cosine * face.w);
+    }
+    return value;
+}
+/* where the copy of the corners for rotation kz lies behind the stored one (kz = 2), in quadwords: the LDS copy of a FEAT_ROTATED
+ * kernel holds the triangle positions three times, stored order, (y, z, x), (z, x, y) */
+WPT_D uint32_t rotatedCopyOffset(int kz, uint32_t triCount) { return (kz == 2 ? 0u : (uint32_t)(kz + 1)) * (3u * triCount); }
+
 /* HitableSphere::pdfValue (hitable_sphere.hpp:149-186) */
 WPT_CALL float spherePdfValue(const wpt_sphere& sp, const wpt_sphere& spHit, f3 org, f3 dir)
 {
@@ -308,6 +326,25 @@ WPT_CALL DirectionDraw sphereDirection(const wpt_sphere& sp, f3 org, Prng prng)
 template<uint32_t F, bool COUNT, class Tri4>
 WPT_D void hotSpotsMeanPdfPair(const SceneView& sv, Tri4 tri4, f3 org, f3 dirA, f3 dirB, PathHot& ps, LaneCounters& lc, float& meanA, float& meanB)
 {
+    if constexpr ((F & FEAT_ROTATED) != 0) {
+        /* corners in each direction's own component order: the hit point is permuted once per direction, and every light's
+         * corners come from the copy of that direction's kz (triangle lights at rest only: the Cornell class).  One direction
+         * after the other: the two share no corners here, and side by side their permuted values would not fit the registers. */
+        auto meanPdf = [&](f3 dir) {
+            const RayAux h = rayAuxRotated<true>(dir);
+            const f3 orgR = rotated(org, auxKz(h));
+            const uint32_t off = rotatedCopyOffset(auxKz(h), sv.triCount);
+            float sum = 0.0f;
+            for (uint32_t i = 0; i < sv.hotspotCount; i++) {
+                const uint32_t p = off + 3 * sv.hotspots[i].prim;
+                sum += hotSpotPdfValueRotated(tri4(p), tri4(p + 1), tri4(p + 2), orgR, dir, h, sv.hotspotFace[i]);
+            }
+            return sum * here(sv.invHotspotCount);
+        };
+        meanA = meanPdf(dirA);
+        meanB = meanPdf(dirB);
+        return;
+    }
     const RayAux hA = rayAux<true>(dirA), hB = rayAux<true>(dirB);
     float sumA = 0.0f, sumB = 0.0f;
     for (uint32_t i = 0; i < sv.hotspotCount; i++) {
@@ -629,7 +666,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
     const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
-    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
+    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
          * once (nothing has been written yet): the next round then runs it for two rounds' worth

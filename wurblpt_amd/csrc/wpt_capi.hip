@@ -176,6 +176,7 @@ uint32_t g_leafBias = 0;
  * block queue) reads on its main thread what the workers ran. */
 std::atomic<uint32_t> g_lastPasses{1};
 std::atomic<const char*> g_kernelName{nullptr};
+std::atomic<const char*> g_kernelForm{""}; /* wpt_kernel_form */
 uint32_t g_topNodes = 65536; /* nodes of a large tree that are stored level by level in front (wpt_set_top_nodes) */
 unsigned long long* g_schedStats = nullptr;
 /* wpt_set_wavefront: 0 = the library decides, 1 = wavefront wherever it exists, 2 = never; launch geometry (0 = defaults) */
@@ -1004,6 +1005,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         if (e == hipSuccess) {
             g_lastPasses.store(launches, std::memory_order_relaxed);
             g_kernelName.store("wf_trace + wf_shade", std::memory_order_relaxed);
+            g_kernelForm.store("", std::memory_order_relaxed);
             return WPT_OK;
         }
         /* The library's own choice must not fail where the single kernel would not: without the memory for the records
@@ -1022,6 +1024,17 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.cuCount = uint32_t(scene->cuCount);
     /* the material records join the scene in LDS where a quarter of a compute unit's 160 KiB holds a workgroup with them */
     args.materialsInLds = (!(g_variant & 0x80u) && COLD_BYTES + ldsBytes + size_t(scene->view.materialCount) * sizeof(wpt_material) <= LDS_BYTES_PER_WORKGROUP_AT_FOUR) ? 1u : 0u;
+    /* The corners in LDS three times, once per rotation of (x, y, z), so that a triangle test reads them in its ray's component
+     * order and selects nothing by axis (wpt_triangle.h, triangleTestRotated): plain product launches of the kernel with the scene in
+     * LDS, where the two extra copies still leave four workgroups per compute unit.  The copies come before the material records:
+     * those then stay in HBM unless they fit as well (the Cornell box: 40 768 of 40 960 bytes with the copies; DESIGN.md section 4
+     * has both measured).  wpt_set_walk(WPT_WALK_SELECT_CORNERS) keeps the kernel that selects. */
+    const size_t rotatedBytes = ldsBytes + 2 * size_t(scene->triCount) * 48;
+    const bool rotated = basic && lds && !count && !anim && !rgl && !transient && !views && !adaptive && !(g_walk & WPT_WALK_SELECT_CORNERS)
+            && COLD_BYTES + rotatedBytes <= LDS_BYTES_PER_WORKGROUP_AT_FOUR;
+    if (rotated)
+        args.materialsInLds = (!(g_variant & 0x80u) && COLD_BYTES + rotatedBytes + size_t(scene->view.materialCount) * sizeof(wpt_material) <= LDS_BYTES_PER_WORKGROUP_AT_FOUR) ? 1u : 0u;
+    g_kernelForm.store(rotated ? "rotated corners" : "", std::memory_order_relaxed);
     args.rowStop = samples_sqrt;
     args.carry = nullptr;
     args.cost = nullptr;
@@ -1110,7 +1123,9 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             else
                 launchFullRgl(a, grid, stream);
         } else {
-            if (basic && lds)
+            if (rotated)
+                launchBasicLdsRotated(a, grid, rotatedBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+            else if (basic && lds)
                 launchBasicLds(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (wide) /* also for the basic feature set: the wide walk exists in the all-features instantiations */
                 launchFullWide(a, grid, stream);
@@ -1682,7 +1697,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes)
 
 wpt_status wpt_set_walk(uint32_t flags)
 {
-    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN))
+    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     g_walk = flags;
     return WPT_OK;
@@ -1805,6 +1820,11 @@ const char* wpt_kernel_name(void)
     /* the kernel family of the process's most recent render call */
     const char* name = g_kernelName.load(std::memory_order_relaxed);
     return name ? name : "wpt_pathtrace";
+}
+
+const char* wpt_kernel_form(void)
+{
+    return g_kernelForm.load(std::memory_order_relaxed);
 }
 
 const char* wpt_device_name(int device)

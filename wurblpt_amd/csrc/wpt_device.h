@@ -24,52 +24,15 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_math.h"
+#include "wpt_triangle.h"
 #include "wpt_anim.h"
 #include "wpt_rgl.h"
 
 namespace wptd {
 
-#define WPT_D __device__ __forceinline__
 /* code that few lanes run and that is large: a real call, so that it does not take registers from the common path */
 #define WPT_CALL static inline __device__ __attribute__((noinline))
 
-constexpr float k_pi = 3.1415926535897932384626433832795029L;
-constexpr float k_pi_2 = 1.5707963267948966192313216916397514L;
-constexpr float k_pi_4 = 0.7853981633974483096156608458198757L;
-constexpr float k_inv_pi = 0.3183098861837906715377675267450287L;
-constexpr float k_maxval = 3.402823466e+38f;
-constexpr float k_epsilon = 1.1920928955078125e-07f;
-constexpr float k_ldeps = 1.084202172485504434e-19f; /* float(epsilon of long double), hitable_triangle.hpp:240 */
-
-struct f2 { float x, y; };
-struct f3 { float x, y, z; };
-struct f4 { float x, y, z, w; };
-
-/* comparison-based min / max, NaN behaviour of gvm.hpp:88,93 */
-WPT_D float fminr(float x, float y) { return x < y ? x : y; }
-WPT_D float fmaxr(float x, float y) { return x > y ? x : y; }
-WPT_D float clampr(float x, float lo, float hi) { return fminr(hi, fmaxr(lo, x)); }
-WPT_D float mixr(float x, float y, float a) { return x + a * (y - x); }
-
-WPT_D f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
-WPT_D f4 mk4(float x, float y, float z, float w) { f4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-WPT_D f3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
-WPT_D f4 ld4(const float* p) { return mk4(p[0], p[1], p[2], p[3]); }
-WPT_D f3 add(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-WPT_D f3 sub(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-WPT_D f3 mul(f3 a, f3 b) { return mk3(a.x * b.x, a.y * b.y, a.z * b.z); }
-WPT_D f3 neg(f3 a) { return mk3(-a.x, -a.y, -a.z); }
-WPT_D f3 scl(float s, f3 a) { return mk3(s * a.x, s * a.y, s * a.z); }    /* s * v */
-WPT_D f3 sclr(f3 a, float s) { return mk3(a.x * s, a.y * s, a.z * s); }   /* v * s */
-WPT_D f3 divs(f3 a, float s) { return mk3(a.x / s, a.y / s, a.z / s); }
-WPT_D f4 add(f4 a, f4 b) { return mk4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-WPT_D f4 sub(f4 a, f4 b) { return mk4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-WPT_D f4 mul(f4 a, f4 b) { return mk4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-WPT_D f4 scl(float s, f4 a) { return mk4(s * a.x, s * a.y, s * a.z, s * a.w); }
-WPT_D f4 sclr(f4 a, float s) { return mk4(a.x * s, a.y * s, a.z * s, a.w * s); }
-WPT_D f4 divs(f4 a, float s) { return mk4(a.x / s, a.y / s, a.z / s, a.w / s); }
-WPT_D float comp(f3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
-WPT_D float comp(f4 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : (i == 2 ? a.z : a.w)); }
 
 /* dot products accumulate from zero like gvm.hpp:1183-1189 (keeps -0 behaviour) */
 WPT_D float dot(f2 a, f2 b) { float d = 0.0f; d += a.x * b.x; d += a.y * b.y; return d; }
@@ -272,113 +235,6 @@ struct Ray {
     f3 o, d;
     f4 ri; /* refractiveIndex */
 };
-/* RayIntersectionHelper (hitable.hpp:66-113) */
-/* Kept per ray in registers while it traverses, so it is small: the axis permutation is
- * packed into one word (kx | ky << 2 | kz << 4) and S.z, which equals inv[kz], is not stored. */
-struct RayAux {
-    f3 inv;
-    int k;
-    float Sx, Sy;
-};
-WPT_D int auxKx(const RayAux& h) { return h.k & 3; }
-WPT_D int auxKy(const RayAux& h) { return (h.k >> 2) & 3; }
-WPT_D int auxKz(const RayAux& h) { return (h.k >> 4) & 3; }
-/* SHEAR_ONLY: for triangle tests alone (the pdf of a light), which read the reciprocal of the direction's largest
- * component and nothing else of `inv`: that one division instead of three, the same bits */
-template<bool SHEAR_ONLY = false> WPT_D RayAux rayAux(f3 dir)
-{
-    RayAux h;
-    if (!SHEAR_ONLY)
-        h.inv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-    float ax = __builtin_fabsf(dir.x), ay = __builtin_fabsf(dir.y), az = __builtin_fabsf(dir.z);
-    int kx, ky, kz;
-    if (az >= ay && az >= ax)
-        kz = 2;
-    else if (ay >= ax)
-        kz = 1;
-    else
-        kz = 0;
-    kx = kz + 1;
-    if (kx == 3)
-        kx = 0;
-    ky = kx + 1;
-    if (ky == 3)
-        ky = 0;
-    if (comp(dir, kz) < 0.0f) {
-        int tmp = kx;
-        kx = ky;
-        ky = tmp;
-    }
-    float invz;
-    if (SHEAR_ONLY) {
-        invz = 1.0f / comp(dir, kz);
-        h.inv = mk3(invz, invz, invz);
-    } else {
-        invz = comp(h.inv, kz);
-    }
-    h.Sx = comp(dir, kx) * invz;
-    h.Sy = comp(dir, ky) * invz;
-    h.k = kx | (ky << 2) | (kz << 4);
-    return h;
-}
-
-/* what survives of a triangle candidate: enough to rebuild the HitRecord later */
-struct Candidate {
-    uint32_t prim; /* 0xffffffff = no hit */
-    float a, invDet, U, V, W; /* det itself is not kept: its sign is the sign of invDet */
-};
-
-/* Watertight test (hitable_triangle.hpp:189-271).  Returns true and fills c when accepted. */
-WPT_D bool triangleTest(f3 v0, f3 v1, f3 v2, f3 org, const RayAux& h, float amin, float amax, Candidate& c)
-{
-    const f3 A = sub(v0, org);
-    const f3 B = sub(v1, org);
-    const f3 C = sub(v2, org);
-    const int kx = auxKx(h), ky = auxKy(h), kz = auxKz(h);
-    const float Sz = comp(h.inv, kz);
-    const float Akz = comp(A, kz), Bkz = comp(B, kz), Ckz = comp(C, kz);
-    const float Ax = comp(A, kx) - h.Sx * Akz;
-    const float Ay = comp(A, ky) - h.Sy * Akz;
-    const float Bx = comp(B, kx) - h.Sx * Bkz;
-    const float By = comp(B, ky) - h.Sy * Bkz;
-    const float Cx = comp(C, kx) - h.Sx * Ckz;
-    const float Cy = comp(C, ky) - h.Sy * Ckz;
-    float U = Cx * By - Cy * Bx;
-    float V = Ax * Cy - Ay * Cx;
-    float W = Bx * Ay - By * Ax;
-    if (__builtin_fabsf(U) < k_ldeps || __builtin_fabsf(V) < k_ldeps || __builtin_fabsf(W) < k_ldeps) {
-        double CxBy = (double)Cx * (double)By;
-        double CyBx = (double)Cy * (double)Bx;
-        U = (float)(CxBy - CyBx);
-        double AxCy = (double)Ax * (double)Cy;
-        double AyCx = (double)Ay * (double)Cx;
-        V = (float)(AxCy - AyCx);
-        double BxAy = (double)Bx * (double)Ay;
-        double ByAx = (double)By * (double)Ax;
-        W = (float)(BxAy - ByAx);
-    }
-    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f))
-        return false;
-    float det = U + V + W;
-    if (det == 0.0f)
-        return false;
-    const float Az = Sz * Akz;
-    const float Bz = Sz * Bkz;
-    const float Cz = Sz * Ckz;
-    const float T = U * Az + V * Bz + W * Cz;
-    const uint32_t sgn = wptm::float_to_bits(det) & 0x80000000u;
-    const float Ts = wptm::bits_to_float(wptm::float_to_bits(T) ^ sgn);
-    const float ds = wptm::bits_to_float(wptm::float_to_bits(det) ^ sgn);
-    if (Ts < amin * ds || Ts > amax * ds)
-        return false;
-    const float invDet = 1.0f / det;
-    c.a = invDet * T;
-    c.invDet = invDet;
-    c.U = U;
-    c.V = V;
-    c.W = W;
-    return true;
-}
 
 /* AABB::mayHit (aabb.hpp:70-86) written out with the reference's comparison chains, whose
  * results for NaN slab distances (0 * inf: origin on a slab plane, direction parallel to it)
@@ -458,7 +314,8 @@ enum {
     FEAT_TRANSIENT = 1024, /* transient film: contributions are also binned by optical path length (wpt_blocks.h, BinsView) */
     FEAT_SPOT = 2048,    /* LightSpot: emission inside a cone around the normal */
     FEAT_VIEWS = 4096,   /* a batch of views: every lane takes its camera from an array (wpt_pathtrace.inc.h, ViewsView) */
-    FEAT_ADAPTIVE = 8192 /* adaptive sampling: every lane takes its pixel's sample count from a map (wpt_pathtrace.inc.h, AdaptiveView) */
+    FEAT_ADAPTIVE = 8192, /* adaptive sampling: every lane takes its pixel's sample count from a map (wpt_pathtrace.inc.h, AdaptiveView) */
+    FEAT_ROTATED = 16384 /* scene in LDS with two more copies of the corners, rotated: triangle tests take them in the ray's component order (triangleTestRotated) */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */

@@ -189,6 +189,9 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     static_assert(!((F & FEAT_ADAPTIVE) && COUNT), "adaptive sampling has no counting build");
     constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
     constexpr bool ADAPTIVE = (F & FEAT_ADAPTIVE) != 0;
+    /* the corners in LDS three times, once per rotation of (x, y, z): a triangle test reads them in its ray's component order */
+    constexpr bool ROTATED = (F & FEAT_ROTATED) != 0;
+    static_assert(!ROTATED || (LDSSCENE && !(F & FEAT_ANIM)), "rotated copies of the corners: scenes at rest in LDS");
     /* node prefetch: for scenes in HBM (Sponza-class frame 3 % faster); not from LDS, where the fetch is short and the
      * registers that hold the node ahead lengthen every step (Cornell 4 % slower) */
     constexpr bool PREFETCH = !LDSSCENE && !WIDE;
@@ -204,7 +207,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
      * the single kernel 106.1 -> 112.5; 10 M triangles 67.97 -> 68.09).  With the scene in LDS the frame is bound by the
      * instructions its waves issue and the same costs (Cornell 1055.6 against 1038.7 / 1049.1 / 1036.0 with 8 / 16 / 24). */
     constexpr int NEE_IN_WALK = LDSSCENE ? 0 : 4;
-    /* [ math tables ][ cold path words: SLOT_COUNT x WG float4 ][ LDSSCENE: nodes, triangle positions ] */
+    /* [ math tables ][ cold path words: SLOT_COUNT x WG float4 ][ LDSSCENE: nodes, triangle positions (ROTATED: and their two
+     * rotated copies), material records where they fit ] */
     extern __shared__ float4 lds[];
     float4* const ldsCold = lds + TABLE_BYTES / 16;
     float4* const ldsScene = ldsCold + SLOT_COUNT * WG;
@@ -240,13 +244,23 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                     : make_float4(0.0f, 0.0f, __uint_as_float(nodeCount), __uint_as_float(nodeCount));
         for (uint32_t i = threadIdx.x; i < t4; i += WG)
             ldsScene[n4 + 2 + i] = sv.triGeom[i];
+        if (ROTATED) {
+            /* the copies for rays whose largest direction component is x (kz = 0: y, z, x) and y (kz = 1: z, x, y), records of the
+             * same shape behind the stored ones (rotatedCopyOffset); the stored order is that of kz = 2 */
+            for (uint32_t i = threadIdx.x; i < t4; i += WG) {
+                const float4 g = sv.triGeom[i];
+                ldsScene[n4 + 2 + t4 + i] = make_float4(g.y, g.z, g.x, g.w);
+                ldsScene[n4 + 2 + 2 * t4 + i] = make_float4(g.z, g.x, g.y, g.w);
+            }
+        }
+        const uint32_t c4 = ROTATED ? 3 * t4 : t4; /* quadwords of triangle positions in LDS */
         if (args.materialsInLds) {
             /* the material record is what a hit's shading waits for first: fetched from LDS through a generic pointer */
             const uint32_t m4 = sv.materialCount * (uint32_t)(sizeof(wpt_material) / 16);
             const float4* from = reinterpret_cast<const float4*>(sv.materials);
             for (uint32_t i = threadIdx.x; i < m4; i += WG)
-                ldsScene[n4 + 2 + t4 + i] = from[i];
-            svInLds.materials = reinterpret_cast<const wpt_material*>(ldsScene + n4 + 2 + t4);
+                ldsScene[n4 + 2 + c4 + i] = from[i];
+            svInLds.materials = reinterpret_cast<const wpt_material*>(ldsScene + n4 + 2 + c4);
         }
     }
     __syncthreads();
@@ -330,6 +344,10 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
      * keeps the leaf's index in leafNode (ldsStep below) */
     uint32_t node = LDSSCENE ? nodeCount : 0u, leafPrim = 0, leafNode = 0;
     float amax = k_maxval;
+    /* ROTATED: the ray's origin in the order of its kz and inv[kz], beside aux, whose Sx and Sy then are the unswapped shear
+     * constants and whose k is RAY_FLIP | the quadword offset of the ray's copy of the corners << 8 | RAY_MAY_NAN */
+    f3 orgRotated = mk3(0.0f, 0.0f, 0.0f);
+    float auxSz = 0.0f;
     /* WIDE: the child whose turn is next (reference, entry distance) waits in registers, so that a step starts with its node's
      * fetch and not with a load from the stack; the others wait on the stack in the reference's order */
     uint2 pend[WIDE ? WIDE_STACK : 1];
@@ -341,7 +359,15 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 
     /* start the traversal of the ray ps.o, ps.d */
     auto beginRay = [&]() {
-        aux = rayAux(ps.d);
+        if constexpr (ROTATED) {
+            aux = rayAuxRotated(ps.d);
+            const int kz = auxKz(aux);
+            orgRotated = rotated(ps.o, kz);
+            auxSz = comp(aux.inv, kz);
+            aux.k = (aux.k & RAY_FLIP) | (int)(rotatedCopyOffset(kz, sv.triCount) << 8);
+        } else {
+            aux = rayAux(ps.d);
+        }
         node = 0;
         amax = k_maxval;
         best.prim = NO_HIT;
@@ -541,6 +567,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                             /* HitableSphere::hit (hitable_sphere.hpp:104-147) */
                             c.invDet = c.U = c.V = c.W = 0.0f;
                             accepted = sphereTest(sphereNow<F>(sv, ps, sv.spheres[leafPrim & ~PRIM_SPHERE]), ps.o, ps.d, par.min_hit_distance, amax, c.a);
+                        } else if constexpr (ROTATED) {
+                            /* the corners from the copy in the ray's order: the same three reads, no select by axis */
+                            const uint32_t at = (((uint32_t)aux.k >> 8) & 0x7fffffu) + 3 * leafPrim;
+                            const float4 g0 = tri4(at), g1 = tri4(at + 1), g2 = tri4(at + 2);
+                            accepted = triangleTestRotated(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), orgRotated, aux.Sx, aux.Sy,
+                                    auxSz, (uint32_t)aux.k & (uint32_t)RAY_FLIP, par.min_hit_distance, amax, c);
                         } else {
                             const float4 g0 = tri4(3 * leafPrim), g1 = tri4(3 * leafPrim + 1), g2 = tri4(3 * leafPrim + 2);
                             f3 v0 = mk3(g0.x, g0.y, g0.z), v1 = mk3(g1.x, g1.y, g1.z), v2 = mk3(g2.x, g2.y, g2.z);
@@ -849,6 +881,7 @@ void launchGroundTruth(const GroundTruthArgs& args, hipStream_t stream);
 constexpr uint32_t ORDER_BUCKETS = 128;
 void launchOrderBuild(const KernelArgs& args, uint32_t* order, uint32_t* work, hipStream_t stream);
 void launchBasicLds(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchBasicLdsRotated(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream); /* sceneLdsBytes: with the two rotated copies of the corners */
 void launchBasic(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchBasicCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFull(const KernelArgs& args, dim3 grid, hipStream_t stream);
