@@ -149,7 +149,10 @@ enum {
     WPT_MATF_HAVE_NIR = 1,
     WPT_MATF_CHROMATIC_DISPERSION = 2,
     WPT_MATF_DIFFUSE_TEX_HAS_ALPHA = 4,
-    WPT_MATF_SPECULAR_TEX_HAS_ALPHA = 8
+    WPT_MATF_SPECULAR_TEX_HAS_ALPHA = 8,
+    /* WPT_MAT_LIGHT_SPOT only: the light is a time-of-flight light (light_tof.hpp).  v[0] = (0, 0, 0, radiance); a texture
+     * scales the fourth channel by its red value; what a ToF sensor receives from it is modulated (wpt_render_tof_block) */
+    WPT_MATF_TOF_LIGHT = 16
 };
 /* Tagged material record (128 bytes).  Member use per type:
  *  LAMBERTIAN     v[0]=albedo                      tex[0]=albedo
@@ -385,6 +388,44 @@ wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera
         const wpt_params* params, const float* edges_host, uint32_t bin_count,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         float* block_rgb, float* block_bins);
+
+/* ---- time-of-flight sensor (amplitude-modulated continuous wave; sensor_tof_amcw.hpp) ----
+ * One launch renders phase_count phase images of one exposure interval.  Plane j holds, per pixel, the energies (a_j, b_j, total)
+ * that the sensor's two taps and their sum collect with the phase offset tau[j]: every contribution adds
+ *   energy = radiance.w * 1000 * pixel_area * 0.5 * exposure_time  to total (radiance.w: the near infrared channel),
+ *   0.5 * energy * (1 + t) to a and 0.5 * energy * (1 - t) to b, with
+ *   t = contrast * cos(tau[j] + 2 pi * opl.w * frac_modfreq_c)  for light emitted by a ToF light (WPT_MATF_TOF_LIGHT), else 0
+ * (sensor_tof_amcw.hpp:227-252 in float, operation for operation), and the plane is the sum times 1 / samples.  A pixel's paths
+ * depend on its index only, so plane j is bit-identical to a launch with phase_count = 1 and tau[0] = tau[j], and `total` is the
+ * same in every plane.  The sensor has no gates: `params` must carry the default ones (min_dist_to_light = min_path_len = 0,
+ * max_dist_to_light = max_path_len = FLT_MAX).  Single kernel, one device.  Refused with WPT_ERR_INVALID_ARGUMENT before a
+ * device is needed: NULL pointers, a phase count outside 1 .. WPT_TOF_MAX_PHASES, sensor values that are NaN or infinite, a
+ * contrast outside [0, 1], gates that are not the defaults. */
+#define WPT_TOF_MAX_PHASES 8u
+typedef struct wpt_tof_sensor {
+    float pixel_area;     /* [um^2] */
+    float exposure_time;  /* of one phase image [us] */
+    float contrast;       /* achievable pixel contrast in [0, 1] */
+    float frac_modfreq_c; /* (float)(modulation frequency [Hz] / speed of light [m/s]), the division made in double */
+    uint32_t phase_count;
+    float tau[WPT_TOF_MAX_PHASES]; /* phase offsets; SensorTofAmcw: tau[j] = j * (2.0f * pi) / phase_count */
+} wpt_tof_sensor;
+
+/* Asynchronous on `hip_stream`.  `planes_device`: float[phase_count][height][width][3] in device memory, full frames,
+ * row 0 = bottom.  Only the block's pixels are written, in every plane. */
+wpt_status wpt_render_tof_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const wpt_tof_sensor* sensor, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* planes_device, void* hip_stream);
+
+/* Synchronous form with MPICoordinator::submitBlock semantics: `block_planes` receives phase_count * block_size * 3 floats
+ * in host memory (plane j's block_size * 3 floats after plane j-1's). */
+wpt_status wpt_render_tof_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const wpt_tof_sensor* sensor, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* block_planes);
+
+/* One contribution on the CPU, by the code the kernels run (wpt_tof.h): adds to acc = (a, b, total) of phase `phase`. */
+wpt_status wpt_tof_accumulate_host(const wpt_tof_sensor* sensor, uint32_t phase, float radiance_w, float opl_w, int is_tof_light,
+        float acc[3]);
 
 /* ---- a batch of views ----
  * One launch renders view_count frames of one scene: frame v from cameras_host[v], with one parameter set, one frame size and one

@@ -1,0 +1,462 @@
+"""The time-of-flight sensor without a GPU: the accumulate rule of wpt_tof.h against the formula, LightTof's record, the
+helpers of SensorTofAmcw against numpy float32, the refusals of wpt_render_tof_block*, and the example application, which
+builds against the public headers and stops without a device."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from wurblpt_amd import _abi, device, host
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "wurblpt_amd", "lib")
+F32 = np.float32
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def compile_cpp(tmp_path, source, name):
+    exe = str(tmp_path / name)
+    cmd = ["g++", "-std=c++20", "-O1", "-fopenmp", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), source,
+           "-L" + LIB, "-lwurblpt_hip", "-Wl,-rpath," + LIB, "-o", exe]
+    subprocess.run(cmd, check=True, timeout=600)
+    return exe
+
+
+_libm = C.CDLL("libm.so.6")
+_libm.cosf.restype = C.c_float
+_libm.cosf.argtypes = [C.c_float]
+
+
+def cosf(x):
+    return F32(_libm.cosf(F32(x)))
+
+
+def bits(x):
+    return np.asarray(x, dtype=np.float32).view(np.uint32)
+
+
+def formula(sensor, phase, radiance_w, opl_w, is_tof_light, acc):
+    """the issue's formula in numpy float32, every operation rounded, libm's cosf"""
+    irradiance = F32(radiance_w) * F32(1000.0)
+    power = irradiance * F32(sensor.pixel_area)
+    energy = power * F32(0.5) * F32(sensor.exposure_time)
+    half = F32(0.5) * energy
+    t = F32(0.0)
+    if is_tof_light:
+        two_pi = F32(2.0) * F32(np.pi)
+        shift = two_pi * F32(opl_w) * F32(sensor.frac_modfreq_c)
+        t = F32(sensor.contrast) * cosf(F32(sensor.tau[phase]) + shift)
+    a = F32(acc[0]) + half * (F32(1.0) + t)
+    b = F32(acc[1]) + half * (F32(1.0) - t)
+    total = F32(acc[2]) + energy
+    return np.array([a, b, total], dtype=np.float32)
+
+
+def test_frac_modfreq_c_is_the_double_division_rounded_once():
+    for f in (10e6, 20e6):
+        s = host.tof_sensor(modulation_frequency=f)
+        assert bits(s.frac_modfreq_c) == bits(F32(f / 299792458.0))
+    s = host.tof_sensor()
+    assert abs(s.frac_modfreq_c - 0.03335641) < 5e-9
+    assert int(bits(s.frac_modfreq_c)) == int(bits(F32(10e6 / 299792458.0))) == 0x3D08A0BB
+    # the float division would differ for some frequencies: the record must hold the double one
+    assert s.phase_count == 4 and s.pixel_area == 144.0 and s.exposure_time == 1000.0 and s.contrast == 0.75
+
+
+def test_tau_is_the_reference_float_order():
+    two_pi = F32(2.0) * F32(np.pi)
+    for n in (4, 8):
+        s = host.tof_sensor(phase_image_count=n)
+        for j in range(n):
+            assert bits(s.tau[j]) == bits(F32(j) * two_pi / F32(n)), (n, j)
+    with pytest.raises(ValueError):
+        host.tof_sensor(phase_image_count=9)
+
+
+def test_rule_equals_the_formula_bit_for_bit():
+    """at least 1e5 seeded contributions through wpt_tof_accumulate_host, accumulated as the kernels do, against the formula:
+    ToF lights and others, radiance 0, the environment's FLT_MAX path length, contrast 0 and 1, every tau of 4 and 8 phases"""
+    rng = np.random.default_rng(20260117)
+    with np.errstate(over="ignore", invalid="ignore"):
+        sensors = []
+        for n in (4, 8):
+            for contrast in (0.0, 0.75, 1.0):
+                for f in (10e6, 20e6, 100e6):
+                    sensors.append(host.tof_sensor(phase_image_count=n, contrast=contrast, modulation_frequency=f,
+                                                   exposure_time=float(F32(rng.uniform(100, 2000))), pixel_area=float(F32(rng.uniform(9, 400)))))
+        n_cases, n_bad = 0, 0
+        per = 100000 // sum(s.phase_count for s in sensors) + 1
+        for s in sensors:
+            for phase in range(s.phase_count):
+                acc = np.zeros(3, dtype=np.float32)
+                ref = acc.copy()
+                for k in range(per):
+                    kind = k % 8
+                    radiance = float(F32(rng.uniform(0.0, 5.0))) if kind != 1 else 0.0
+                    opl = float(F32(rng.uniform(0.0, 60.0))) if kind != 2 else FLT_MAX
+                    tof = 0 if kind in (2, 3) else 1       # the environment (no hit) is never a ToF light
+                    if kind == 4:
+                        opl = float(F32(rng.uniform(0.0, 1e5)))   # phases of many turns
+                    device.tof_accumulate_host(s, phase, radiance, opl, tof, acc)
+                    ref = formula(s, phase, radiance, opl, tof, ref)
+                    n_cases += 1
+                    n_bad += int((bits(acc) != bits(ref)).any())
+                    acc[:] = ref        # one contribution is compared at a time
+                assert np.isfinite(ref).all() and ref[2] > 0
+        assert n_cases >= 100000 and n_bad == 0, (n_cases, n_bad)
+
+
+def test_rule_special_cases():
+    s = host.tof_sensor(contrast=0.0)
+    acc = device.tof_accumulate_host(s, 2, 1.5, 3.25, 1, np.zeros(3, dtype=np.float32))
+    assert acc[0] == acc[1] == F32(0.5) * acc[2] and acc[2] == F32(1.5) * F32(1000) * F32(144) * F32(0.5) * F32(1000)
+    s = host.tof_sensor()
+    acc = device.tof_accumulate_host(s, 1, 2.0, FLT_MAX, 0, np.zeros(3, dtype=np.float32))   # the environment
+    assert acc[0] == acc[1] == F32(0.5) * acc[2] and acc[2] > 0
+    acc = device.tof_accumulate_host(s, 0, 0.0, 4.0, 1, np.ones(3, dtype=np.float32))         # radiance 0 adds nothing
+    assert (acc == 1.0).all()
+    # phase 0 at path length 0: all of the contrast goes to tap a
+    acc = device.tof_accumulate_host(s, 0, 1.0, 0.0, 1, np.zeros(3, dtype=np.float32))
+    assert acc[0] == F32(0.875) * acc[2] and acc[1] == F32(0.125) * acc[2]
+    L = device.lib()
+    for bad in ((None, 0), (s, 4), (s, 77)):
+        st = L.wpt_tof_accumulate_host(C.byref(bad[0]) if bad[0] is not None else None, bad[1], 1.0, 1.0, 1, C.c_void_p(acc.ctypes.data))
+        assert st == 1
+    assert L.wpt_tof_accumulate_host(C.byref(s), 0, 1.0, 1.0, 1, None) == 1
+
+
+RECORD_PROGRAM = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <wurblpt/wurblpt.hpp>
+#include <wurblpt/tof.hpp>
+using namespace WurblPT;
+static void print(const wpt_material& m)
+{
+    unsigned int b[5];
+    memcpy(b, m.v[0], 16);
+    memcpy(b + 4, m.f, 4);
+    printf("%u %u %d %d %d %08x %08x %08x %08x %08x\n", m.type, m.flags, m.tex[0], m.tex[1], m.normal_tex, b[0], b[1], b[2], b[3], b[4]);
+}
+int main(int argc, char* argv[])
+{
+    /* argv: radiance angle; prints LightTof, LightTof with a texture, then the records of a scene with a two-sided ToF light */
+    if (argc != 3)
+        return 2;
+    const float radiance = strtof(argv[1], nullptr), angle = strtof(argv[2], nullptr);
+    TextureChecker checker(vec3(1.0f), vec3(0.0f));
+    FlattenContext ctx;
+    wpt_material m;
+    if (!LightTof(radiance, angle).describe(m, ctx))
+        return 1;
+    print(m);
+    if (!LightTof(radiance, angle, &checker).describe(m, ctx))
+        return 1;
+    print(m);
+    Scene scene;
+    Material* front = scene.take(new LightTof(radiance, angle));
+    Material* back = scene.take(new MaterialLambertian(vec4(0.0f)));
+    Material* both = scene.take(new MaterialTwoSided(front, back));
+    scene.take(new MeshInstance(scene.take(generateQuad()), both), HotSpot);
+    scene.updateBVH();
+    FlatScene flat;
+    if (!scene.flatten(flat))
+        return 1;
+    printf("%zu\n", flat.materials.size());
+    for (const wpt_material& fm : flat.materials)
+        print(fm);
+    const wpt_scene_desc desc = flat.desc();
+    wpt_scene* uploaded = nullptr;
+    const wpt_status st = wpt_scene_upload(&desc, &uploaded);
+    printf("upload %d %s\n", (int)st, st == WPT_OK ? "ok" : wpt_last_error());
+    if (uploaded)
+        wpt_scene_free(uploaded);
+    return 0;
+}
+"""
+
+
+def test_light_tof_record(tmp_path):
+    """type 9 with flag 16, v[0] = (0, 0, 0, radiance), f[0] = cosf(0.5f * angle) bit for bit, tex[0] the texture; inside a
+    MaterialTwoSided the nesting is intact; upload validation accepts the scene"""
+    src = tmp_path / "record.cpp"
+    src.write_text(RECORD_PROGRAM)
+    exe = compile_cpp(tmp_path, str(src), "record")
+    for radiance, angle in ((40.0 / (4.0 * np.pi), np.radians(120.0)), (1.0, 0.3), (7.5, 3.1), (0.125, 1.0471976)):
+        radiance, angle = F32(radiance), F32(angle)
+        out = subprocess.run([exe, repr(float(radiance)), repr(float(angle))], capture_output=True, check=True, timeout=60)
+        lines = [line.split() for line in out.stdout.decode().strip().split("\n")]
+        plain, textured = lines[0], lines[1]
+        assert plain[:5] == ["9", "16", "-1", "-1", "-1"]
+        assert [int(x, 16) for x in plain[5:9]] == [0, 0, 0, int(bits(radiance))]
+        assert int(plain[9], 16) == int(bits(cosf(F32(0.5) * angle))), (angle, plain)
+        assert textured[:3] == ["9", "16", "0"] and textured[5:] == plain[5:]
+        count = int(lines[2][0])
+        mats = lines[3:3 + count]
+        two = [m for m in mats if m[0] == "7"]
+        assert len(two) == 1
+        front, back = mats[int(two[0][2])], mats[int(two[0][3])]
+        assert front[:2] == ["9", "16"] and front[5:] == plain[5:] and back[0] == "1" and back[1] == "1"     # Lambertian(vec4): NIR given
+        assert [m[1] for m in mats if m[0] != "9"] in (["1", "0"], ["0", "1"])                           # the flag on the light only
+        upload = lines[3 + count]
+        assert upload[0] == "upload" and (upload[1] == "0" or "HIP" in " ".join(upload) or "ROCm" in " ".join(upload)), upload
+
+
+def _materials(sc):
+    return [sc.d.materials[i] for i in range(sc.d.material_count)]
+
+
+def _upload_status(sc):
+    handle = C.c_void_p()
+    st = device.lib().wpt_scene_upload(sc.desc, C.byref(handle))
+    if st == 0 and handle.value:        # only where a GPU is present
+        device.lib().wpt_scene_free(handle)
+    return st, device.lib().wpt_last_error().decode()
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5])
+def test_tof_scenes_and_their_twins(variant):
+    times = (0.5, 0.501) if variant == 1 else (0.0, 0.0)
+    sc = host.tof_scene(24, 16, variant, 0, *times)
+    lights = [m for m in _materials(sc) if m.type == _abi.MAT_LIGHT_SPOT]
+    assert len(lights) == 1 and lights[0].flags == _abi.MATF_TOF_LIGHT and list(lights[0].v[0])[:3] == [0.0, 0.0, 0.0] and lights[0].v[0][3] > 0
+    assert sc.d.hotspot_count == 2
+    assert (sc.d.animation_count > 0) == (variant == 1)
+    assert (lights[0].tex[0] >= 0) == (variant == 5)        # the textured light: its texture is the record's tex[0]
+    st, message = _upload_status(sc)
+    assert st == 0 or "no HIP device" in message or "no ROCm" in message, message
+    r = lights[0].v[0][3]
+    for twin, emit in ((1, r), (2, 0.0)):
+        tw = host.tof_scene(24, 16, variant, twin, *times)
+        assert tw.d.tri_count == sc.d.tri_count and tw.d.node_count == sc.d.node_count and tw.d.material_count == sc.d.material_count
+        spot = [m for m in _materials(tw) if m.type == _abi.MAT_LIGHT_SPOT]
+        assert len(spot) == 1 and spot[0].flags == 0 and list(spot[0].v[0])[:3] == [emit] * 3
+        assert bits(spot[0].f[0]) == bits(lights[0].f[0]) and spot[0].tex[0] == lights[0].tex[0]
+    if variant == 3:
+        glass = [m for m in _materials(sc) if m.type == _abi.MAT_GLASS]
+        assert len(glass) == 1 and list(glass[0].v[1]) == [1.5, 1.5, 1.5, F32(1.3)] and glass[0].flags == 0
+    if variant == 2:    # small enough for the kernel that keeps the scene in LDS
+        assert sc.d.node_count * 32 + sc.d.tri_count * 48 <= 20 * 1024
+
+
+def test_upload_validation_refuses_the_flag_on_other_types_and_unknown_types():
+    sc = host.tof_scene(16, 16, 2)
+    mats = _materials(sc)
+    for m in mats:
+        if m.type == _abi.MAT_LIGHT_SPOT:
+            continue
+        m.flags |= _abi.MATF_TOF_LIGHT
+        st, message = _upload_status(sc)
+        assert st == 1 and "time-of-flight" in message, (m.type, st, message)
+        m.flags &= ~_abi.MATF_TOF_LIGHT
+    st, message = _upload_status(sc)
+    assert st == 0 or "no HIP device" in message or "no ROCm" in message, message
+    sc = host.spot_scene(16, 16, 0)
+    for t in (10, 99):
+        sc.d.materials[0].type = t
+        st, message = _upload_status(sc)
+        assert st == 4 and "material type" in message, (t, st, message)
+
+
+HELPERS_PROGRAM = r"""
+#include <cstdio>
+#include <cstring>
+#include <wurblpt/wurblpt.hpp>
+#include <wurblpt/tof.hpp>
+using namespace WurblPT;
+static unsigned int b(float x) { unsigned int u; memcpy(&u, &x, 4); return u; }
+int main()
+{
+    SensorTofAmcw s(4, 2);
+    printf("defaults %u %08x %.17g %08x %08x %08x %08x %08x %08x %d\n", s.phaseImageCount, b(s.wavelength), s.modulationFrequency, b(s.exposureTime),
+            b(s.readoutTime), b(s.pauseTime), b(s.pixelArea), b(s.contrast), b(s.quantumEfficiency), s.maxElectrons);
+    printf("consts %.17g %08x %08x %08x\n", speedOfLight, b(hc), b(s.fracModfreqC()), b(s.fracCModfreq()));
+    for (unsigned int n : { 4u, 8u }) {
+        s.phaseImageCount = n;
+        printf("tau");
+        for (unsigned int j = 0; j < n; j++)
+            printf(" %08x", b(s.tau(j)));
+        printf("\n");
+    }
+    s.phaseImageCount = 4;
+    printf("timing %08x %08x %08x", b(s.frameDuration()), b(s.fps()), b(s.phaseImageDuration()));
+    s.setPauseTimeForFPS(30.0f);
+    printf(" %08x %08x %08x\n", b(s.pauseTime), b(s.frameDuration()), b(s.fps()));
+    s.modulationFrequency = 20e6;
+    const wpt_tof_sensor all = s.describe(), one = s.describe(3);
+    printf("record %u %08x %08x %08x %08x %08x %u %08x\n", all.phase_count, b(all.pixel_area), b(all.exposure_time), b(all.contrast),
+            b(all.frac_modfreq_c), b(all.tau[3]), one.phase_count, b(one.tau[0]));
+    /* hand-made phase images, 8 pixels: the four quadrants, the axes, no difference at all, and just below a full turn */
+    const float re[8] = { 1.0f, -1.0f, -1.0f, 1.0f, 1.0f, 0.0f, 0.0f, 1.0f };
+    const float im[8] = { 1.0f, 1.0f, -1.0f, -1.0f, 0.0f, 2.5f, 0.0f, -1e-7f };
+    Array<float> phases[4] = { Array<float>(4, 2, 4), Array<float>(4, 2, 4), Array<float>(4, 2, 4), Array<float>(4, 2, 4) };
+    for (int i = 0; i < 8; i++) { /* D0 - D2 = re, D3 - D1 = im */
+        phases[0][i][0] = 0.5f * re[i] + 0.25f;
+        phases[2][i][0] = -0.5f * re[i] + 0.25f;
+        phases[3][i][0] = 0.5f * im[i] + 0.25f;
+        phases[1][i][0] = -0.5f * im[i] + 0.25f;
+    }
+    const Array<float> r = s.result(phases);
+    for (int i = 0; i < 8; i++)
+        printf("result %08x %08x %08x %08x %08x %08x %08x %08x\n", b(phases[0][i][0]), b(phases[1][i][0]), b(phases[2][i][0]), b(phases[3][i][0]),
+                b(r[i][0]), b(r[i][1]), b(r[i][2]), b(r[i][3]));
+    /* phase() without shot noise */
+    Array<float> energies(4, 2, 3);
+    for (int i = 0; i < 8; i++) {
+        energies[i][0] = 1.0e5f * float(i) + 3.0f;
+        energies[i][1] = 7.0e4f * float(8 - i);
+        energies[i][2] = energies[i][0] + energies[i][1];
+    }
+    energies[7][0] = 1.0e9f; /* saturates */
+    const Array<float> p = s.phase(energies, 0.0f);
+    for (int i = 0; i < 8; i++)
+        printf("phase %08x %08x %08x %08x %08x %08x\n", b(energies[i][0]), b(energies[i][1]), b(p[i][0]), b(p[i][1]), b(p[i][2]), b(p[i][3]));
+    return 0;
+}
+"""
+
+
+def _f(word):
+    return np.array([int(word, 16)], dtype=np.uint32).view(np.float32)[0]
+
+
+def test_sensor_helpers_against_numpy_float32(tmp_path):
+    src = tmp_path / "helpers.cpp"
+    src.write_text(HELPERS_PROGRAM)
+    exe = compile_cpp(tmp_path, str(src), "helpers")
+    out = subprocess.run([exe], capture_output=True, check=True, timeout=60).stdout.decode().strip().split("\n")
+    rows = [line.split() for line in out]
+    d = rows[0]
+    assert d[1] == "4" and float(d[3]) == 10e6 and d[10] == "100000"
+    assert [_f(d[k]) for k in (2, 4, 5, 6, 7, 8, 9)] == [F32(880), F32(1000), F32(1000), F32(42000), F32(144), F32(0.75), F32(0.8)]
+    c = rows[1]
+    assert float(c[1]) == 299792458.0 and int(c[2], 16) == int(bits(F32(1.98644582)))
+    assert int(c[3], 16) == int(bits(F32(10e6 / 299792458.0))) and int(c[4], 16) == int(bits(F32(299792458.0 / 10e6)))
+    two_pi = F32(2.0) * F32(np.pi)
+    for row, n in ((rows[2], 4), (rows[3], 8)):
+        assert [int(x, 16) for x in row[1:]] == [int(bits(F32(j) * two_pi / F32(n))) for j in range(n)]
+    t = rows[4]
+    frame = (F32(4) * (F32(1000) + F32(1000)) + F32(42000)) / F32(1e6)
+    assert int(t[1], 16) == int(bits(frame)) and int(t[2], 16) == int(bits(F32(1.0) / frame))
+    assert int(t[3], 16) == int(bits((F32(1000) + F32(1000)) / F32(1e6)))
+    pause = F32(1e6) / F32(30.0) - F32(4) * (F32(1000) + F32(1000))
+    frame30 = (F32(4) * (F32(1000) + F32(1000)) + pause) / F32(1e6)
+    assert int(t[4], 16) == int(bits(pause)) and int(t[5], 16) == int(bits(frame30)) and int(t[6], 16) == int(bits(F32(1.0) / frame30))
+    rec = rows[5]
+    ref = host.tof_sensor(modulation_frequency=20e6)
+    assert rec[1] == "4" and rec[7] == "1"
+    assert [int(x, 16) for x in rec[2:7]] == [int(bits(v)) for v in (ref.pixel_area, ref.exposure_time, ref.contrast, ref.frac_modfreq_c, ref.tau[3])]
+    assert int(rec[8], 16) == int(bits(ref.tau[3]))
+    # result(): the C++ member and device.tof_result against each other and against the formula in float32
+    res = [r for r in rows if r[0] == "result"]
+    assert len(res) == 8
+    D = np.array([[_f(r[1 + k]) for r in res] for k in range(4)], dtype=np.float32)
+    got = np.array([[_f(r[5 + k]) for r in res] for k in range(4)], dtype=np.float32)
+    dist, amp, inten, shift = device.tof_result(D, 20e6)
+    for name, mine, theirs in (("distance", dist, got[0]), ("amplitude", amp, got[1]), ("intensity", inten, got[2]), ("phase shift", shift, got[3])):
+        assert (bits(mine) == bits(theirs)).all(), (name, mine, theirs)
+    quadrant = np.array([0.25, 0.75, 1.25, 1.75]) * np.pi
+    assert np.allclose(shift[:4], quadrant, atol=1e-6) and shift[4] == 0 and abs(shift[5] - np.pi / 2) < 1e-6
+    assert shift[6] == 0 and dist[6] == 0 and amp[6] == 0                       # no difference at all
+    assert 2 * np.pi - 1e-6 < shift[7] <= F32(2 * np.pi) + F32(1e-6)              # wraps to just below a full turn
+    assert np.allclose(dist, 299792458.0 / 20e6 * shift / (4 * np.pi), rtol=1e-6)
+    assert np.allclose(inten, 0.5, atol=1e-6)
+    # scaling the phase images leaves distance and phase shift as they are
+    d2, _, _, s2 = device.tof_result(D * F32(4.0), 20e6)
+    assert (bits(d2) == bits(dist)).all() and (bits(s2) == bits(shift)).all()
+    # phase() with shotNoiseFactor 0
+    ph = [r for r in rows if r[0] == "phase"]
+    for r in ph:
+        e = np.array([_f(r[1]), _f(r[2])], dtype=np.float32)
+        electrons = F32(0.8) * F32(880) * e / F32(1.98644582) / F32(10000)
+        dig = np.clip(electrons, F32(0), F32(100000)) / F32(100000)
+        want = [dig[0] - dig[1], dig[0] + dig[1], dig[0], dig[1]]
+        assert [int(x, 16) for x in r[3:7]] == [int(bits(v)) for v in want], r
+    assert _f(ph[7][5]) == 1.0      # the saturated tap
+
+
+def test_render_tof_refuses_bad_calls_without_a_device():
+    L = device.lib()
+    sc = host.tof_scene(16, 16, 2)
+    cam = sc.camera
+    good = host.default_params()
+    sensor = host.tof_sensor()
+    buf = (C.c_float * (8 * 16 * 16 * 3))()
+    scene = C.c_void_p(0x1000)        # never followed: every refusal below comes before the scene is looked at
+
+    def both(scene_, cam_, params_, sensor_, planes_):
+        a = L.wpt_render_tof_block_device(scene_, cam_, C.byref(params_) if params_ is not None else None,
+                                          C.byref(sensor_) if sensor_ is not None else None, 16, 16, 1, 0, 256, planes_, None)
+        m1 = L.wpt_last_error().decode()
+        b = L.wpt_render_tof_block(scene_, cam_, C.byref(params_) if params_ is not None else None,
+                                   C.byref(sensor_) if sensor_ is not None else None, 16, 16, 1, 0, 256, planes_)
+        m2 = L.wpt_last_error().decode()
+        assert a == b == 1, (a, b, m1, m2)
+        return m1
+
+    planes = C.cast(buf, C.c_void_p)
+    assert "NULL" in both(None, cam, good, sensor, planes)
+    assert "NULL" in both(scene, None, good, sensor, planes)
+    assert "NULL" in both(scene, cam, None, sensor, planes)
+    assert "NULL" in both(scene, cam, good, None, planes)
+    assert "NULL" in both(scene, cam, good, sensor, None)
+    for count in (0, 9, 1000):
+        s = _abi.TofSensor.from_buffer_copy(sensor)
+        s.phase_count = count
+        assert "phase count" in both(scene, cam, good, s, planes)
+    for field in ("pixel_area", "exposure_time", "contrast", "frac_modfreq_c"):
+        for value in (float("nan"), float("inf"), float("-inf")):
+            s = _abi.TofSensor.from_buffer_copy(sensor)
+            setattr(s, field, value)
+            assert "NaN or infinite" in both(scene, cam, good, s, planes), (field, value)
+    s = _abi.TofSensor.from_buffer_copy(sensor)
+    s.tau[3] = float("nan")
+    assert "NaN or infinite" in both(scene, cam, good, s, planes)
+    s.tau[3] = 0.0
+    s.tau[7] = float("nan")          # behind the phase count: not looked at, so the call gets as far as the next check
+    s.contrast = 1.5
+    assert "contrast" in both(scene, cam, good, s, planes)
+    for contrast in (-0.01, 1.0001):
+        s = _abi.TofSensor.from_buffer_copy(sensor)
+        s.contrast = contrast
+        assert "contrast" in both(scene, cam, good, s, planes)
+    for field, value in (("min_dist_to_light", 0.5), ("max_dist_to_light", 100.0), ("min_path_len", 1.0), ("max_path_len", 50.0)):
+        p = host.default_params()
+        setattr(p, field, value)
+        assert "gates" in both(scene, cam, p, sensor, planes), field
+
+
+def test_tof_camera_example_builds_and_needs_a_device(tmp_path):
+    """One include plus <wurblpt/tof.hpp> and one library, -Wall -Wextra -Werror; without a GPU the program says so and stops,
+    nothing is rendered on the CPU"""
+    import torch
+    exe = compile_cpp(tmp_path, os.path.join(ROOT, "examples", "tof_camera.cpp"), "tof_camera")
+    if torch.cuda.is_available():
+        return          # it builds; with a device present its run is the gpu test's
+    r = subprocess.run([exe, "16", "12", "1", str(tmp_path)], capture_output=True, timeout=120)
+    assert r.returncode != 0 and b"no HIP device" in r.stderr
+    assert not os.path.exists(str(tmp_path / "result.pfm"))
+
+
+def test_tof_header_stays_out_of_the_main_header():
+    """wurblpt.hpp does not pull the time-of-flight classes in (the reference's two ToF applications keep failing on
+    SensorTofAmcw through it, as tests/test_reference_apps.py requires)"""
+    text = open(os.path.join(ROOT, "include", "wurblpt", "wurblpt.hpp")).read()
+    assert "tof.hpp" not in text and "SensorTofAmcw" not in text
+
+
+def test_existing_translation_units_are_recorded_unchanged():
+    """profiles/tof_code_objects.txt, written by tools/code_object_compare.sh: every translation unit the parent commit had
+    compiles to the same gfx950 code object from this tree's sources, and the four time-of-flight units are new"""
+    rows = [line.split(" : ") for line in open(os.path.join(ROOT, "profiles", "tof_code_objects.txt")) if not line.startswith("#")]
+    verdict = {r[0]: r[-1].strip() for r in rows}
+    new = sorted(u for u, v in verdict.items() if v == "new")
+    assert new == ["wpt_k_basic_lds_tof", "wpt_k_full_anim_tof", "wpt_k_full_rgl_anim_tof", "wpt_k_full_tof"]
+    assert all(v == "same" for u, v in verdict.items() if u not in new), verdict
+    makefile = open(os.path.join(ROOT, "wurblpt_amd", "csrc", "Makefile")).read()
+    units = {w[len("$(BUILD)/"):-2] for w in makefile.split() if w.startswith("$(BUILD)/wpt_") and w.endswith(".o")}
+    hip_units = {u for u in units if os.path.exists(os.path.join(ROOT, "wurblpt_amd", "csrc", u + ".hip"))}
+    assert hip_units - {"wpt_wavefront_host"} <= set(verdict), sorted(hip_units - set(verdict))

@@ -9,6 +9,8 @@ WPT_ABI_VERSION = 5
 WPT_OK = 0
 
 NODE_INNER, NODE_TRIANGLE, NODE_SPHERE, NODE_EMPTY = 0, 1, 2, 3
+MATF_TOF_LIGHT = 16
+TOF_MAX_PHASES = 8
 MAT_NONE, MAT_LAMBERTIAN, MAT_LIGHT_DIFFUSE, MAT_MIRROR, MAT_GGX, MAT_GLASS, MAT_MODPHONG, MAT_TWOSIDED, MAT_RGL, MAT_LIGHT_SPOT = range(10)
 
 
@@ -108,6 +110,12 @@ class Params(C.Structure):
                 ("min_path_len", C.c_float), ("max_path_len", C.c_float), ("t0", C.c_float), ("t1", C.c_float)]
 
 
+class TofSensor(C.Structure):
+    """wpt_tof_sensor: the time-of-flight sensor's constants and the phase offsets of the phase images of one launch"""
+    _fields_ = [("pixel_area", C.c_float), ("exposure_time", C.c_float), ("contrast", C.c_float), ("frac_modfreq_c", C.c_float),
+                ("phase_count", C.c_uint32), ("tau", C.c_float * TOF_MAX_PHASES)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")]
 
@@ -120,5 +128,5 @@ STRUCT_SIZES = {
     "wpt_instance": (Instance, 48), "wpt_sphere": (Sphere, 48), "wpt_hotspot": (Hotspot, 116), "wpt_material": (Material, 128),
     "wpt_texture": (Texture, 88), "wpt_rgl_warp": (RglWarp, 76), "wpt_rgl_brdf": (RglBrdf, 388), "wpt_camera": (Camera, 140), "wpt_params": (Params, 40),
     "wpt_keyframe": (Keyframe, 44), "wpt_animation": (Animation, 8),
-    "wpt_counters": (Counters, 48),
+    "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
 }

@@ -26,6 +26,7 @@
 
 #include "wpt_device.h"
 #include "wpt_lens.h"
+#include "wpt_tof.h"
 
 namespace wptk {
 
@@ -75,7 +76,9 @@ template<bool COUNT> WPT_D void sec(LaneCounters& lc, int k, bool mine = true)
  * sample = the next sample's stratum, column | row << 16 (row == samplesSqrt: all done); pixel = x | y << 16
  * (launches check samples_sqrt, width and height against 65535): no division per sample.
  * opticalPathLength and the next-event factor have three channels here: SensorRGB reads channels 0..2 only
- * (sensor_rgb.hpp:63-80), and nothing else reads their fourth. */
+ * (sensor_rgb.hpp:63-80), and nothing else reads their fourth.  FEAT_TOF kernels: the time-of-flight sensor reads the fourth
+ * channel only (sensor_tof_amcw.hpp:227-252), so there the three floats of opl and of neeFactor all hold the fourth
+ * channel's value (sensorChannels below), and acc holds the taps a, b and their total. */
 enum { SLOT_PRNG = 0, SLOT_ATT = 1, SLOT_RI = 2, SLOT_NEXTATT = 3, SLOT_ACC = 4, SLOT_OPL = 5, SLOT_NEE = 6, SLOT_SRDIR = 7, SLOT_COUNT = 8 };
 
 struct Slot {
@@ -438,11 +441,70 @@ WPT_D int binOf(const BinsView& b, float x)
     return (int)k;
 }
 
+/* The channels of a four-channel path value that the launch's sensor reads, for the three floats a slot has room for:
+ * x, y, z for the RGB sensors; the fourth (near infrared) in all three for the time-of-flight sensor */
+template<uint32_t F> WPT_D f3 sensorChannels(f4 v)
+{
+    if constexpr ((F & FEAT_TOF) != 0)
+        return mk3(v.w, v.w, v.w);
+    else
+        return mk3(v.x, v.y, v.z);
+}
+/* ... and back: the next-event factor from its slot as the four-channel value that multiplies the light's emission */
+template<uint32_t F> WPT_D f4 neeFactorOf(const Slot& nee)
+{
+    if constexpr ((F & FEAT_TOF) != 0)
+        return mk4(0.0f, 0.0f, 0.0f, nee.x);
+    else
+        return mk4(nee.x, nee.y, nee.z, 0.0f);
+}
+
+/* Material::isTofLight of a resolved material, for the kernels that ask (the others do not read the flags for it) */
+template<uint32_t F> WPT_D bool isTofLight(const wpt_material& m)
+{
+    if constexpr ((F & FEAT_TOF) != 0)
+        return (m.flags & WPT_MATF_TOF_LIGHT) != 0;
+    else
+        return false;
+}
+
 /* Sensor::accumulateRadiance of the launch: the frame's accumulator as above and, in FEAT_TRANSIENT kernels, the bins --
  * behind the same distance gate, by each channel's own path length (the path-length gate of `par` is the frame's only).
- * Where the three channels' lengths are equal (everything but dispersive glass) the bin is looked up once. */
-template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, const BinsView& bv, f3 opl, float distanceToLight, f4 radiance, PS& ps)
+ * Where the three channels' lengths are equal (everything but dispersive glass) the bin is looked up once.
+ *
+ * FEAT_TOF kernels: SensorTofAmcw::accumulateRadiance (wpt_tof.h).  `opl.x` is the fourth channel of the optical path length,
+ * `tofLight` says whether the hit that emitted is a ToF light's (Material::isTofLight of the resolved material); no gate.  The
+ * launch describes its sensor in the BinsView: `edges` are the sensor's constants and the phases' tau (wpttof::C_*), `binCount`
+ * the number of phase images.  One phase lives in the accumulator slot and leaves through the frame like an RGB pixel; several
+ * live in `bins` like the transient film's planes, [phase][pixel][a, b, total], each plane fed by the very operations of the
+ * one-phase launch with its tau (the cosine is evaluated per phase; `total` is the same sequence of additions in every plane). */
+template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, const BinsView& bv, f3 opl, float distanceToLight, f4 radiance, PS& ps,
+        bool tofLight = false)
 {
+    if constexpr ((F & FEAT_TOF) != 0) {
+        const float* const c = bv.edges;
+        const float energy = wpttof::energy(c[wpttof::C_PIXEL_AREA], c[wpttof::C_EXPOSURE_TIME], radiance.w);
+        if (bv.binCount == 1) {
+            Slot acc = ps.get(SLOT_ACC);
+            const float t = tofLight ? wpttof::modulation(c[wpttof::C_CONTRAST], c[wpttof::C_FRAC_MODFREQ_C], c[wpttof::C_TAU], opl.x) : 0.0f;
+            wpttof::add(energy, t, acc.x, acc.y, acc.z);
+            ps.set3(SLOT_ACC, mk3(acc.x, acc.y, acc.z));
+        } else if (energy != 0.0f) {
+            /* (a contribution of no energy -- the emission of every hit that is no light -- would add 0 to sums that are never
+             * negative: the planes keep their bits, and their memory is left alone) */
+            const uint32_t pxy = ps.getW(SLOT_SRDIR);
+            float* p = bv.bins + 3 * ((size_t)(pxy >> 16) * bv.width + (pxy & 0xffffu));
+            for (uint32_t j = 0; j < bv.binCount; j++, p += bv.stride) {
+                const float t = tofLight ? wpttof::modulation(c[wpttof::C_CONTRAST], c[wpttof::C_FRAC_MODFREQ_C], c[wpttof::C_TAU + j], opl.x) : 0.0f;
+                float a = p[0], b = p[1], total = p[2];
+                wpttof::add(energy, t, a, b, total);
+                p[0] = a;
+                p[1] = b;
+                p[2] = total;
+            }
+        }
+        return;
+    }
     if constexpr ((F & FEAT_ADAPTIVE) != 0) {
         /* accumulateRadiance, each addition made to the sample's own sum as well (PathLdsSum), behind the same gates */
         if (!(distanceToLight >= par.min_dist_to_light && distanceToLight <= par.max_dist_to_light))
@@ -650,7 +712,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     ray.ri = ps.get4(SLOT_RI);
     const Slot oplSlot = ps.get(SLOT_OPL);
     const uint32_t pathComponent = oplSlot.w;
-    const f3 opl = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(best.a, mk3(ray.ri.x, ray.ri.y, ray.ri.z)));
+    const f3 opl = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(best.a, sensorChannels<F>(ray.ri)));
     if (!(pathComponent + 1 < par.max_path_components))
         return NEXT_NEW;
     long long tSection = 0;
@@ -666,7 +728,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
     const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
-    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED)) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
+    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED | ((F & FEAT_TOF) ? (FEAT_TOF | FEAT_SPOT | FEAT_TWOSIDED) : 0u))) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
          * once (nothing has been written yet): the next round then runs it for two rounds' worth
@@ -713,7 +775,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     const f4 att = ps.get4(SLOT_ATT);
     {
         f4 rad = mul(att, materialEmitted<F>(sv, m, h, ray.d));
-        accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps);
+        accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps, isTofLight<F>(m));
     }
     section(2);
     if (sr.type == SCATTER_NONE) {
@@ -767,8 +829,9 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
             sec<COUNT>(lc, SEC_NEE_SETUP, dpdf > 0.0f);
             if (dpdf > 0.0f) {
                 const f4 neeFactor = sclr(divs(mul(att, directAtt), directPdf), powerHeuristicWeight(directPdf, dpdf));
+                const f3 neeChannels = sensorChannels<F>(neeFactor);
                 Slot nee;
-                nee.x = neeFactor.x; nee.y = neeFactor.y; nee.z = neeFactor.z;
+                nee.x = neeChannels.x; nee.y = neeChannels.y; nee.z = neeChannels.z;
                 nee.w = hotSpotPrim;
                 ps.set(SLOT_NEE, nee);
                 if (MERGED) {
@@ -800,7 +863,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
         materialEval<F>(sv, m, ray, h, lightDir, directAtt, dpdf, mc);
         if (dpdf > 0.0f) {
             const f4 neeFactor = sclr(divs(mul(att, directAtt), directPdf), powerHeuristicWeight(directPdf, dpdf));
-            ps.set3(SLOT_NEE, mk3(neeFactor.x, neeFactor.y, neeFactor.z));
+            ps.set3(SLOT_NEE, sensorChannels<F>(neeFactor));
             if (MERGED) {
                 ps.neeO = h.p;
                 ps.neeD = lightDir;
@@ -842,15 +905,15 @@ WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS&
         if (best.prim == nee.w) {
             Hit lh = finishHit<F>(sv, best, ps.o, ps.d, ps.time, tri4);
             const wpt_material& lm = resolveMaterial<F>(sv, lh.material, lh);
-            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh, ps.d));
+            f4 rad = mul(neeFactorOf<F>(nee), materialEmitted<F>(sv, lm, lh, ps.d));
             const f4 ri = ps.get4(SLOT_RI);
-            f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, mk3(ri.x, ri.y, ri.z)));
-            accumulate<F>(par, bins, oplLight, lh.a, rad, ps);
+            f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, sensorChannels<F>(ri)));
+            accumulate<F>(par, bins, oplLight, lh.a, rad, ps, isTofLight<F>(lm));
         }
     } else if (F & FEAT_ENVMAP) {
         if (best.prim == NO_HIT) {
             const Slot nee = ps.get(SLOT_NEE);
-            f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), envL(sv, ps.d));
+            f4 rad = mul(neeFactorOf<F>(nee), envL(sv, ps.d));
             accumulate<F>(par, bins, mk3(k_maxval, k_maxval, k_maxval), k_maxval, rad, ps);
         }
     }

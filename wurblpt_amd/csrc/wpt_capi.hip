@@ -290,6 +290,8 @@ wpt_status validate(const wpt_scene_desc* d)
         const wpt_material& m = d->materials[i];
         if (m.type > WPT_MAT_LIGHT_SPOT)
             return fail(WPT_ERR_UNSUPPORTED, "material type is not known to the kernel");
+        if ((m.flags & WPT_MATF_TOF_LIGHT) && m.type != WPT_MAT_LIGHT_SPOT)
+            return fail(WPT_ERR_INVALID_ARGUMENT, "only a spot light can be a time-of-flight light (WPT_MATF_TOF_LIGHT)");
         if (m.type == WPT_MAT_RGL) {
             if (m.tex[0] < 0 || uint32_t(m.tex[0]) >= d->rgl_count)
                 return fail(WPT_ERR_INVALID_ARGUMENT, "material references a measured BRDF outside the array");
@@ -886,8 +888,9 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         uint32_t band_pixels, uint32_t band_first, uint32_t band_stride,
         float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr,
-        const wptk::ViewsView* views = nullptr, const wptk::AdaptiveView* adaptive = nullptr)
+        const wptk::ViewsView* views = nullptr, const wptk::AdaptiveView* adaptive = nullptr, bool tof = false)
 {
+    /* (tof: a launch for the time-of-flight sensor, which `transient` then describes -- wpt_blocks.h, accumulate) */
     if (!scene || !camera || !params || !(frame_device || transient))
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
@@ -974,7 +977,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     args.waitBelow = waitBelowChoices[(g_variant >> 2) & 0x3u];
     /* kernel choice.  Low nibble of the variant word: 1 = keep the scene in HBM, 2 = all features. */
     const uint32_t force = g_variant & 0x3u;
-    const bool basic = (need & ~FEAT_BASIC) == 0 && force != 2;
+    /* (the time-of-flight kernel with the scene in LDS knows spot lights and two-sided materials besides) */
+    const bool basic = (need & ~(tof ? FEAT_BASIC | FEAT_SPOT | FEAT_TWOSIDED : FEAT_BASIC)) == 0 && force != 2;
     const bool lds = smallScene && force != 1;
     const bool rgl = (need & FEAT_RGL) != 0; /* measured BRDFs have their own instantiation */
     /* Pixel pool: frames with more pixels than the device has lanes at once are handed out pixel by pixel (the launchers
@@ -1047,7 +1051,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     /* the transient film: the LDS kernel for the Cornell class, the all-features kernel for other scenes at rest, the moving-scene
      * kernels for moving scenes and for measured BRDFs */
     const bool transientLds = transient && basic && lds && !anim && !rgl;
-    if (transient)
+    if (transient && !tof)
         g_kernelName.store(transientLds ? "wpt_pathtrace, transient, scene in LDS"
                 : rgl ? "wpt_pathtrace, transient, measured BRDFs"
                 : anim ? "wpt_pathtrace, transient, all features, moving scenes" : "wpt_pathtrace, transient, all features", std::memory_order_relaxed);
@@ -1066,8 +1070,22 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 : rgl ? "wpt_pathtrace, adaptive, measured BRDFs"
                 : anim ? "wpt_pathtrace, adaptive, all features, moving scenes"
                 : basic ? "wpt_pathtrace, adaptive, basic" : "wpt_pathtrace, adaptive, all features", std::memory_order_relaxed);
+    /* the time-of-flight sensor: the same four kinds */
+    if (tof)
+        g_kernelName.store(transientLds ? "wpt_pathtrace, time of flight, scene in LDS"
+                : rgl ? "wpt_pathtrace, time of flight, measured BRDFs"
+                : anim ? "wpt_pathtrace, time of flight, all features, moving scenes" : "wpt_pathtrace, time of flight, all features", std::memory_order_relaxed);
     auto launch = [&](const wptk::KernelArgs& a) {
-        if (adaptive) {
+        if (tof) {
+            if (transientLds)
+                launchBasicLdsTof(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+            else if (rgl)
+                launchFullRglAnimTof(a, grid, stream);
+            else if (anim)
+                launchFullAnimTof(a, grid, stream);
+            else
+                launchFullTof(a, grid, stream);
+        } else if (adaptive) {
             if (adaptiveLds)
                 launchBasicLdsAdaptive(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
@@ -1577,6 +1595,133 @@ wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera,
         if (p)
             (void)hipFree(p);
     return st;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* refuses a bad time-of-flight call before a device is needed */
+wpt_status tofCheck(const void* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor, const void* planes)
+{
+    if (!scene || !camera || !params || !sensor || !planes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: NULL argument");
+    if (sensor->phase_count == 0 || sensor->phase_count > WPT_TOF_MAX_PHASES)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: phase count must lie in 1 .. " + std::to_string(WPT_TOF_MAX_PHASES));
+    bool finite = std::isfinite(sensor->pixel_area) && std::isfinite(sensor->exposure_time) && std::isfinite(sensor->contrast)
+            && std::isfinite(sensor->frac_modfreq_c);
+    for (uint32_t j = 0; j < sensor->phase_count; j++)
+        finite = finite && std::isfinite(sensor->tau[j]);
+    if (!finite)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: a sensor value is NaN or infinite");
+    if (!(sensor->contrast >= 0.0f && sensor->contrast <= 1.0f))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: contrast must lie in [0, 1]");
+    if (params->min_dist_to_light != 0.0f || params->max_dist_to_light != FLT_MAX || params->min_path_len != 0.0f || params->max_path_len != FLT_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: it has no gates (the distance and path length gates must be the defaults)");
+    return WPT_OK;
+}
+
+/* one time-of-flight launch.  One phase: the kernel keeps the taps in the pixel's accumulator and writes the plane as an RGB
+ * launch writes its frame.  Several: the planes' block is zeroed, rendered into and scaled, all in stream order, as the
+ * transient film's.  `planes` is plane 0's pixel 0 with `stride` floats between planes. */
+wpt_status tofLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* planes, size_t stride,
+        hipStream_t stream)
+{
+    const wpt_status checked = tofCheck(scene, camera, params, sensor, planes);
+    if (checked != WPT_OK)
+        return checked;
+    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
+    if (uint64_t(width) * height > 0xffffffffull || uint64_t(block_start) + block_size > uint64_t(width) * height)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
+    if (block_size == 0)
+        return WPT_OK;
+    const uint32_t phases = sensor->phase_count;
+    float consts[wpttof::C_TAU + WPT_TOF_MAX_PHASES] = {};
+    consts[wpttof::C_PIXEL_AREA] = sensor->pixel_area;
+    consts[wpttof::C_EXPOSURE_TIME] = sensor->exposure_time;
+    consts[wpttof::C_CONTRAST] = sensor->contrast;
+    consts[wpttof::C_FRAC_MODFREQ_C] = sensor->frac_modfreq_c;
+    for (uint32_t j = 0; j < phases; j++)
+        consts[wpttof::C_TAU + j] = sensor->tau[j];
+    float* dConsts = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dConsts), sizeof(consts), stream));
+    hipError_t e = hipMemcpyAsync(dConsts, consts, sizeof(consts), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && phases > 1)
+        e = hipMemset2DAsync(planes + size_t(block_start) * 3, stride * sizeof(float), 0, size_t(block_size) * 3 * sizeof(float), phases, stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(dConsts, stream);
+        return fail(WPT_ERR_HIP, std::string("time-of-flight sensor: ") + hipGetErrorString(e));
+    }
+    wptk::BinsView bv = wptk::BinsView{};
+    bv.edges = dConsts;
+    bv.bins = planes;
+    bv.stride = stride;
+    bv.binCount = phases;
+    bv.width = width;
+    wpt_status st = renderLaunch(scene, camera, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0,
+            phases == 1 ? planes : nullptr, nullptr, stream, &bv, nullptr, nullptr, true);
+    if (st == WPT_OK && phases > 1) {
+        const uint64_t n = uint64_t(block_size) * 3 * phases;
+        const uint32_t blocks = uint32_t(std::min<uint64_t>((n + 255) / 256, 65536));
+        hipLaunchKernelGGL(wpt_transient_finish_kernel, dim3(blocks), dim3(256), 0, stream, planes, stride, block_start, block_size, phases,
+                1.0f / float(samples_sqrt * samples_sqrt));
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("time-of-flight sensor: ") + hipGetErrorString(e));
+    }
+    (void)hipFreeAsync(dConsts, stream);
+    return st;
+}
+
+} /* namespace */
+
+extern "C" {
+
+wpt_status wpt_render_tof_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* planes_device,
+        void* hip_stream)
+{
+    return tofLaunch(scene, camera, params, sensor, width, height, samples_sqrt, block_start, block_size, planes_device,
+            size_t(width) * height * 3, static_cast<hipStream_t>(hip_stream));
+}
+
+wpt_status wpt_render_tof_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_planes)
+{
+    const wpt_status checked = tofCheck(scene, camera, params, sensor, block_planes);
+    if (checked != WPT_OK)
+        return checked;
+    if (block_size == 0)
+        return WPT_OK;
+    /* device memory for the block only, behind a pointer biased so that pixel `block_start` lands at offset 0 */
+    const size_t blockFloats = size_t(block_size) * 3;
+    float* dPlanes = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dPlanes), blockFloats * sensor->phase_count * sizeof(float)));
+    wpt_status st = tofLaunch(scene, camera, params, sensor, width, height, samples_sqrt, block_start, block_size,
+            dPlanes - size_t(block_start) * 3, blockFloats, nullptr);
+    if (st == WPT_OK)
+        st = wpt_scene_check(scene);
+    if (st == WPT_OK) {
+        const hipError_t e = hipMemcpy(block_planes, dPlanes, blockFloats * sensor->phase_count * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(dPlanes);
+    return st;
+}
+
+wpt_status wpt_tof_accumulate_host(const wpt_tof_sensor* sensor, uint32_t phase, float radiance_w, float opl_w, int is_tof_light, float acc[3])
+{
+    if (!sensor || !acc)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: NULL argument");
+    if (sensor->phase_count == 0 || sensor->phase_count > WPT_TOF_MAX_PHASES || phase >= sensor->phase_count)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "time-of-flight sensor: phase outside the sensor's phase count (1 .. " + std::to_string(WPT_TOF_MAX_PHASES) + ")");
+    const float energy = wpttof::energy(sensor->pixel_area, sensor->exposure_time, radiance_w);
+    const float t = is_tof_light ? wpttof::modulation(sensor->contrast, sensor->frac_modfreq_c, sensor->tau[phase], opl_w) : 0.0f;
+    wpttof::add(energy, t, acc[0], acc[1], acc[2]);
+    return WPT_OK;
 }
 
 wpt_status wpt_ground_truth_device(wpt_scene* scene, const wpt_camera* camera, const wpt_camera* camera_prev,

@@ -315,7 +315,8 @@ enum {
     FEAT_SPOT = 2048,    /* LightSpot: emission inside a cone around the normal */
     FEAT_VIEWS = 4096,   /* a batch of views: every lane takes its camera from an array (wpt_pathtrace.inc.h, ViewsView) */
     FEAT_ADAPTIVE = 8192, /* adaptive sampling: every lane takes its pixel's sample count from a map (wpt_pathtrace.inc.h, AdaptiveView) */
-    FEAT_ROTATED = 16384 /* scene in LDS with two more copies of the corners, rotated: triangle tests take them in the ray's component order (triangleTestRotated) */
+    FEAT_ROTATED = 16384, /* scene in LDS with two more copies of the corners, rotated: triangle tests take them in the ray's component order (triangleTestRotated) */
+    FEAT_TOF = 32768     /* time-of-flight sensor: the accumulator holds the taps a, b and their total, fed from the fourth channel (wpt_tof.h, wpt_blocks.h) */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */
@@ -1407,7 +1408,10 @@ template<uint32_t F> WPT_D f4 materialEmitted(const SceneView& sv, const wpt_mat
             e = ld4(m.v[0]);
             if ((F & FEAT_TEXTURES) && m.tex[0] >= 0) {
                 f4 c = textureValue(sv, m.tex[0], h.tc);
-                e = mul(e, mk4(c.x, c.y, c.z, average3(mk3(c.x, c.y, c.z))));
+                if ((F & FEAT_TOF) && (m.flags & WPT_MATF_TOF_LIGHT))
+                    e.w = e.w * c.x; /* light_tof.hpp:57-61: the fourth channel times the texture's red value, nothing else */
+                else
+                    e = mul(e, mk4(c.x, c.y, c.z, average3(mk3(c.x, c.y, c.z))));
             }
         }
         return e;

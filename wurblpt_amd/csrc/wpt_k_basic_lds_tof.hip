@@ -1,0 +1,14 @@
+/* wpt_k_basic_lds_tof.hip -- instantiates wpt_pathtrace<FEAT_BASIC | FEAT_TWOSIDED | FEAT_SPOT | FEAT_TOF, false, true>: the
+ * time-of-flight sensor for scenes of the basic feature set, ToF lights and two-sided materials small enough for LDS; four
+ * workgroups per CU like its siblings, without the rotated copies of the corners */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchBasicLdsTof(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream)
+{
+    launchMaybePooled(wpt_pathtrace<FEAT_BASIC | FEAT_TWOSIDED | FEAT_SPOT | FEAT_TOF, false, true, 4>, args, grid, COLD_BYTES + sceneLdsBytes, stream);
+}
+
+}

@@ -1,0 +1,13 @@
+/* wpt_k_full_tof.hip -- instantiates wpt_pathtrace<FEAT_ALL | FEAT_TOF, false, false>: the time-of-flight sensor for scenes at
+ * rest that fetch the scene from HBM; four waves per SIMD like its RGB twin wpt_k_full.hip */
+#define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#include "wpt_pathtrace.inc.h"
+
+namespace wptk {
+
+void launchFullTof(const KernelArgs& args, dim3 grid, hipStream_t stream)
+{
+    launchMaybePooled(wpt_pathtrace<FEAT_ALL | FEAT_TOF, false, false, 4>, args, grid, COLD_BYTES, stream);
+}
+
+}

@@ -118,7 +118,8 @@ struct KernelArgs {
     wpt_counters* counters;
     unsigned long long* schedStats; /* COUNT builds: 16 scheduler statistics, or NULL */
     union { /* (no launch has both: the kernels of either feature are instantiated without the other) */
-        BinsView bins;   /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there) */
+        BinsView bins;   /* FEAT_TRANSIENT kernels: the transient film (frame may be NULL there); FEAT_TOF kernels: the sensor and
+                          * its phase planes (wpt_blocks.h, accumulate; with several phases frame is NULL) */
         ViewsView views; /* FEAT_VIEWS kernels: the batch's cameras; frame holds viewCount full frames, blockSize is all their pixels */
         AdaptiveView adaptive; /* FEAT_ADAPTIVE kernels: the sample-count map and the moment film; samplesSqrt above is unused */
     };
@@ -187,6 +188,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     static_assert(!((F & FEAT_VIEWS) && (F & FEAT_TRANSIENT)), "a batch of views has no transient film (they share KernelArgs' union)");
     static_assert(!((F & FEAT_ADAPTIVE) && (F & (FEAT_VIEWS | FEAT_TRANSIENT))), "adaptive sampling has no views and no transient film (they share KernelArgs' union)");
     static_assert(!((F & FEAT_ADAPTIVE) && COUNT), "adaptive sampling has no counting build");
+    static_assert(!((F & FEAT_TOF) && ((F & (FEAT_VIEWS | FEAT_TRANSIENT | FEAT_ADAPTIVE)) || COUNT)), "the time-of-flight sensor: one view, no other film, no counting build");
     constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
     constexpr bool ADAPTIVE = (F & FEAT_ADAPTIVE) != 0;
     /* the corners in LDS three times, once per rotation of (x, y, z): a triangle test reads them in its ray's component order */
@@ -792,7 +794,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                                 m[2] = invSamples * m[2];
                             }
                         }
-                    } else if (!(F & FEAT_TRANSIENT) || args.frame) {
+                    } else if (!(F & (FEAT_TRANSIENT | FEAT_TOF)) || args.frame) {
                         /* SensorRGB::finishPixel (sensor_rgb.hpp:82-87) */
                         const Slot acc = ps.get(SLOT_ACC);
                         float* out = args.frame + 3 * at;
@@ -899,6 +901,12 @@ void launchBasicLdsTransient(const KernelArgs& args, dim3 grid, size_t sceneLdsB
 void launchFullTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFullRglAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* the time-of-flight sensor (FEAT_SPOT | FEAT_TOF, args.bins): the Cornell class with the scene in LDS (two-sided materials
+ * included: a ToF light has a back side), all features (at rest, moving), measured BRDFs */
+void launchBasicLdsTof(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchFullTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullAnimTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
+void launchFullRglAnimTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
 /* a batch of views (FEAT_VIEWS, args.views): every scene kind of the single kernel, product and counting builds; measured BRDFs
  * take the moving-scene instantiation whether the scene moves or not */
 void launchBasicLdsViews(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);

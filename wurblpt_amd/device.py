@@ -23,7 +23,8 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
-           "wpt_render_adaptive_block_device", "wpt_render_adaptive_block", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -68,6 +69,11 @@ def lib():
                                                        C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_adaptive_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
                                                 C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.wpt_render_tof_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.POINTER(_abi.TofSensor),
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.wpt_render_tof_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.POINTER(_abi.TofSensor),
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.wpt_tof_accumulate_host.argtypes = [C.POINTER(_abi.TofSensor), C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_void_p]
         L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
         L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.wpt_set_walk.argtypes = [C.c_uint32]
@@ -166,6 +172,54 @@ def samples_sqrt_for_error(frame, moments, pilot_samples_sqrt, rel_error, min_sq
     n = np.clip(np.ceil(np.sqrt(need)), float(min_sqrt), float(max_sqrt))
     n[~finite] = max_sqrt
     return n.astype(np.uint16)
+
+
+def _tof_phases(sensor, phases):
+    """the sensor record of a launch: all of `sensor`'s phase images, or those whose indices `phases` lists (in that order)"""
+    if phases is None:
+        return sensor
+    s = _abi.TofSensor.from_buffer_copy(sensor)
+    phases = list(phases)
+    if not (1 <= len(phases) <= _abi.TOF_MAX_PHASES and all(0 <= j < sensor.phase_count for j in phases)):
+        raise ValueError("phases: 1 to %d indices below the sensor's phase count %d" % (_abi.TOF_MAX_PHASES, sensor.phase_count))
+    s.phase_count = len(phases)
+    for k, j in enumerate(phases):
+        s.tau[k] = sensor.tau[j]
+    return s
+
+
+def tof_accumulate_host(sensor, phase, radiance_w, opl_w, is_tof_light, acc):
+    """wpt_tof_accumulate_host: one contribution added to acc = float32[3] (a, b, total) on the CPU by the kernels' code"""
+    _check(lib().wpt_tof_accumulate_host(C.byref(sensor), phase, radiance_w, opl_w, 1 if is_tof_light else 0, C.c_void_p(acc.ctypes.data)))
+    return acc
+
+
+def tof_result(phase_differences, modulation_frequency):
+    """SensorTofAmcw::result() (sensor_tof_amcw.hpp:173-213) in numpy float32.  `phase_differences`: [n, ...] with n a multiple
+    of 4, a - b of the n phase images (digital numbers or energies: distance and phase shift do not depend on their scale,
+    amplitude and intensity scale with it).  Returns (distance [m], amplitude, intensity, phase_shift [rad])."""
+    import numpy as np
+    from . import host
+    D = np.asarray(phase_differences, dtype=np.float32)
+    n = D.shape[0]
+    assert n % 4 == 0 and n > 0, "a multiple of 4 phase images"
+    d0, d1, d2, d3 = D[0], D[n // 4], D[2 * n // 4], D[3 * n // 4]
+    re, im = d0 - d2, d3 - d1
+    zero = (np.abs(d0 - d2) <= 0) & (np.abs(d1 - d3) <= 0)
+    # the C library's atan2f, which the reference's std::atan2 is (numpy's own float32 arctan2 differs from it in the last bit)
+    libm = C.CDLL("libm.so.6")
+    libm.atan2f.restype = C.c_float
+    libm.atan2f.argtypes = [C.c_float, C.c_float]
+    shift = np.frompyfunc(libm.atan2f, 2, 1)(im, re).astype(np.float32)
+    # `phaseShift += 2.0 * pi` with the float pi: a double addition rounded to float
+    shift = np.where(shift < 0, (shift.astype(np.float64) + 2.0 * float(np.float32(np.pi))).astype(np.float32), shift)
+    frac_c_modfreq = np.float32(host.SPEED_OF_LIGHT / float(modulation_frequency))
+    distance = frac_c_modfreq * shift * np.float32(0.25) * np.float32(1.0 / np.pi)
+    shift = np.where(zero, np.float32(0), shift).astype(np.float32)
+    distance = np.where(zero, np.float32(0), distance).astype(np.float32)
+    amplitude = (np.sqrt((d0 - d2) * (d0 - d2) + (d1 - d3) * (d1 - d3)) * np.float32(np.pi / 2)).astype(np.float32)
+    intensity = (np.float32(0.5) * (d0 + d1 + d2 + d3)).astype(np.float32)
+    return distance, amplitude, intensity, shift
 
 
 def device_count():
@@ -292,6 +346,46 @@ class DeviceScene:
         _check(lib().wpt_render_transient_block(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K, w, h,
                                                 samples_sqrt, start, size, C.c_void_p(rgb.ctypes.data), C.c_void_p(bins.ctypes.data)))
         return rgb, bins
+
+    def render_tof_into(self, planes, samples_sqrt, sensor, phases=None, block=None, params=None, stream=None):
+        """Asynchronously renders pixels [start, start+size) of the time-of-flight sensor's phase images in one launch.
+        `planes`: CUDA float32 tensor [n, h, w, 3] = (a, b, total) per phase image; `sensor`: host.tof_sensor(...);
+        `phases`: indices of the sensor's phase images to render (default: all of them, n = sensor.phase_count).  Plane j is
+        bit for bit the one-phase launch of that phase; `params` must carry the default gates."""
+        from . import host
+        w, h = self.host.width, self.host.height
+        s = _tof_phases(sensor, phases)
+        assert planes.is_cuda and planes.is_contiguous() and planes.dtype.is_floating_point and planes.element_size() == 4 \
+            and planes.numel() == s.phase_count * w * h * 3
+        p = params if params is not None else host.default_params()
+        start, size = block if block is not None else (0, w * h)
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(lib().wpt_render_tof_block_device(self._handle, self.host.camera, C.byref(p), C.byref(s), w, h, samples_sqrt, start, size,
+                                                  C.c_void_p(planes.data_ptr()), sptr))
+
+    def render_tof(self, samples_sqrt, sensor, phases=None, block=None, params=None):
+        """Synchronous convenience: returns the planes [n, h, w, 3] as a numpy array (pixels outside `block` are 0)."""
+        import torch
+        w, h = self.host.width, self.host.height
+        n = _tof_phases(sensor, phases).phase_count
+        planes = torch.zeros((n, h, w, 3), dtype=torch.float32, device="cuda")
+        self.render_tof_into(planes, samples_sqrt, sensor, phases, block, params, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        self.check()
+        return planes.cpu().numpy()
+
+    def render_tof_host(self, samples_sqrt, sensor, block, phases=None, params=None):
+        """wpt_render_tof_block: submitBlock semantics; returns the block's planes [n, size, 3]."""
+        import numpy as np
+        from . import host
+        w, h = self.host.width, self.host.height
+        s = _tof_phases(sensor, phases)
+        p = params if params is not None else host.default_params()
+        start, size = block
+        planes = np.zeros((s.phase_count, size, 3), dtype=np.float32)
+        _check(lib().wpt_render_tof_block(self._handle, self.host.camera, C.byref(p), C.byref(s), w, h, samples_sqrt, start, size,
+                                           C.c_void_p(planes.ctypes.data)))
+        return planes
 
     def render_views_into(self, frames, cameras, samples_sqrt, params=None, counters=None, stream=None):
         """Asynchronously renders a batch of views in one launch: frame v of `frames`, a CUDA float32 tensor [V, h, w, 3], from

@@ -154,6 +154,40 @@ def cornell(width, height, tall_box_material=0, short_object_material=0):
     return HostScene(h, width, height, "cornell(tall=%d,short=%d)" % (tall_box_material, short_object_material))
 
 
+SPEED_OF_LIGHT = 299792458.0  # m/s in vacuum (the reference's constants.hpp)
+
+
+def tof_sensor(phase_image_count=4, modulation_frequency=10e6, exposure_time=1000.0, pixel_area=12.0 * 12.0, contrast=0.75):
+    """The record of a SensorTofAmcw with the reference's defaults (sensor_tof_amcw.hpp:75-88) for DeviceScene.render_tof:
+    frac_modfreq_c = float32(modulation_frequency / c), the division made in double; tau_j = j * (2.0f * pi) / count in the
+    reference's float order.  exposure_time in microseconds, pixel_area in square micrometers."""
+    if not 1 <= phase_image_count <= _abi.TOF_MAX_PHASES:
+        raise ValueError("tof_sensor: 1 .. %d phase images" % _abi.TOF_MAX_PHASES)
+    s = _abi.TofSensor()
+    s.pixel_area, s.exposure_time, s.contrast = pixel_area, exposure_time, contrast
+    s.frac_modfreq_c = float(np.float32(float(modulation_frequency) / SPEED_OF_LIGHT))
+    s.phase_count = phase_image_count
+    two_pi = np.float32(2.0) * np.float32(np.pi)
+    for j in range(phase_image_count):
+        s.tau[j] = float(np.float32(j) * two_pi / np.float32(phase_image_count))
+    return s
+
+
+def tof_scene(width, height, variant=0, twin=0, t0=0.0, t1=0.0):
+    """Scenes for the time-of-flight sensor, camera at the origin looking along -z with a vertical field of view of 70 degrees.
+    variant 0: the room of wurblpt-tof-example at rest at time 0 (wall, ModPhong quad and icosahedron, a two-sided ToF light
+    at the camera); 1: the same room with its animations, bounded for the exposure interval [t0, t1] (pass the same t0, t1 in
+    the render parameters); 2: a wall, a two-sided ToF light at the camera and a Cornell-class box (small enough for LDS);
+    3: a glass slab of thickness 0.5 and index (1.5, 1.5, 1.5, 1.3), no dispersion, between the camera and a ToF light that
+    faces it; 4: the room's wall and light alone; 5: a ToF light with an emission texture facing the camera and a cube it lights.
+    twin 1 replaces LightTof(r, angle) by LightSpot(angle, vec3(r)): under SensorRGB its x channel is the ToF scene's fourth;
+    twin 2 by LightSpot(angle, vec3(0)): what an RGB sensor sees of the ToF scene."""
+    L = lib()
+    L.wpt_host_tof_scene.restype = C.c_void_p
+    L.wpt_host_tof_scene.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint, C.c_uint]
+    return HostScene(L.wpt_host_tof_scene(variant, twin, t0, t1, width, height), width, height, "tof_scene(variant=%d,twin=%d)" % (variant, twin))
+
+
 def random_triangles(n, seed, width, height, with_texcoords=True, aperture=0.0):
     h = lib().wpt_host_random_triangles(n, seed, 1 if with_texcoords else 0, width, height, aperture)
     return HostScene(h, width, height, "random_triangles(%d,%d)" % (n, seed))

@@ -17,6 +17,7 @@
 #include "../../include/wurblpt/generator.hpp"
 #include "../../include/wurblpt/scene.hpp"
 #include "../../include/wurblpt/sensor.hpp"
+#include "../../include/wurblpt/tof.hpp"
 
 using namespace WurblPT;
 
@@ -328,6 +329,114 @@ wpt_host_scene* wpt_host_spot_scene(int variant, unsigned int width, unsigned in
     fprintf(stderr, "wpt_host: spot scene variant %d is not known\n", variant);
     delete hs;
     return nullptr;
+}
+
+/* Scenes for the time-of-flight sensor (include/wurblpt/tof.hpp).  `twin`: 0 = the ToF light LightTof(r, angle); 1 = in its
+ * place LightSpot(angle, vec3(r)), whose x channel under SensorRGB is the ToF scene's fourth channel; 2 = LightSpot(angle,
+ * vec3(0)), the ToF light as an RGB sensor sees it.
+ *   0  the room of wurblpt-tof-example.cpp:59-87 with its objects at rest at time 0, camera :103-105
+ *   1  the same room with its two animations, bounded for the exposure interval [t0, t1]
+ *   2  a wall, a two-sided ToF light at the camera and a Cornell-class box in front of the wall (scene small enough for LDS)
+ *   3  a glass slab of thickness 0.5 and index (1.5, 1.5, 1.5, 1.3) between the camera and a ToF light that faces it
+ *   4  the room's wall and light alone
+ *   5  a ToF light with an emission texture (6 x 4 texels whose red, green and blue differ) facing the camera, and a Lambertian
+ *      cube that it lights */
+wpt_host_scene* wpt_host_tof_scene(int variant, int twin, float t0, float t1, unsigned int width, unsigned int height)
+{
+    if (variant < 0 || variant > 5 || twin < 0 || twin > 2) {
+        fprintf(stderr, "wpt_host: time-of-flight scene variant %d (twin %d) is not known\n", variant, twin);
+        return nullptr;
+    }
+    wpt_host_scene* hs = new wpt_host_scene;
+    Scene& scene = hs->scene;
+    auto tofLight = [&](float radiance, float openingAngle, const Texture* tex = nullptr) -> Material* {
+        if (twin == 0)
+            return scene.take(new LightTof(radiance, openingAngle, tex));
+        return scene.take(new LightSpot(openingAngle, twin == 1 ? vec3(radiance) : vec3(0.0f), tex));
+    };
+    const Transformation lightTransformation(vec3(0.0f), toQuat(radians(180.0f), vec3(1.0f, 0.0f, 0.0f)), vec3(0.10f, 0.05f, 1.0f));
+    if (variant == 0 || variant == 1 || variant == 4) {
+        Material* bgMaterial = scene.take(new MaterialLambertian(vec4(1.0f)));
+        Transformation bgTransformation(vec3(0.0f, 0.0f, -2.0f), quat::null(), vec3(5.0f));
+        scene.take(new MeshInstance(scene.take(generateQuad(bgTransformation)), bgMaterial));
+        if (variant != 4) {
+            Material* quadMaterial = scene.take(new MaterialModPhong(vec3(0.7f), vec3(0.3f), 100.0f));
+            Transformation quadTransformation(vec3(0.0f), quat::null(), vec3(0.2f));
+            Material* objectMaterial = scene.take(new MaterialModPhong(vec3(0.5f), vec3(0.5f), 100.0f));
+            Transformation objectTransformation(vec3(0.0f), quat::null(), vec3(0.33f));
+            if (variant == 1) {
+                int quadAnimationIndex = scene.take(new AnimationKeyframes(0.0f, Transformation(vec3(-1.0f, 0.5f, -1.5f)),
+                            5.0f, Transformation(vec3(+1.0f, 0.5f, -1.5f))));
+                scene.take(new MeshInstance(scene.take(generateQuad(quadTransformation)), quadMaterial, quadAnimationIndex));
+                AnimationKeyframes* objectAnimation = new AnimationKeyframes();
+                for (int k = 0; k < 5; k++)
+                    objectAnimation->addKeyframe(1.25f * k, Transformation(vec3(0.0f, -0.3f, -1.0f), toQuat(radians(60.0f * k), vec3(0.0f, 1.0f, 0.5f))));
+                int objectAnimationIndex = scene.take(objectAnimation);
+                scene.take(new MeshInstance(scene.take(generateIcosahedron(objectTransformation)), objectMaterial, objectAnimationIndex));
+            } else {
+                scene.take(new MeshInstance(scene.take(generateQuad(quadTransformation)), quadMaterial, Transformation(vec3(-1.0f, 0.5f, -1.5f))));
+                scene.take(new MeshInstance(scene.take(generateIcosahedron(objectTransformation)), objectMaterial,
+                            Transformation(vec3(0.0f, -0.3f, -1.0f), toQuat(radians(0.0f), vec3(0.0f, 1.0f, 0.5f)))));
+            }
+        }
+        Material* lightFrontSide = tofLight(40.0f / (4.0f * pi), radians(120.0f));
+        Material* lightBackSide = scene.take(new MaterialLambertian(vec4(0.0f)));
+        Material* lightMaterial = scene.take(new MaterialTwoSided(lightFrontSide, lightBackSide));
+        scene.take(new MeshInstance(scene.take(generateQuad(lightTransformation)), lightMaterial), HotSpot);
+    } else if (variant == 2) {
+        Material* wall = scene.take(new MaterialLambertian(vec4(0.75f)));
+        Material* box = scene.take(new MaterialLambertian(vec4(0.5f)));
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(0.0f, 0.0f, -3.0f), quat::null(), vec3(6.0f)))), wall));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(0.3f, -0.2f, -2.0f), toQuat(radians(30.0f), vec3(0.0f, 1.0f, 0.0f)),
+                                vec3(0.4f)))), box));
+        Material* lightFrontSide = tofLight(40.0f / (4.0f * pi), radians(120.0f));
+        Material* lightBackSide = scene.take(new MaterialLambertian(vec4(0.0f)));
+        Material* lightMaterial = scene.take(new MaterialTwoSided(lightFrontSide, lightBackSide));
+        scene.take(new MeshInstance(scene.take(generateQuad(lightTransformation)), lightMaterial), HotSpot);
+    } else if (variant == 5) {
+        unsigned int state = 2468u;
+        auto next = [&state]() { state = state * 1664525u + 1013904223u; return state >> 8; };
+        Array<uint8_t> picture(6, 4, 3);
+        for (size_t i = 0; i < picture.elementCount(); i++) {
+            const unsigned int red = 32u + (next() & 0x7fu); /* green and blue lie above the red by 40 and 80, interpolated too */
+            for (int c = 0; c < 3; c++)
+                picture[i][c] = uint8_t(red + 40u * c);
+        }
+        Texture* pictureTex = scene.take(createTextureImage(picture, LinearizeSRGB_Off));
+        Material* light = tofLight(2.0f, radians(150.0f), pictureTex);
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(0.0f, 0.0f, -3.0f), quat::null(), vec3(1.5f, 1.0f, 1.0f)))), light), HotSpot);
+        Material* box = scene.take(new MaterialLambertian(vec4(0.5f)));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(0.8f, -0.4f, -1.6f), toQuat(radians(30.0f), vec3(0.0f, 1.0f, 0.0f)),
+                                vec3(0.3f)))), box));
+    } else {
+        /* the slab's faces at z = -1 and z = -1.5, the light at z = -3 facing the camera (+z) */
+        Material* glass = scene.take(new MaterialGlass(vec4(0.0f), vec4(1.5f, 1.5f, 1.5f, 1.3f)));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(0.0f, 0.0f, -1.25f), quat::null(), vec3(4.0f, 4.0f, 0.25f)))), glass));
+        Material* light = tofLight(1.0f, radians(120.0f));
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(0.0f, 0.0f, -3.0f), quat::null(), vec3(0.5f)))), light), HotSpot);
+    }
+    scene.updateBVH(t0, t1);
+    if (!scene.flatten(hs->flat, &hs->error)) {
+        fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
+        delete hs;
+        return nullptr;
+    }
+    if (variant == 3) {
+        /* no dispersion: MaterialGlass takes an index that differs between channels as chromatic dispersion and then follows
+         * one random channel per hit; this slab bends every channel alike (by the first channel's index) and differs only in
+         * how fast the near infrared travels in it */
+        for (wpt_material& m : hs->flat.materials)
+            if (m.type == WPT_MAT_GLASS)
+                m.flags &= ~uint32_t(WPT_MATF_CHROMATIC_DISPERSION);
+    }
+    hs->desc = hs->flat.desc();
+    Camera camera(Optics(Projection(radians(70.0f), float(width) / height))); /* at the origin, looking along -z */
+    camera.describe(hs->camera, t0);
+    hs->cameraObject.reset(new Camera(camera));
+    hs->vfov = radians(70.0f);
+    hs->from = vec3(0.0f);
+    hs->at = vec3(0.0f, 0.0f, -1.0f);
+    return hs;
 }
 
 wpt_host_scene* wpt_host_random_triangles(unsigned int n, unsigned int seed, int withTexcoords, unsigned int width,
