@@ -475,7 +475,7 @@ wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera,
         uint32_t block_start, uint32_t block_size, float* block_rgb, float* block_moments /* may be NULL */);
 
 /* Waits for the device; WPT_ERR_HIP if a launch since the last call failed (the kernels have no waits that could run
- * out: every loop of theirs ends with its work). */
+ * out: every loop of theirs ends with its work; lanes that hand a pixel on between its slices never wait for one another). */
 wpt_status wpt_scene_check(wpt_scene* scene);
 
 /* ---- ground truth (GroundTruth / getGroundTruth, wurblpt.hpp:453-769) ----
@@ -539,7 +539,7 @@ wpt_status wpt_postproc_host(int op, const float* rgb_host, void* out_host, uint
 /* Kernel launch geometry knobs (0 = default); for benchmarking only, results do not change.  wpt_set_launch_config,
  * wpt_set_top_nodes and wpt_set_wavefront are PROCESS-GLOBAL hooks for tests and measurements: set them before rendering
  * starts, not while other threads render (MPICoordinator's worker threads read them).
- * variant, byte 0: 0x01 scene from HBM even if it fits LDS, 0x02 all-features kernel, 0x20 separate SHADE / NEE-END / NEW rounds, 0x10 no pixel pool (every lane renders the one pixel it was launched for), 0x80 material records from HBM even where they fit into LDS next to the scene, 0x40 never two passes over a frame (timed first row of strata, then the rest with the longest tiles first; scenes fetched from HBM), bits 0x0c: a kind of material with few lanes in a long round stands back once (0 = fewer than 6 lanes, 0x04 = never, 0x08 = fewer than 3, 0x0c = fewer than 12; kernels without textures / spheres / environment only); byte 1: leave threshold of the traversal loop in eighths + 1; byte 2: lanes a long round needs + 1; byte 3:
+ * variant, byte 0: 0x01 scene from HBM even if it fits LDS, 0x02 all-features kernel, 0x20 separate SHADE / NEE-END / NEW rounds, 0x10 no pixel pool (every lane renders the one pixel it was launched for), 0x80 material records from HBM even where they fit into LDS next to the scene, 0x40 never two passes over a frame (timed first row of strata, then the rest with the longest tiles first; scenes fetched from HBM) and never pixels in slices (wpt_set_slices; scenes in LDS), bits 0x0c: a kind of material with few lanes in a long round stands back once (0 = fewer than 6 lanes, 0x04 = never, 0x08 = fewer than 3, 0x0c = fewer than 12; kernels without textures / spheres / environment only); byte 1: leave threshold of the traversal loop in eighths + 1; byte 2: lanes a long round needs + 1; byte 3:
  * leaf bias (DESIGN.md section 4 has what each was measured to do). */
 wpt_status wpt_set_launch_config(uint32_t threads_per_group, uint32_t variant);
 /* Storage order of the BVH nodes in HBM for scenes uploaded from now on: the first `nodes` nodes of a tree that is
@@ -572,6 +572,30 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
 #define WPT_WALK_TRIANGLES_AS_GIVEN 8u
 #define WPT_WALK_SELECT_CORNERS 16u
 wpt_status wpt_set_walk(uint32_t flags);
+/* Pixels in slices (results do not depend on it; process-global like the hooks above).  A pooled, plain product launch of the
+ * kernels with the scene in LDS cuts every pixel into `units` units of `rows` rows of strata and hands out all first units,
+ * then all second units, and so on, each time in the frame's own order, in one launch: the work that is left when the pool
+ * runs dry is a fraction of a pixel per lane instead of a whole one.  A pixel's samples stay one sequence from one generator
+ * (a unit goes on where the one before it stopped), so the frame is the same bit for bit.  Variant bit 0x40 of
+ * wpt_set_launch_config switches it off like the two passes of the other kernels; wpt_kernel_form says ", sliced xU".
+ *   wpt_slices_plan   the library's own choice for a launch of block_size pixels on a device that holds lanes_at_once lanes
+ *                     (compute units * 1024): units = 1 (not sliced) outside 2 to 64 pixels per lane and below samples_sqrt = 8.
+ *                     Otherwise it aims for t = samples_sqrt * sqrt(0.5 / pixels per lane) units, 15 at most -- a unit's start
+ *                     costs a hand-over through memory, and the end of the launch that the units shorten is the smaller a part
+ *                     of it the more pixels a lane renders; below t = 2 the launch is not sliced, otherwise rows =
+ *                     ceil(samples_sqrt / t), at least 2, and units = ceil(samples_sqrt / rows).  A pure function of its
+ *                     arguments that needs no device.
+ *   wpt_set_slices    0 = the plan (default), 1 = never, n = 2 .. 15: rows = ceil(samples_sqrt / n), units = ceil(samples_sqrt /
+ *                     rows), whatever the pixels per lane.  WPT_SLICES_DECLINE_ODD beside n (tests): a unit of a pixel on an odd
+ *                     slot of the launch is never taken over by the lane that draws it; the lane that rendered the unit before
+ *                     it runs it straight on -- the path a launch otherwise takes only where a unit is drawn before it is ready.
+ *   wpt_last_slice_stats  of the process's most recent render call, after waiting for the device: units that the lane that drew
+ *                     them took over, and units that their pixel's lane ran on with; 0 and 0 if the call was not sliced.  Their
+ *                     sum is pixels * (units - 1). */
+#define WPT_SLICES_DECLINE_ODD 0x100u
+wpt_status wpt_slices_plan(uint32_t block_size, uint32_t lanes_at_once, uint32_t samples_sqrt, uint32_t* units, uint32_t* rows);
+wpt_status wpt_set_slices(uint32_t n);
+wpt_status wpt_last_slice_stats(uint64_t* taken, uint64_t* continued);
 /* Which form of the path tracer renders frames whose scene is fetched from HBM (results do not depend on it):
  * mode 0 = the library decides per launch (default), 1 = the wavefront form wherever it exists (trace and shade as two
  * kernels that hand rays through HBM, wpt_wavefront.inc.h: everything but counting launches and moving scenes), 2 = never.
@@ -602,7 +626,8 @@ wpt_status wpt_set_scheduler_stats(unsigned long long* stats_device);
 /* Kernel family of the process's most recent render call (for profile matching). */
 const char* wpt_kernel_name(void);
 /* The form of that family's kernel the most recent render call launched, where a family has more than one: "rotated corners" for
- * the kernel with the scene in LDS that holds the corners in all three rotations (WPT_WALK_SELECT_CORNERS above), otherwise "". */
+ * the kernel with the scene in LDS that holds the corners in all three rotations (WPT_WALK_SELECT_CORNERS above), otherwise ""; ", sliced xU" behind it where the launch handed its pixels out in U units each
+ * (wpt_set_slices). */
 const char* wpt_kernel_form(void);
 /* What the reference records about a run for the CPU (wurblpt.hpp:393-400,425-435: COMPILER, CPU_MODEL), for the device:
  * marketing name and architecture of HIP device `device` ("AMD Instinct MI355X (gfx950:...)", or "" if there is none), and

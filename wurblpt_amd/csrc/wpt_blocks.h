@@ -35,7 +35,7 @@ using namespace wptd;
 constexpr uint32_t NO_HIT = 0xffffffffu;
 
 enum { RAY_PATH = 0, RAY_NEE_LIGHT = 1, RAY_NEE_ENV = 2, RAY_PATH_WAITED = 3 /* a path ray's hit that has stood back once */ };
-enum { NEXT_TRACE = 0, NEXT_NEW = 1, NEXT_DONE = 2, NEXT_WAIT = 3 };
+enum { NEXT_TRACE = 0, NEXT_NEW = 1, NEXT_DONE = 2, NEXT_WAIT = 3, NEXT_HANDED_ON = 4 /* FEAT_SLICED kernels: the pixel goes on in its next unit, the lane is free */ };
 
 /* COUNT builds: how often each stretch of the kernel's code runs, for the instruction budget (tools/instruction_budget.py multiplies
  * them with the stretches' instruction counts from the assembly): executions by a wave (at least one lane in it) and by lanes */
@@ -728,7 +728,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
     const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
-    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED | ((F & FEAT_TOF) ? (FEAT_TOF | FEAT_SPOT | FEAT_TWOSIDED) : 0u))) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
+    if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED | FEAT_SLICED | ((F & FEAT_TOF) ? (FEAT_TOF | FEAT_SPOT | FEAT_TWOSIDED) : 0u))) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
          * once (nothing has been written yet): the next round then runs it for two rounds' worth

@@ -184,6 +184,49 @@ uint32_t g_wfMode = 0;
 wptk::WfConfig g_wfConfig = { 0, 0, 0, 1, 0, 0, 0, 0, 0 };
 /* wpt_set_walk: WPT_WALK_* bits */
 uint32_t g_walk = 0;
+/* wpt_set_slices: 0 = wpt_slices_plan, 1 = never, 2 .. 15 = that many units; WPT_SLICES_DECLINE_ODD beside it */
+uint32_t g_slices = 0;
+/* the two counters of the sliced kernels (wpt_last_slice_stats), one pair per device, allocated at a device's first sliced
+ * launch and kept; g_lastSliceStats: the pair the most recent render call's kernel adds to, or NULL if it was not sliced */
+constexpr int SLICE_STATS_DEVICES = 64;
+std::atomic<unsigned long long*> g_sliceStats[SLICE_STATS_DEVICES];
+std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
+/* Units per pixel that wpt_slices_plan aims for at most: the best of the sweep over 1, 2, 4, 8 and 15 on the bench frame
+ *  */
+constexpr uint32_t SLICE_UNITS_TARGET = 15;
+
+/* wpt_kernel_form of a launch of the kernels with the scene in LDS */
+const char* ldsKernelForm(bool rotated, uint32_t units)
+{
+    static const std::vector<std::string> forms = [] {
+        std::vector<std::string> f;
+        for (int r = 0; r < 2; r++)
+            for (uint32_t u = 0; u <= wptk::SLICE_UNITS_MAX; u++)
+                f.push_back(std::string(r ? "rotated corners" : "") + (u > 1 ? ", sliced x" + std::to_string(u) : std::string()));
+        return f;
+    }();
+    return forms[(rotated ? wptk::SLICE_UNITS_MAX + 1 : 0) + (units <= wptk::SLICE_UNITS_MAX ? units : 0)].c_str();
+}
+
+unsigned long long* sliceStatsOfCurrentDevice()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SLICE_STATS_DEVICES)
+        return nullptr;
+    unsigned long long* p = g_sliceStats[dev].load(std::memory_order_acquire);
+    if (!p) {
+        if (hipMalloc(reinterpret_cast<void**>(&p), 2 * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        unsigned long long* expected = nullptr;
+        if (!g_sliceStats[dev].compare_exchange_strong(expected, p, std::memory_order_acq_rel)) {
+            (void)hipFree(p);
+            p = expected;
+        }
+    }
+    return p;
+}
 
 template<typename T> wpt_status uploadArray(wpt_scene* s, const T* src, size_t count, const T** dst)
 {
@@ -1075,6 +1118,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         g_kernelName.store(transientLds ? "wpt_pathtrace, time of flight, scene in LDS"
                 : rgl ? "wpt_pathtrace, time of flight, measured BRDFs"
                 : anim ? "wpt_pathtrace, time of flight, all features, moving scenes" : "wpt_pathtrace, time of flight, all features", std::memory_order_relaxed);
+    bool sliced = false; /* decided below: the twins of the two kernels with the scene in LDS that hand pixels out in slices */
     auto launch = [&](const wptk::KernelArgs& a) {
         if (tof) {
             if (transientLds)
@@ -1142,9 +1186,9 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 launchFullRgl(a, grid, stream);
         } else {
             if (rotated)
-                launchBasicLdsRotated(a, grid, rotatedBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                (sliced ? launchBasicLdsRotatedSliced : launchBasicLdsRotated)(a, grid, rotatedBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (basic && lds)
-                launchBasicLds(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                (sliced ? launchBasicLdsSliced : launchBasicLds)(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (wide) /* also for the basic feature set: the wide walk exists in the all-features instantiations */
                 launchFullWide(a, grid, stream);
             else if (basic)
@@ -1209,11 +1253,53 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             (void)hipGetLastError();
         }
     }
+    /* Pixels in slices for the kernels with the scene in LDS (wpt_pathtrace.inc.h, SlicesView; variant bit 0x40: never): the
+     * frame's own order and one launch, which is what the two passes above cost these kernels, but the launch ends on a
+     * fraction of a pixel.  Pooled, plain product launches only.  Without the memory for it the plain kernel renders the frame. */
+    uint32_t* sliceWords = nullptr;
+    float4* sliceCarry = nullptr;
+    g_lastSliceStats.store(nullptr, std::memory_order_relaxed);
+    if (sceneInLds && pool != nullptr && !(g_variant & 0x40u) && !views && !adaptive && !transient && !tof && !count
+            && uint64_t(block_size) > lanesAtOnce && block_size <= wptk::SLICE_SLOT_MASK) {
+        uint32_t units = 1, rows = samples_sqrt;
+        const uint32_t forced = g_slices & 0xffu;
+        if (forced == 0) {
+            wpt_slices_plan(block_size, uint32_t(lanesAtOnce), samples_sqrt, &units, &rows);
+        } else if (forced >= 2) {
+            rows = (samples_sqrt + forced - 1) / forced;
+            units = (samples_sqrt + rows - 1) / rows;
+        }
+        /* (the pool's counter runs past its last index by less than the lanes of the launch) */
+        unsigned long long* stats = nullptr;
+        if (units >= 2 && uint64_t(units) * block_size + 2 * lanesAtOnce < 0x100000000ull && (stats = sliceStatsOfCurrentDevice()) != nullptr) {
+            if (hipMallocAsync(reinterpret_cast<void**>(&sliceCarry), size_t(block_size) * 2 * sizeof(float4), stream) == hipSuccess
+                    && hipMallocAsync(reinterpret_cast<void**>(&sliceWords), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
+                    && hipMemsetAsync(sliceWords, 0, size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
+                    && hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), stream) == hipSuccess) {
+                wptk::KernelArgs inSlices = args;
+                inSlices.slices.words = sliceWords;
+                inSlices.slices.carry = sliceCarry;
+                inSlices.slices.stats = stats;
+                inSlices.slices.rows = rows;
+                inSlices.slices.units = units;
+                inSlices.slices.declineOdd = (g_slices & WPT_SLICES_DECLINE_ODD) ? 1u : 0u;
+                sliced = true;
+                launch(inSlices);
+                sliced = false;
+                passesDone = true;
+                g_lastSliceStats.store(stats, std::memory_order_relaxed);
+                g_kernelForm.store(ldsKernelForm(rotated, units), std::memory_order_relaxed);
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
     if (!passesDone)
         launch(args);
-    g_lastPasses.store(passesDone && !adaptive ? 2u : 1u, std::memory_order_relaxed);
+    g_lastPasses.store(passesDone && !adaptive && !sliceWords ? 2u : 1u, std::memory_order_relaxed);
     const hipError_t launched = hipGetLastError();
-    for (void* p : { static_cast<void*>(pool), static_cast<void*>(carry), static_cast<void*>(cost), static_cast<void*>(order), static_cast<void*>(work) })
+    for (void* p : { static_cast<void*>(pool), static_cast<void*>(carry), static_cast<void*>(cost), static_cast<void*>(order), static_cast<void*>(work),
+            static_cast<void*>(sliceWords), static_cast<void*>(sliceCarry) })
         if (p)
             (void)hipFreeAsync(p, stream);
     HIP_TRY(launched);
@@ -1845,6 +1931,58 @@ wpt_status wpt_set_walk(uint32_t flags)
     if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     g_walk = flags;
+    return WPT_OK;
+}
+
+wpt_status wpt_slices_plan(uint32_t block_size, uint32_t lanes_at_once, uint32_t samples_sqrt, uint32_t* units, uint32_t* rows)
+{
+    if (!units || !rows)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    /* as for two passes: with fewer than 2 pixels per lane the launch has no end to shorten, with more than 64 its end is a
+     * small part of it; a pixel of fewer than 8 rows of strata is a small unit already */
+    *units = 1;
+    *rows = samples_sqrt > 0 ? samples_sqrt : 1u;
+    if (lanes_at_once == 0 || samples_sqrt < 8 || uint64_t(block_size) < 2ull * lanes_at_once || uint64_t(block_size) > 64ull * lanes_at_once)
+        return WPT_OK;
+    /* What the units buy is the end of the launch, which is a share of the frame's time that falls with the pixels per lane
+     * (10 % at 4, measured); what they cost is a write-back and an invalidation of the L2 per unit, 1 to 2 ns of the launch
+     * each.  With the frame's time per sample (0.77 ns) the difference is largest at about samples_sqrt * sqrt(0.5 / pixels
+     * per lane) units: 11 for the bench frame, 2 at 16 pixels per lane and 256 spp, none at 64 pixels per lane and 64 spp,
+     * which is what those frames measured. */
+    const double perLane = double(block_size) / double(lanes_at_once);
+    uint32_t target = uint32_t(std::sqrt(0.5 * double(samples_sqrt) * double(samples_sqrt) / perLane));
+    target = target > SLICE_UNITS_TARGET ? SLICE_UNITS_TARGET : target;
+    if (target < 2)
+        return WPT_OK;
+    uint32_t r = (samples_sqrt + target - 1) / target;
+    r = r < 2 ? 2 : r;
+    *rows = r;
+    *units = (samples_sqrt + r - 1) / r;
+    return WPT_OK;
+}
+
+wpt_status wpt_set_slices(uint32_t n)
+{
+    if ((n & ~WPT_SLICES_DECLINE_ODD) > wptk::SLICE_UNITS_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "slices: 0 (the library's plan), 1 (never) or 2 .. 15 units, with or without WPT_SLICES_DECLINE_ODD");
+    g_slices = n;
+    return WPT_OK;
+}
+
+wpt_status wpt_last_slice_stats(uint64_t* taken, uint64_t* continued)
+{
+    if (!taken || !continued)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *taken = 0;
+    *continued = 0;
+    const unsigned long long* stats = g_lastSliceStats.load(std::memory_order_relaxed);
+    if (!stats)
+        return WPT_OK;
+    unsigned long long host[2] = { 0, 0 };
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host, stats, sizeof(host), hipMemcpyDeviceToHost));
+    *taken = host[0];
+    *continued = host[1];
     return WPT_OK;
 }
 

@@ -316,7 +316,8 @@ enum {
     FEAT_VIEWS = 4096,   /* a batch of views: every lane takes its camera from an array (wpt_pathtrace.inc.h, ViewsView) */
     FEAT_ADAPTIVE = 8192, /* adaptive sampling: every lane takes its pixel's sample count from a map (wpt_pathtrace.inc.h, AdaptiveView) */
     FEAT_ROTATED = 16384, /* scene in LDS with two more copies of the corners, rotated: triangle tests take them in the ray's component order (triangleTestRotated) */
-    FEAT_TOF = 32768     /* time-of-flight sensor: the accumulator holds the taps a, b and their total, fed from the fourth channel (wpt_tof.h, wpt_blocks.h) */
+    FEAT_TOF = 32768,    /* time-of-flight sensor: the accumulator holds the taps a, b and their total, fed from the fourth channel (wpt_tof.h, wpt_blocks.h) */
+    FEAT_SLICED = 65536  /* pixels are handed out in units of strata rows, so that the launch ends on a fraction of a pixel (wpt_pathtrace.inc.h, SlicesView) */
 };
 
 /* a primitive index with this bit is a sphere (index in the low bits), otherwise a triangle */

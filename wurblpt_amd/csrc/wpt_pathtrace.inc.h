@@ -81,6 +81,27 @@ struct AdaptiveView {
     const uint16_t* samplesSqrt; /* [height][width] in device memory */
     float* moments;              /* [height][width][3] in device memory, or NULL */
 };
+/* Pixels in slices (FEAT_SLICED kernels, pooled launches): every pixel is cut into `units` units of `rows` rows of strata, and
+ * the pool hands out indices in [0, units * blockSize): index `at` is unit g = at / blockSize of the pixel behind slot
+ * at % blockSize -- all first units in the frame's order, then all second units, and so on.  The work unit that ends the launch
+ * is then 1 / units of a pixel.  A pixel's samples stay one sequence from one generator: the lane that ends unit g - 1 stores
+ * the generator and the sum (carry, the two quadwords of a first pass) and sets bit g of the slot's word, "unit g is ready"; the
+ * lane that draws unit g sets bit 16 + g, "unit g was drawn".  Each does so with one atomic OR and looks at what the other had
+ * set before: the drawer runs the unit if it was ready and otherwise goes back to the pool, and the lane that finds its next
+ * unit already drawn runs it itself, straight on.  Exactly one of the two runs the unit, and neither waits for the other.
+ * The OR that says "ready" is a release at agent scope and the drawer's OR an acquire, so that the carry crosses the L2s of
+ * the XCDs; that costs a write-back of the L2 on one side and an invalidation on the other, which is what a unit's start costs
+ * (with acquire and release on both sides the frame of 64 pixels per lane and 64 spp took 1389 ms instead of 937; 817 unsliced). */
+struct SlicesView {
+    uint32_t* words;           /* per slot, zero at the launch: bit g = unit g is ready, bit 16 + g = unit g was drawn and declined */
+    float4* carry;             /* per slot: prng slot, acc slot */
+    unsigned long long* stats; /* [0] units taken over by the lane that drew them, [1] units their pixel's lane ran on with */
+    uint32_t rows, units;      /* units <= SLICE_UNITS_MAX; (units - 1) * rows < samplesSqrt <= units * rows */
+    uint32_t declineOdd;       /* tests: units of odd slots are never taken over (their pixel's lane runs them all) */
+};
+constexpr uint32_t SLICE_UNITS_MAX = 15;      /* unit bits per half of a slot's word: g = 1 .. units - 1 */
+constexpr uint32_t SLICE_SLOT_BITS = 28;      /* a lane keeps slot | g << 28 in one register */
+constexpr uint32_t SLICE_SLOT_MASK = (1u << SLICE_SLOT_BITS) - 1u;
 struct KernelArgs {
     SceneView sv;
     wpt_camera cam;
@@ -122,11 +143,13 @@ struct KernelArgs {
                           * its phase planes (wpt_blocks.h, accumulate; with several phases frame is NULL) */
         ViewsView views; /* FEAT_VIEWS kernels: the batch's cameras; frame holds viewCount full frames, blockSize is all their pixels */
         AdaptiveView adaptive; /* FEAT_ADAPTIVE kernels: the sample-count map and the moment film; samplesSqrt above is unused */
+        SlicesView slices; /* FEAT_SLICED kernels: the units pixels are handed out in (read only where the launch has a pool) */
     };
 };
 /* the adaptive member must not change the union's size or the layout of what follows it: the existing kernels' code objects
  * stay as they were */
 static_assert(sizeof(AdaptiveView) <= sizeof(BinsView) && alignof(AdaptiveView) <= alignof(BinsView), "AdaptiveView must fit in BinsView's place");
+static_assert(sizeof(SlicesView) <= sizeof(BinsView) && alignof(SlicesView) <= alignof(BinsView), "SlicesView must fit in BinsView's place");
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
 WPT_D bool lanePixel(const KernelArgs& args, uint32_t gid, uint32_t& pixel)
@@ -189,8 +212,10 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     static_assert(!((F & FEAT_ADAPTIVE) && (F & (FEAT_VIEWS | FEAT_TRANSIENT))), "adaptive sampling has no views and no transient film (they share KernelArgs' union)");
     static_assert(!((F & FEAT_ADAPTIVE) && COUNT), "adaptive sampling has no counting build");
     static_assert(!((F & FEAT_TOF) && ((F & (FEAT_VIEWS | FEAT_TRANSIENT | FEAT_ADAPTIVE)) || COUNT)), "the time-of-flight sensor: one view, no other film, no counting build");
+    static_assert(!((F & FEAT_SLICED) && ((F & (FEAT_VIEWS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_TOF)) || COUNT)), "pixels in slices: plain product launches (they share KernelArgs' union)");
     constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
     constexpr bool ADAPTIVE = (F & FEAT_ADAPTIVE) != 0;
+    constexpr bool SLICED = (F & FEAT_SLICED) != 0;
     /* the corners in LDS three times, once per rotation of (x, y, z): a triangle test reads them in its ray's component order */
     constexpr bool ROTATED = (F & FEAT_ROTATED) != 0;
     static_assert(!ROTATED || (LDSSCENE && !(F & FEAT_ANIM)), "rotated copies of the corners: scenes at rest in LDS");
@@ -282,6 +307,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     auto pixelOf = [&](uint32_t gid, uint32_t& pixel) -> bool { return lanePixel(args, gid, pixel); };
     const bool firstPass = !ADAPTIVE && args.rowStop < args.samplesSqrt; /* (an adaptive launch is one pass) */
     const uint32_t laneLimit = args.order ? *args.orderCount : args.blockSize; /* indices a lane may take */
+    /* SLICED: units per pixel and rows per unit; a launch without a pool renders every pixel in one piece */
+    uint32_t sliceUnits = 1, sliceRows = 0;
+    if constexpr (SLICED) {
+        sliceUnits = args.pool ? args.slices.units : 1u;
+        sliceRows = args.pool ? args.slices.rows : args.samplesSqrt;
+    }
     FrameArgs fa;
     fa.cam = args.cam;
     fa.par = args.par;
@@ -299,10 +330,37 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     uint32_t view = 0;
     /* ADAPTIVE: the sample count n of the lane's pixel (0: not rendered), a register of its own; never wave-uniform */
     uint32_t laneSqrt = 0;
+    /* SLICED: the lane's slot | its unit g << SLICE_SLOT_BITS, a register of its own */
+    uint32_t unit = 0;
     /* the lane takes the pixel behind index `at` of the launch; false: there is none */
     auto startPixel = [&](uint32_t at) -> bool {
         uint32_t pixel = args.blockStart;
         bool have;
+        if constexpr (SLICED) {
+            /* unit g of the pixel behind slot at % laneLimit.  A first unit starts the pixel as ever; a later one is this lane's
+             * if the lane that ran the unit before it has already left it behind (SlicesView), and then goes on from the carry */
+            uint32_t g = 0, slot = at;
+            if (at >= laneLimit) {
+                g = at / laneLimit;
+                slot = at - g * laneLimit;
+            }
+            have = pixelOf(slot, pixel);
+            if (g > 0) {
+                have = false;
+                if (g < sliceUnits) {
+                    const uint32_t before = __hip_atomic_fetch_or(args.slices.words + slot, 1u << (16 + g), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+                    have = ((before >> g) & 1u) != 0 && !(args.slices.declineOdd && (slot & 1u));
+                }
+            }
+            unit = slot | (g << SLICE_SLOT_BITS);
+            pathStateInit(ps, pixel, pixel % args.width, pixel / args.width);
+            if (have && g > 0) {
+                ps.base[SLOT_PRNG * WG] = args.slices.carry[2 * (size_t)slot];
+                ps.base[SLOT_ACC * WG] = args.slices.carry[2 * (size_t)slot + 1];
+                atomicAdd(args.slices.stats, 1ull);
+            }
+            return have;
+        }
         if (args.order) {
             have = at < laneLimit;
             if (have)
@@ -411,7 +469,10 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                 if ((int)lane == leader)
                     first = atomicAdd(args.pool, want);
                 first = (uint32_t)__builtin_amdgcn_readlane((int)first, leader);
-                poolDry = first + want >= laneLimit; /* the counter only grows: nothing behind it for this wave */
+                if constexpr (SLICED)
+                    poolDry = first + want >= sliceUnits * laneLimit; /* indices the pool hands out: every unit of every slot */
+                else
+                    poolDry = first + want >= laneLimit; /* the counter only grows: nothing behind it for this wave */
                 if (state == S_DONE) {
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                     if (startPixel(first + rank))
@@ -739,7 +800,26 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             if (state == S_NEW) { /* the pixel's next sample (wurblpt.hpp:348-360), or nothing more */
                 const bool passEnds = firstPass && (ps.getW(SLOT_ACC) >> 16) >= args.rowStop;
                 int next;
-                if constexpr (ADAPTIVE) {
+                if constexpr (SLICED) {
+                    /* the lane's unit ends where the pixel's next row of strata is the next unit's first */
+                    const uint32_t g = unit >> SLICE_SLOT_BITS;
+                    const uint32_t rowEnd = (g + 1) * sliceRows < args.samplesSqrt ? (g + 1) * sliceRows : args.samplesSqrt;
+                    next = (ps.getW(SLOT_ACC) >> 16) >= rowEnd ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv);
+                    if (next == NEXT_DONE && rowEnd < args.samplesSqrt) {
+                        /* not the pixel's last: leave generator and sum behind, then say so.  Whoever drew the next unit before
+                         * this moment has passed it by: then it is this lane's, which has the pixel's state where it is */
+                        const uint32_t slot = unit & SLICE_SLOT_MASK;
+                        args.slices.carry[2 * (size_t)slot] = ps.base[SLOT_PRNG * WG];
+                        args.slices.carry[2 * (size_t)slot + 1] = ps.base[SLOT_ACC * WG];
+                        const uint32_t before = __hip_atomic_fetch_or(args.slices.words + slot, 1u << (g + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                        next = NEXT_HANDED_ON; /* the lane is done with it, and nothing of it goes to the frame yet */
+                        if (((before >> (17 + g)) & 1u) != 0 || (args.slices.declineOdd && (slot & 1u))) {
+                            unit += 1u << SLICE_SLOT_BITS;
+                            atomicAdd(args.slices.stats + 1, 1ull);
+                            next = NEXT_NEW; /* its first sample starts with the wave's next long round */
+                        }
+                    }
+                } else if constexpr (ADAPTIVE) {
                     /* a sample has ended unless the pixel is at its first stratum: M += S * S, then S = 0 */
                     const f3 s = ps.sampleSum;
                     if (args.adaptive.moments && ps.getW(SLOT_ACC) != 0) {
@@ -884,6 +964,9 @@ constexpr uint32_t ORDER_BUCKETS = 128;
 void launchOrderBuild(const KernelArgs& args, uint32_t* order, uint32_t* work, hipStream_t stream);
 void launchBasicLds(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
 void launchBasicLdsRotated(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream); /* sceneLdsBytes: with the two rotated copies of the corners */
+/* their twins that hand pixels out in slices (FEAT_SLICED, args.slices) */
+void launchBasicLdsSliced(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+void launchBasicLdsRotatedSliced(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
 void launchBasic(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchBasicCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
 void launchFull(const KernelArgs& args, dim3 grid, hipStream_t stream);

@@ -17,6 +17,7 @@ def lib_path():
 
 
 WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS = 1, 2, 4, 8, 16  # wpt_set_walk (include/wurblpt_hip.h)
+SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
 EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_scene_upload", "wpt_scene_free", "wpt_scene_check",
            "wpt_postproc_to_srgb", "wpt_postproc_max_luminance", "wpt_postproc_uniform_rational_quantization",
@@ -24,7 +25,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -224,6 +225,31 @@ def tof_result(phase_differences, modulation_frequency):
 
 def device_count():
     return lib().wpt_device_count()
+
+
+def set_slices(n):
+    """wpt_set_slices: 0 = the library's plan, 1 = never, 2 .. 15 = that many units per pixel (| SLICES_DECLINE_ODD: tests)"""
+    L = lib()
+    L.wpt_set_slices.argtypes = [C.c_uint32]
+    _check(L.wpt_set_slices(n))
+
+
+def slices_plan(block_size, lanes_at_once, samples_sqrt):
+    """wpt_slices_plan: (units, rows) the library cuts the pixels of such a launch into; needs no device"""
+    L = lib()
+    L.wpt_slices_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    units, rows = C.c_uint32(), C.c_uint32()
+    _check(L.wpt_slices_plan(block_size, lanes_at_once, samples_sqrt, C.byref(units), C.byref(rows)))
+    return int(units.value), int(rows.value)
+
+
+def last_slice_stats():
+    """wpt_last_slice_stats: (taken, continued) of the most recent render call; waits for the device"""
+    L = lib()
+    L.wpt_last_slice_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    taken, continued = C.c_uint64(), C.c_uint64()
+    _check(L.wpt_last_slice_stats(C.byref(taken), C.byref(continued)))
+    return int(taken.value), int(continued.value)
 
 
 class DeviceScene:
