@@ -624,7 +624,9 @@ WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const
         if (cam.surround_mode == WPT_SURROUND_180)
             lon *= 0.5f;
         const float lat = (v - 0.5f) * k_pi;
-        const float clat = wptm::cosf_(lat), slat = wptm::sinf_(lat), clon = wptm::cosf_(lon), slon = wptm::sinf_(lon);
+        float clat, slat, clon, slon;
+        wptm::sincosf_(lat, &slat, &clat);
+        wptm::sincosf_(lon, &slon, &clon);
         D = mk3(clat * slon, slat, -clat * clon);
         O = sclr(mk3(-clon, 0.0f, -slon), stereoscopicShift);
     } else {

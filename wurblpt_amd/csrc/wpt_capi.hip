@@ -24,7 +24,8 @@ using namespace wptk;
 namespace {
 
 /* Bit-parity self test of the arithmetic the kernel relies on: ops 0..5 are the
- * transcendentals of wpt_math.h, 6 = IEEE division, 7 = IEEE square root, 10 acos, 11 atan2(x, 1), 12 float(2 * asin(double)). */
+ * transcendentals of wpt_math.h, 6 = IEEE division, 7 = IEEE square root, 10 acos, 11 atan2(x, 1), 12 float(2 * asin(double)),
+ * 13 / 14 the sine / cosine of sincosf_(x), 15 / 16 the x / y of the sampler's inUnitDisk(x, y). */
 __global__ void wpt_selftest_kernel(int op, int n, const float* a, const float* b, float* out)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -44,6 +45,22 @@ __global__ void wpt_selftest_kernel(int op, int n, const float* a, const float* 
     case 10: r = wptm::acosf_(x); break;
     case 11: r = wptm::atan2f_(x, 1.0f); break;
     case 12: r = (float)(2.0 * wptm::asin_d((double)x)); break;
+    case 13:
+    case 14: {
+        float s, c;
+        wptm::sincosf_(x, &s, &c);
+        r = op == 13 ? s : c;
+        break;
+    }
+    case 15:
+    case 16: {
+        f2 u;
+        u.x = x;
+        u.y = y;
+        const f2 d = inUnitDisk(u);
+        r = op == 15 ? d.x : d.y;
+        break;
+    }
     default: r = 1.0f / x; break;
     }
     out[i] = r;

@@ -134,26 +134,23 @@ WPT_D f2 in01x2(Prng& p)
 /* ---- Sampler (sampler.hpp:39-109) ---- */
 WPT_D f2 inUnitDisk(f2 u)
 {
+    /* The reference's two arms (|ox| > |oy| or not) are the same operations on exchanged operands, and a wave has lanes in both:
+     * the operands are chosen by select and the wave divides once.  At (0, 0) the quotient is NaN; the angle is set to 0 ahead
+     * of the sine and cosine and the result to (0, 0) after them. */
     float ox = 2.0f * u.x - 1.0f;
     float oy = 2.0f * u.y - 1.0f;
+    const bool centre = ox == 0.0f && oy == 0.0f;
+    const bool wide = __builtin_fabsf(ox) > __builtin_fabsf(oy);
+    const float num = wide ? oy : ox;
+    const float rad = wide ? ox : oy;
+    const float q = k_pi_4 * (num / rad);
+    float theta = wide ? q : k_pi_2 - q;
+    theta = centre ? 0.0f : theta;
+    float s, c;
+    wptm::sincosf_(theta, &s, &c);
     f2 r;
-    if (ox == 0.0f && oy == 0.0f) {
-        r.x = 0.0f;
-        r.y = 0.0f;
-    } else {
-        float theta, rad;
-        if (__builtin_fabsf(ox) > __builtin_fabsf(oy)) {
-            rad = ox;
-            theta = k_pi_4 * (oy / ox);
-        } else {
-            rad = oy;
-            theta = k_pi_2 - k_pi_4 * (ox / oy);
-        }
-        float s, c;
-        wptm::sincosf_(theta, &s, &c);
-        r.x = rad * c;
-        r.y = rad * s;
-    }
+    r.x = centre ? 0.0f : rad * c;
+    r.y = centre ? 0.0f : rad * s;
     return r;
 }
 WPT_D f3 inTriangle(f2 u)
@@ -193,7 +190,9 @@ WPT_D f3 onUnitSphere(f2 u)
     const float z = 1.0f - 2.0f * u.x;
     const float r = __builtin_sqrtf(fmaxr(0.0f, 1.0f - z * z));
     const float phi = 2.0f * k_pi * u.y;
-    return mk3(r * wptm::cosf_(phi), r * wptm::sinf_(phi), z);
+    float sphi, cphi;
+    wptm::sincosf_(phi, &sphi, &cphi);
+    return mk3(r * cphi, r * sphi, z);
 }
 /* Sampler::toSphere (sampler.hpp:112-120) */
 WPT_D f3 toSphere(f3 direction, float cosThetaMax, f2 u)
@@ -201,7 +200,9 @@ WPT_D f3 toSphere(f3 direction, float cosThetaMax, f2 u)
     const float cosTheta = (1.0f - u.x) + u.x * cosThetaMax;
     const float sinTheta = __builtin_sqrtf(fmaxr(0.0f, 1.0f - cosTheta * cosTheta));
     const float phi = u.y * 2.0f * k_pi;
-    const f3 vectorAroundZ = mk3(wptm::cosf_(phi) * sinTheta, wptm::sinf_(phi) * sinTheta, cosTheta);
+    float sphi, cphi;
+    wptm::sincosf_(phi, &sphi, &cphi);
+    const f3 vectorAroundZ = mk3(cphi * sinTheta, sphi * sinTheta, cosTheta);
     return normalize(toWorld(frameFromNormal(direction), vectorAroundZ));
 }
 

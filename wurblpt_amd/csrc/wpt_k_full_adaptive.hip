@@ -1,5 +1,6 @@
 /* wpt_k_full_adaptive.hip -- instantiates wpt_pathtrace<FEAT_ALL | FEAT_ADAPTIVE, false, false>: adaptive sampling of a scene at rest with any feature but measured BRDFs (the Sponza class) */
 #define WPT_MATH_TABLES_IN_LDS /* this unit's kernels keep the tables of expf / powf in LDS (wpt_math.h) */
+#define WPT_SINCOSF_SEPARATE /* sincosf_ as sinf_ + cosf_: either fused form costs this kernel scratch (wpt_math.h) */
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {

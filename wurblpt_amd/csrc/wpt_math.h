@@ -697,7 +697,52 @@ WPT_HD float atan2f_(float y, float x)
 
 WPT_HD void sincosf_(float x, float* s, float* c)
 {
-    /* glibc's sincosf evaluates the same two polynomials on the same reduced argument as sinf and cosf */
+    /* glibc's sincosf evaluates the same two polynomials on the same reduced argument as sinf and cosf.  Below 120 that is
+     * written here as one stretch without a branch, for waves whose lanes differ in size class and quadrant (every sampler's
+     * angle): one reduction, each polynomial once with sinf_poly's operations in its order, and selects.  The bits are those of
+     * sinf_ / cosf_ for every float (tests/sincos_fused.cpp compares all 2^32):
+     *  - where sinf_ skips the reduction (|y| < pi/4) reduce_fast gives n = 0 and fma(-0.0, hpi, x) = x, and the sign of
+     *    quadrant 0 is 1, so both polynomials see the arguments of the "small" arm;
+     *  - the two returns for tiny arguments (y, 1.0f) are selects at the end: the polynomials of a tiny argument are finite.
+     * A translation unit that defines WPT_SINCOSF_POLY_BRANCH keeps the shared reduction but picks each polynomial by the branch
+     * on the quadrant's parity (sinf_poly as it stands): the form for a kernel that has no registers for both at once. */
+    const float y = x;
+#ifndef WPT_SINCOSF_SEPARATE
+    if (__builtin_expect(abstop12(y) < abstop12(120.0f), 1)) {
+        int n;
+        const double xr = reduce_fast((double)y, &n);
+        const double xs = xr * quadrant_sign(n & 3);
+        const double x2 = xr * xr;
+        const bool tiny = abstop12(y) < abstop12(0x1p-12f);
+#ifdef WPT_SINCOSF_POLY_BRANCH
+        const float sv = sinf_poly(xs, x2, (n & 2) != 0, n);
+        const float cv = sinf_poly(xs, x2, (n & 2) != 0, n ^ 1);
+        *s = tiny ? y : sv;
+        *c = tiny ? 1.0f : cv;
+#else
+        const double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10, c4 = 0x1.99343027bf8c3p-16;
+        const double s1 = -0x1.555545995a603p-3, s2 = 0x1.1107605230bc4p-7, s3 = -0x1.994eb3774cf24p-13;
+        /* the sine's polynomial (sinf_poly, n even) */
+        const double x3 = xs * x2;
+        const double st1 = fma_d(x2, s3, s2);
+        const double x7 = x3 * x2;
+        const double st = fma_d(x3, s1, xs);
+        const float S = (float)fma_d(x7, st1, st);
+        /* the cosine's (sinf_poly, n odd), negated in quadrants 2 and 3 */
+        const double x4 = x2 * x2;
+        const double ct2 = fma_d(x2, c4, c3);
+        const double ct1 = fma_d(x2, c1, c0);
+        const double x6 = x4 * x2;
+        const double ct = fma_d(x4, c2, ct1);
+        const double r = fma_d(x6, ct2, ct);
+        const float Cn = (float)((n & 2) ? -r : r);
+        const bool odd = (n & 1) != 0;
+        *s = tiny ? y : (odd ? Cn : S);
+        *c = tiny ? 1.0f : (odd ? S : Cn);
+#endif
+        return;
+    }
+#endif
     *s = sinf_(x);
     *c = cosf_(x);
 }
