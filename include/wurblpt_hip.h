@@ -565,13 +565,25 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
  *   WPT_WALK_SELECT_CORNERS  plain product launches of the kernel with the scene in LDS keep the triangle test that selects the
  *                           corners' components by the ray's axes (A/B runs and tests; by default such a launch holds the
  *                           corners in LDS in all three rotations of (x, y, z), where that still leaves four workgroups per
- *                           compute unit, and a test reads them in its ray's order: wpt_kernel_form) */
+ *                           compute unit, and a test reads them in its ray's order: wpt_kernel_form)
+ *   WPT_WALK_NO_FOLD        the kernels with the scene in LDS keep every node's own first child in their copy of the tree (A/B
+ *                           runs and tests; by default a first child whose box is its parent's bit for bit is folded into the
+ *                           parent's link, because its box test repeats the parent's on the same inputs: wpt_fold.h) */
 #define WPT_WALK_WIDE 1u
 #define WPT_WALK_FULL_SHADOW 2u
 #define WPT_WALK_COUNT_PRODUCT 4u
 #define WPT_WALK_TRIANGLES_AS_GIVEN 8u
 #define WPT_WALK_SELECT_CORNERS 16u
+#define WPT_WALK_NO_FOLD 32u
 wpt_status wpt_set_walk(uint32_t flags);
+/* Nodes whose link the kernels with the scene in LDS fold in their copy of the tree: inner nodes that go past one or more inner
+ * first children with their own box.
+ *   wpt_scene_folded_links  of an uploaded scene, counted at the upload (0 for a scene that does not fit LDS)
+ *   wpt_fold_plan           the same count from a description, a pure function that needs no device, whatever the scene's size;
+ *                           lds_words (or NULL): node_count words, word 7 of every node's copy in LDS with the folds applied
+ *                           (an index: where a ray that passes the box goes, node_count = out of the tree; >= 2^31: a leaf) */
+wpt_status wpt_scene_folded_links(const wpt_scene* scene, uint32_t* folded);
+wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t* lds_words);
 /* Pixels in slices (results do not depend on it; process-global like the hooks above).  A pooled, plain product launch of the
  * kernels with the scene in LDS cuts every pixel into `units` units of `rows` rows of strata and hands out all first units,
  * then all second units, and so on, each time in the frame's own order, in one launch: the work that is left when the pool

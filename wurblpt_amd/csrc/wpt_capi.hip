@@ -174,6 +174,7 @@ struct wpt_scene {
     SceneView view;
     uint32_t features;
     uint32_t nodeCount, triCount;
+    uint32_t foldedLinks; /* wpt_scene_folded_links */
     uint32_t animationCount;
     std::vector<void*> allocations;
     int cuCount;
@@ -459,6 +460,22 @@ wpt_status validate(const wpt_scene_desc* d)
     return WPT_OK;
 }
 
+/* Nodes whose link the LDS copy of a tree folds (wpt_fold.h: they go past one or more first children with their own box),
+ * counted with the rule the kernels' prologue applies over device nodes (8 words each) in the order the kernels see them.
+ * words (or NULL): every node's word 7 in LDS. */
+uint32_t countFoldedLinks(const uint32_t* nodes, uint32_t nodeCount, uint32_t* words)
+{
+    uint32_t folded = 0;
+    for (uint32_t i = 0; i < nodeCount; i++) {
+        uint32_t links;
+        const uint32_t word = wptf::foldLdsWord(nodes, nodeCount, i, true, &links);
+        folded += links > 0 ? 1u : 0u;
+        if (words)
+            words[i] = word;
+    }
+    return folded;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -611,6 +628,9 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
                     s->view.boxesMayBeNan = 1u;
         }
         UP(uploadArray(s, dev.data(), dev.size(), &nodes));
+        s->foldedLinks = 0;
+        if (size_t(n) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES) /* the trees that are walked from LDS */
+            s->foldedLinks = countFoldedLinks(reinterpret_cast<const uint32_t*>(dev.data()), n, nullptr);
         if (g_walk & WPT_WALK_WIDE) {
             /* The wide form (wpt_pathtrace.inc.h): the binary tree collapsed by one level.  Wide nodes are made for the root and
              * for every inner node that is an entry of a wide node, in depth-first order (a wide node's first inner entry follows
@@ -1098,6 +1118,10 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             && COLD_BYTES + rotatedBytes <= LDS_BYTES_PER_WORKGROUP_AT_FOUR;
     if (rotated)
         args.materialsInLds = (!(g_variant & 0x80u) && COLD_BYTES + rotatedBytes + size_t(scene->view.materialCount) * sizeof(wpt_material) <= LDS_BYTES_PER_WORKGROUP_AT_FOUR) ? 1u : 0u;
+    /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h); wpt_set_walk(WPT_WALK_NO_FOLD)
+     * keeps every node's own first child */
+    if (!(g_walk & WPT_WALK_NO_FOLD))
+        args.materialsInLds |= LDS_FOLD;
     g_kernelForm.store(rotated ? "rotated corners" : "", std::memory_order_relaxed);
     args.rowStop = samples_sqrt;
     args.carry = nullptr;
@@ -1139,7 +1163,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     auto launch = [&](const wptk::KernelArgs& a) {
         if (tof) {
             if (transientLds)
-                launchBasicLdsTof(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                launchBasicLdsTof(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
                 launchFullRglAnimTof(a, grid, stream);
             else if (anim)
@@ -1148,7 +1172,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 launchFullTof(a, grid, stream);
         } else if (adaptive) {
             if (adaptiveLds)
-                launchBasicLdsAdaptive(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                launchBasicLdsAdaptive(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
                 launchFullRglAnimAdaptive(a, grid, stream);
             else if (anim)
@@ -1159,7 +1183,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 launchFullAdaptive(a, grid, stream);
         } else if (views) {
             if (viewsLds)
-                launchBasicLdsViews(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                launchBasicLdsViews(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
                 count ? launchFullRglAnimCountViews(a, grid, stream) : launchFullRglAnimViews(a, grid, stream);
             else if (anim)
@@ -1170,7 +1194,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 count ? launchFullCountViews(a, grid, stream) : launchFullViews(a, grid, stream);
         } else if (transient) {
             if (transientLds)
-                launchBasicLdsTransient(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                launchBasicLdsTransient(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (rgl)
                 launchFullRglAnimTransient(a, grid, stream);
             else if (anim)
@@ -1203,9 +1227,9 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 launchFullRgl(a, grid, stream);
         } else {
             if (rotated)
-                (sliced ? launchBasicLdsRotatedSliced : launchBasicLdsRotated)(a, grid, rotatedBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                (sliced ? launchBasicLdsRotatedSliced : launchBasicLdsRotated)(a, grid, rotatedBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (basic && lds)
-                (sliced ? launchBasicLdsSliced : launchBasicLds)(a, grid, ldsBytes + (a.materialsInLds ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
+                (sliced ? launchBasicLdsSliced : launchBasicLds)(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
             else if (wide) /* also for the basic feature set: the wide walk exists in the all-features instantiations */
                 launchFullWide(a, grid, stream);
             else if (basic)
@@ -1945,7 +1969,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes)
 
 wpt_status wpt_set_walk(uint32_t flags)
 {
-    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS))
+    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     g_walk = flags;
     return WPT_OK;
@@ -2000,6 +2024,38 @@ wpt_status wpt_last_slice_stats(uint64_t* taken, uint64_t* continued)
     HIP_TRY(hipMemcpy(host, stats, sizeof(host), hipMemcpyDeviceToHost));
     *taken = host[0];
     *continued = host[1];
+    return WPT_OK;
+}
+
+wpt_status wpt_scene_folded_links(const wpt_scene* scene, uint32_t* folded)
+{
+    if (!scene || !folded)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *folded = scene->foldedLinks;
+    return WPT_OK;
+}
+
+wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t* lds_words)
+{
+    if (!folded)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const wpt_status st = validate(desc);
+    if (st != WPT_OK)
+        return st;
+    /* the device nodes of wpt_scene_upload, depth-first (the storage order of every tree that fits LDS) */
+    const uint32_t n = desc->node_count;
+    std::vector<uint32_t> end(n), words(size_t(n) * 8);
+    for (uint32_t i = n; i-- > 0;)
+        end[i] = desc->nodes[i].kind == WPT_NODE_INNER ? end[desc->nodes[i].link] : i + 1;
+    for (uint32_t i = 0; i < n; i++) {
+        const wpt_bvh_node& nd = desc->nodes[i];
+        const float box[6] = { nd.lo[0], nd.hi[0], nd.lo[1], nd.lo[2], nd.hi[1], nd.hi[2] };
+        memcpy(&words[8 * size_t(i)], box, sizeof(box));
+        words[8 * size_t(i) + 6] = end[i];
+        words[8 * size_t(i) + 7] = nd.kind == WPT_NODE_INNER ? (NODE_CHILD | (i + 1)) : nd.kind == WPT_NODE_TRIANGLE ? nd.link
+                : nd.kind == WPT_NODE_SPHERE ? (PRIM_SPHERE | nd.link) : (NODE_CHILD | end[i]);
+    }
+    *folded = countFoldedLinks(words.data(), n, lds_words);
     return WPT_OK;
 }
 

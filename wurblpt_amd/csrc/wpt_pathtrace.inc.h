@@ -43,6 +43,7 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_blocks.h"
+#include "wpt_fold.h"
 
 namespace wptk {
 
@@ -62,6 +63,9 @@ constexpr uint32_t LDS_SCENE_MAX_BYTES = 20 * 1024;
 /* a quarter of a compute unit's 160 KiB: what a workgroup may use where four of them are to share the unit (the material
  * records join the scene in LDS where they still fit into it) */
 constexpr uint32_t LDS_BYTES_PER_WORKGROUP_AT_FOUR = 160 * 1024 / 4;
+/* KernelArgs::materialsInLds is a word of bits for the kernels with the scene in LDS */
+constexpr uint32_t LDS_MATERIALS = 1u; /* the material records are in LDS too */
+constexpr uint32_t LDS_FOLD = 2u;      /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h) */
 /* the material records are copied to LDS quadword by quadword and read there through a generic pointer */
 static_assert(sizeof(wpt_material) % 16 == 0 && alignof(wpt_material) <= 16, "wpt_material must be a whole number of quadwords");
 /* A batch of views (FEAT_VIEWS kernels): the launch's lane indices g in [0, viewCount * viewPixels) are view g / viewPixels,
@@ -135,7 +139,7 @@ struct KernelArgs {
     const uint32_t* order;        /* second pass: pixels in the order they are handed out */
     const uint32_t* orderCount;   /* second pass: entries of `order` */
     uint32_t cuCount; /* for the launchers: compute units of the device */
-    uint32_t materialsInLds; /* scene in LDS: the material records are there too */
+    uint32_t materialsInLds; /* scene in LDS: LDS_MATERIALS (the material records are there too) | LDS_FOLD */
     wpt_counters* counters;
     unsigned long long* schedStats; /* COUNT builds: 16 scheduler statistics, or NULL */
     union { /* (no launch has both: the kernels of either feature are instantiated without the other) */
@@ -252,17 +256,19 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 
     if (LDSSCENE) {
         /* nodes (2 x float4 each), the null node, then the triangle positions (3 x float4 each).  The LDS copy of a node has
-         * the walk's own word 7 (ldsStep below): an inner node's first child as a plain index, a leaf's word complemented
-         * (>= 2^31), links clamped to nodeCount.  The null node (index nodeCount: skip and child both nodeCount) is where
+         * the walk's own word 7 (ldsStep below, wpt_fold.h): the node a ray that passes an inner node's box goes to as a plain
+         * index -- its first child, or with LDS_FOLD what lies behind the first children that repeat its box -- a leaf's word
+         * complemented (>= 2^31), links clamped to nodeCount.  The null node (index nodeCount: skip and child both nodeCount) is where
          * every lane that does not walk stands, so that a step leaves it where it is whatever its box test says. */
         const uint32_t n4 = 2 * nodeCount, t4 = 3 * sv.triCount;
         for (uint32_t i = threadIdx.x; i < n4; i += WG) {
             float4 q = sv.nodes[i];
             if (i & 1) {
-                const uint32_t skip = __float_as_uint(q.z), word = __float_as_uint(q.w);
+                const uint32_t skip = __float_as_uint(q.z);
+                uint32_t links;
                 q.z = __uint_as_float(skip < nodeCount ? skip : nodeCount);
-                const uint32_t child = word & NODE_INDEX_MASK;
-                q.w = __uint_as_float(word >= NODE_CHILD ? (child < nodeCount ? child : nodeCount) : ~word);
+                q.w = __uint_as_float(wptf::foldLdsWord(reinterpret_cast<const uint32_t*>(sv.nodes), nodeCount, i >> 1,
+                        (args.materialsInLds & LDS_FOLD) != 0, &links));
             }
             ldsScene[i] = q;
         }
@@ -281,7 +287,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
             }
         }
         const uint32_t c4 = ROTATED ? 3 * t4 : t4; /* quadwords of triangle positions in LDS */
-        if (args.materialsInLds) {
+        if (args.materialsInLds & LDS_MATERIALS) {
             /* the material record is what a hit's shading waits for first: fetched from LDS through a generic pointer */
             const uint32_t m4 = sv.materialCount * (uint32_t)(sizeof(wpt_material) / 16);
             const float4* from = reinterpret_cast<const float4*>(sv.materials);

@@ -16,7 +16,7 @@ def lib_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get("WPT_LIB_DIR", "lib"), "libwurblpt_hip.so")
 
 
-WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS = 1, 2, 4, 8, 16  # wpt_set_walk (include/wurblpt_hip.h)
+WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD = 1, 2, 4, 8, 16, 32  # wpt_set_walk (include/wurblpt_hip.h)
 SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
 EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_scene_upload", "wpt_scene_free", "wpt_scene_check",
@@ -25,7 +25,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -252,6 +252,18 @@ def last_slice_stats():
     return int(taken.value), int(continued.value)
 
 
+def fold_plan(host_scene, with_words=False):
+    """wpt_fold_plan: the nodes whose link the kernels with the scene in LDS fold in their copy of the scene's tree; with
+    with_words (count, word 7 of every node's LDS copy as numpy uint32).  Needs no device"""
+    import numpy as np
+    L = lib()
+    L.wpt_fold_plan.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    folded = C.c_uint32()
+    words = np.zeros(int(host_scene.d.node_count), np.uint32)
+    _check(L.wpt_fold_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(folded), C.c_void_p(words.ctypes.data) if with_words else None))
+    return (int(folded.value), words) if with_words else int(folded.value)
+
+
 class DeviceScene:
     """A flattened scene resident in HBM on the current device."""
 
@@ -259,6 +271,14 @@ class DeviceScene:
         self._handle = C.c_void_p()
         _check(lib().wpt_scene_upload(host_scene.desc, C.byref(self._handle)))
         self.host = host_scene
+
+    def folded_links(self):
+        """wpt_scene_folded_links: the folded nodes, counted at the upload"""
+        L = lib()
+        L.wpt_scene_folded_links.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        folded = C.c_uint32()
+        _check(L.wpt_scene_folded_links(self._handle, C.byref(folded)))
+        return int(folded.value)
 
     def close(self):
         if self._handle:
