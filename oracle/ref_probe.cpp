@@ -6,12 +6,14 @@
  * (-I/root/reference/libwurblpt); the binary goes to oracle/_ref/ (git-ignored) and its
  * output to tests/golden/ref_golden.json (committed: data only, no reference source).
  *
- * Only reference headers that compile from the reference tree alone are used:
+ * Only reference headers that compile from the reference tree alone are used here:
  * gvm, prng, sampler, tangentspace, fresnel, ray, aabb, hitable, bvh, transformation,
  * animation, optics, camera, geometryproc.  Everything that (transitively) includes
  * <tgd/array.hpp> -- texture, material*, mesh, hitable_triangle, envmap, sensor, scene,
- * wurblpt.hpp -- needs the external libtgd, which is not in this image, and is therefore NOT
- * built (no stand-in headers are written for it).
+ * wurblpt.hpp -- needs an external container library that is not installed.  That part is the
+ * business of ref_frames.cpp next to this file, which compiles the reference's whole library
+ * with the stand-in container of oracle/tgd_standin/ and pins its mcpt() and its classes
+ * (tests/golden/frames/).
  *
  * Floats are written as their 32-bit patterns (hex) so that comparisons are bit-exact.
  */

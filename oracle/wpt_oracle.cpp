@@ -1449,6 +1449,23 @@ V4 materialEmitted(const Ctx& c, uint32_t mat, const Ray& ray, const HitRecord& 
         }
         return e;
     }
+    case WPT_MAT_LIGHT_SPOT: { /* light_spot.hpp:45-60; with WPT_MATF_TOF_LIGHT light_tof.hpp:55-69 */
+        V4 e = v4(0.0f);
+        if (!hit.backside) {
+            float cosine = dot(hit.normal, -ray.direction);
+            if (cosine >= m.f[0]) { /* inside the opening angle; f[0] = cos(0.5 * openingAngle) */
+                e = v4(m.v[0]);
+                if (m.tex[0] >= 0) {
+                    V3 c3 = rgb(textureValue(c, m.tex[0], hit.texcoords));
+                    if (m.flags & WPT_MATF_TOF_LIGHT)
+                        e.w = e.w * c3.x; /* a ToF light: (0, 0, 0, radiance), the radiance times the texture's red value */
+                    else
+                        e = e * V4 { c3.x, c3.y, c3.z, average3(c3) };
+                }
+            }
+        }
+        return e;
+    }
     case WPT_MAT_MODPHONG: { /* material_modphong.hpp:183-190 */
         V4 e = v4(0.0f);
         if (!hit.backside)
