@@ -16,7 +16,10 @@
  *                  answer under the same file name, for the test to compare.
  *   -DPIN_DEVICE   pin_render <tests/golden> <output directory> [one case]
  *                  the product's mcpt(), linked to libwurblpt_hip.so, time of flight included
- *                  (all phase images in one launch).
+ *                  (all phase images in one launch).  Without [one case] it also answers the hit vectors
+ *                  (tests/golden/frames/vectors_hits_*.npy) on the device: the scenes it builds for them are
+ *                  flattened, uploaded and walked by the library's test hook wpt_selftest_hits_host (the ground
+ *                  truth kernel's walk and finishHit); the rows go to <output directory>/vectors/.
  */
 #include <cstdio>
 #include <cstdint>
@@ -27,6 +30,8 @@
 #include <vector>
 
 #include <dlfcn.h>
+#include <errno.h>
+#include <sys/stat.h>
 
 #include <wurblpt/wurblpt.hpp>
 #include <wurblpt/tof.hpp> /* LightTof, SensorTofAmcw: the reference's umbrella header has them, this set keeps them here */
@@ -230,6 +235,57 @@ static bool renderCase(const PinScenes::Case& c, const std::string& goldenDir, c
     return PinIO::writeNpy(fileName, shape, data.data());
 }
 
+/* test hook of libwurblpt_hip.so, not part of its public header (wpt_capi.hip) */
+extern "C" wpt_status wpt_selftest_hits_host(wpt_scene* scene, int n, const float* rays8_host, float* out15_host);
+
+static bool answerHitVectors(const std::string& goldenDir, const std::string& outDir)
+{
+    if (mkdir(outDir.c_str(), 0777) != 0 && errno != EEXIST)
+        return false;
+    size_t answered = 0;
+    for (const PinScenes::Probe& probe : PinScenes::probes()) {
+        if (std::string(probe.kind) != "hits")
+            continue;
+        const PinScenes::Case& c = *PinScenes::findCase(probe.caseName);
+        const std::string name = std::string("vectors_hits_") + c.name + ".npy";
+        PinScenes::Setup s;
+        PinScenes::setUp(c, s, goldenDir);
+        FlatScene flat;
+        std::string error;
+        if (!s.scene.flatten(flat, &error)) {
+            fprintf(stderr, "%s: %s\n", c.name, error.c_str());
+            return false;
+        }
+        const wpt_scene_desc desc = flat.desc();
+        std::vector<float> rows;
+        if (!PinIO::readRows(goldenDir + "/frames/" + name, 8 + 15, rows))
+            return false;
+        const size_t n = rows.size() / 23;
+        std::vector<float> rays(8 * n), out(15 * n);
+        for (size_t r = 0; r < n; r++)
+            memcpy(rays.data() + 8 * r, rows.data() + 23 * r, 8 * sizeof(float));
+        wpt_scene* dscene = nullptr;
+        if (wpt_scene_upload(&desc, &dscene) != WPT_OK) {
+            fprintf(stderr, "%s: %s\n", c.name, wpt_last_error());
+            return false;
+        }
+        const wpt_status st = wpt_selftest_hits_host(dscene, int(n), rays.data(), out.data());
+        if (st != WPT_OK)
+            fprintf(stderr, "%s: %s\n", c.name, wpt_last_error());
+        wpt_scene_free(dscene);
+        if (st != WPT_OK)
+            return false;
+        for (size_t r = 0; r < n; r++) {
+            memcpy(rows.data() + 23 * r + 8, out.data() + 15 * r, 15 * sizeof(float));
+            rows[23 * r + 9] = 0.0f; /* the index of the triangle: the reference has none to compare with */
+        }
+        if (!PinIO::writeNpy(outDir + "/" + name, { n, 23 }, rows.data()))
+            return false;
+        answered++;
+    }
+    return answered > 0;
+}
+
 int main(int argc, char* argv[])
 {
     if (argc != 3 && argc != 4) {
@@ -243,7 +299,7 @@ int main(int argc, char* argv[])
         if (!renderCase(c, goldenDir, outDir + "/" + c.name + ".npy"))
             return 1;
     }
-    return 0;
+    return (argc == 4 || answerHitVectors(goldenDir, outDir + "/vectors")) ? 0 : 1;
 }
 
 #endif

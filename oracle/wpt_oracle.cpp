@@ -418,7 +418,18 @@ struct Ctx {
     const wpt_params* pr;
     wpt_counters cnt;
     float time = 0.0f; /* stands for the thread's AnimationCache: the time of the path being traced (wurblpt.hpp:361) */
+    /* tally of triangle tests and of those that enter the double-precision fall-back, for the tests that must reach it; per
+     * thread like cnt, summed where cnt is summed (wpt_oracle_triangle_tally) */
+    mutable uint64_t triTests = 0, triFallback = 0;
 };
+static uint64_t g_triTests = 0, g_triFallback = 0;
+/* call it where one thread at a time runs */
+inline void tallySum(Ctx& c)
+{
+    g_triTests += c.triTests;
+    g_triFallback += c.triFallback;
+    c.triTests = c.triFallback = 0;
+}
 
 /* AnimationCache::get / getM / getN of animation `ai` at the path's time (animation.hpp:61-117) */
 inline wptanim::Trs animationAt(const Ctx& c, int ai, float t)
@@ -469,7 +480,9 @@ inline HitRecord triangleHit(const Ctx& c, uint32_t prim, const Ray& ray, const 
     float V = Ax * Cy - Ay * Cx;
     float W = Bx * Ay - By * Ax;
     const float ldeps = float(std::numeric_limits<long double>::epsilon());
+    c.triTests++;
     if (std::fabs(U) < ldeps || std::fabs(V) < ldeps || std::fabs(W) < ldeps) {
+        c.triFallback++;
         double CxBy = double(Cx) * double(By);
         double CyBx = double(Cy) * double(Bx);
         U = CxBy - CyBx;
@@ -1721,6 +1734,7 @@ int wpt_oracle_render(const wpt_scene_desc* scene, const wpt_camera* camera, con
             total.leaf_tests += c.cnt.leaf_tests;
             total.pdf_tests += c.cnt.pdf_tests;
             total.scatters += c.cnt.scatters;
+            tallySum(c);
         }
     }
     if (counters)
@@ -2084,8 +2098,21 @@ int wpt_oracle_ground_truth(const wpt_scene_desc* scene, const wpt_camera* camer
             if (arrays[19])
                 static_cast<int32_t*>(arrays[19])[pixel] = matInd;
         }
+#pragma omp critical
+        tallySum(c);
     }
     return 0;
+}
+
+/* Triangle tests made by wpt_oracle_render, wpt_oracle_ground_truth and wpt_oracle_bvh_hits since the last call, and how many of
+ * them entered the double-precision fall-back (|U|, |V| or |W| below 2^-63); the call resets both.  Not thread safe. */
+void wpt_oracle_triangle_tally(uint64_t* tests, uint64_t* fallback)
+{
+    if (tests)
+        *tests = g_triTests;
+    if (fallback)
+        *fallback = g_triFallback;
+    g_triTests = g_triFallback = 0;
 }
 
 /* LensDistortion::undistort then ::distort of the result (optics.hpp:214-308): pq -> 4 floats per point */
@@ -2564,6 +2591,7 @@ void wpt_oracle_bvh_hits(const wpt_scene_desc* scene, int n, const float* rays, 
     }
     if (counters)
         *counters = c.cnt;
+    tallySum(c);
 }
 
 /* BVH::hit over caller-given nodes whose leaves are "probe hitables": leaf `prim` reports a

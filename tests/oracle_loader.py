@@ -131,6 +131,13 @@ class Oracle:
         self.L.wpt_oracle_bvh_hits(scene.desc, C.c_int(n), C.c_void_p(rays8.ctypes.data), C.c_void_p(out.ctypes.data), C.byref(cnt))
         return out, cnt.as_dict()
 
+    def triangle_tally(self):
+        """(triangle tests, those that entered the double-precision fall-back) of the renders, ground truth calls and bvh_hits
+        since the last call; resets both"""
+        tests, fallback = C.c_uint64(), C.c_uint64()
+        self.L.wpt_oracle_triangle_tally(C.byref(tests), C.byref(fallback))
+        return int(tests.value), int(fallback.value)
+
     def wide_walk_check(self, scene, rays8):
         """The collapsed four-wide walk of DESIGN.md section 7.1 next to BVH::hit: (rays that differ, statistics)."""
         rays8 = np.ascontiguousarray(rays8, np.float32)

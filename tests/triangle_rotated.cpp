@@ -2,6 +2,12 @@
 // selected by the ray's axes) against triangleTestRotated (corners and origin in the order of the ray's kz, the swap as a sign
 // flip), on uint32 views of accepted, a, invDet, U, V, W, with the ray's constants from rayAux / rayAuxRotated as the walk makes
 // them and again as the light-pdf loop does (SHEAR_ONLY).  One line per set: cases, accepted, fall-back, differences.
+//
+// Second mode, `triangle_rotated --dump FILE N`: the first N cases of every set, made by one thread from the set's seed, written
+// to FILE for the tests that give them to the device (tests/test_gpu_triangle.py) or evaluate them exactly
+// (tests/test_triangle_exact.py).  Per case 26 words of 32 bits: the 17 floats of the case (v0, v1, v2, origin, direction, amin,
+// amax), the select form's host result (accepted, then the bits of a, invDet, U, V, W, zero when rejected), 1 where the case enters
+// the double-precision fall-back, RayAux::k of rayAux and of rayAuxRotated.  The sets follow one another in the order of main().
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +47,36 @@ static inline bool entersFallback(f3 v0, f3 v1, f3 v2, f3 org, const RayAux& h)
     return __builtin_fabsf(U) < k_ldeps || __builtin_fabsf(V) < k_ldeps || __builtin_fabsf(W) < k_ldeps;
 }
 
+/* --dump: where one() writes the cases it sees, and how many the set still owes */
+struct Dump {
+    FILE* file = nullptr;
+    long long left = 0;
+};
+static Dump g_dump;
+
+static inline void dumpCase(f3 v0, f3 v1, f3 v2, f3 org, f3 dir, float amin, float amax, bool accepted, const Candidate& c, bool fallback, int k, int kRotated)
+{
+    if (!g_dump.file || g_dump.left <= 0)
+        return;
+    const float in[17] = { v0.x, v0.y, v0.z, v1.x, v1.y, v1.z, v2.x, v2.y, v2.z, org.x, org.y, org.z, dir.x, dir.y, dir.z, amin, amax };
+    uint32_t w[26];
+    memcpy(w, in, sizeof in);
+    w[17] = accepted ? 1u : 0u;
+    w[18] = accepted ? bits(c.a) : 0u;
+    w[19] = accepted ? bits(c.invDet) : 0u;
+    w[20] = accepted ? bits(c.U) : 0u;
+    w[21] = accepted ? bits(c.V) : 0u;
+    w[22] = accepted ? bits(c.W) : 0u;
+    w[23] = fallback ? 1u : 0u;
+    w[24] = (uint32_t)k;
+    w[25] = (uint32_t)kRotated;
+    if (fwrite(w, sizeof w, 1, g_dump.file) != 1) {
+        perror("--dump");
+        exit(2);
+    }
+    g_dump.left--;
+}
+
 /* one case through both forms */
 static inline void one(f3 v0, f3 v1, f3 v2, f3 org, f3 dir, float amin, float amax, Tally& t)
 {
@@ -59,8 +95,10 @@ static inline void one(f3 v0, f3 v1, f3 v2, f3 org, f3 dir, float amin, float am
         t.swapped++;
     if (ha)
         t.accepted++;
-    if (entersFallback(v0, v1, v2, org, h))
+    const bool fallback = entersFallback(v0, v1, v2, org, h);
+    if (fallback)
         t.fallback++;
+    dumpCase(v0, v1, v2, org, dir, amin, amax, ha, a, fallback, h.k, r.k);
     bool same = ha == hb && auxKz(h) == kz;
     if (ha && hb)
         same = same && bits(a.a) == bits(b.a) && bits(a.invDet) == bits(b.invDet) && bits(a.U) == bits(b.U) && bits(a.V) == bits(b.V) && bits(a.W) == bits(b.W);
@@ -99,6 +137,13 @@ static unsigned long long report(const char* name, const Tally& t)
 template<class Case> static Tally run(long long count, uint64_t seed, Case make)
 {
     Tally total;
+    if (g_dump.file) { /* --dump: `count` cases, whatever the number of threads */
+        uint64_t s = seed;
+        g_dump.left = count;
+        for (long long i = 0; g_dump.left > 0; i++)
+            make(s, i, total);
+        return total;
+    }
 #pragma omp parallel
     {
         Tally t;
@@ -116,11 +161,21 @@ static inline f3 rnd3(uint64_t& s, float r) { return mk3(sym(s, r), sym(s, r), s
 
 int main(int argc, char** argv)
 {
-    const long long N = argc > 1 ? atoll(argv[1]) : 100000000ll;
+    const bool dump = argc == 4 && strcmp(argv[1], "--dump") == 0;
+    if (argc > 1 && argv[1][0] == '-' && !dump) {
+        fprintf(stderr, "usage: %s [cases of the random set] | --dump FILE cases-per-set\n", argv[0]);
+        return 2;
+    }
+    /* --dump runs every set for 20 N cases, which each of them divides by 20 again */
+    const long long N = dump ? 20 * atoll(argv[3]) : (argc > 1 ? atoll(argv[1]) : 100000000ll);
+    if (dump && (N <= 0 || !(g_dump.file = fopen(argv[2], "wb")))) {
+        perror(argv[2]);
+        return 2;
+    }
     unsigned long long bad = 0;
 
     /* random rays aimed at a point inside (or a little outside) a random triangle: about half of them hit */
-    bad += report("random", run(N, 1, [](uint64_t& s, long long, Tally& t) {
+    bad += report("random", run(dump ? N / 20 : N, 1, [](uint64_t& s, long long, Tally& t) {
         const f3 v0 = rnd3(s, 10.0f), v1 = rnd3(s, 10.0f), v2 = rnd3(s, 10.0f), org = rnd3(s, 20.0f);
         const float u = 1.5f * unit(s) - 0.25f, v = 1.5f * unit(s) - 0.25f;
         const f3 target = add(v0, add(scl(u, sub(v1, v0)), scl(v, sub(v2, v0))));
@@ -181,6 +236,45 @@ int main(int argc, char** argv)
         one(v0, v1, v2, org, dir, -3.402823466e+38f, 3.402823466e+38f, t);
     }));
 
+    /* products of two numbers near 2^-62: the differences U, V, W are denormal or zero in single precision, det often so small
+     * that invDet is infinite (and a = invDet * T infinite or NaN); every case enters the fall-back */
+    bad += report("denormal products", run(N / 20, 6, [](uint64_t& s, long long i, Tally& t) {
+        const float scale = ldexpf(1.0f, -60 - (int)(i % 4));
+        const f3 org = rnd3(s, ldexpf(1.0f, -58));
+        const f3 v0 = add(org, rnd3(s, scale)), v1 = add(org, rnd3(s, scale)), v2 = add(org, rnd3(s, scale));
+        const f3 c = mk3((v0.x + v1.x + v2.x) / 3.0f, (v0.y + v1.y + v2.y) / 3.0f, (v0.z + v1.z + v2.z) / 3.0f);
+        f3 dir = sub(c, org);
+        if (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f)
+            dir = rnd3(s, 1.0f);
+        one(v0, v1, v2, org, dir, -3.402823466e+38f, 3.402823466e+38f, t);
+    }));
+
+    /* accepted cases of the random set again, with amin or amax at the case's own a or at one of the two floats next to it:
+     * Ts < amin * ds and Ts > amax * ds are decided at or next to equality */
+    bad += report("interval ends", run(N / 20, 7, [](uint64_t& s, long long i, Tally& t) {
+        for (;;) {
+            const f3 v0 = rnd3(s, 10.0f), v1 = rnd3(s, 10.0f), v2 = rnd3(s, 10.0f), org = rnd3(s, 20.0f);
+            const float u = 1.5f * unit(s) - 0.25f, v = 1.5f * unit(s) - 0.25f;
+            const f3 target = add(v0, add(scl(u, sub(v1, v0)), scl(v, sub(v2, v0))));
+            f3 dir = sub(target, org);
+            const float len = __builtin_sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
+            dir = mk3(dir.x / len, dir.y / len, dir.z / len);
+            Candidate c;
+            if (!triangleTest(v0, v1, v2, org, rayAux(dir), 1e-4f, 3.402823466e+38f, c))
+                continue;
+            const float end = (i % 3) == 0 ? nextafterf(c.a, -INFINITY) : ((i % 3) == 1 ? c.a : nextafterf(c.a, INFINITY));
+            if ((i / 3) & 1)
+                one(v0, v1, v2, org, dir, 1e-4f, end, t);
+            else
+                one(v0, v1, v2, org, dir, end, 3.402823466e+38f, t);
+            return;
+        }
+    }));
+
+    if (dump && fclose(g_dump.file) != 0) {
+        perror(argv[2]);
+        return 2;
+    }
     printf("total: %llu differences\n", bad);
     return bad == 0 ? 0 : 1;
 }

@@ -74,6 +74,50 @@ WPT_D void store1(void* array, uint32_t pixel, float v)
 
 constexpr uint32_t GT_FEATURES = FEAT_TEXTURES | FEAT_LENS | FEAT_SPHERES | FEAT_ANIM;
 
+/* BVH::hit (bvh.hpp:270-329) in the stackless form: the closest candidate in [amin, amax], later candidates win ties */
+WPT_D Candidate closestHit(const SceneView& sv, f3 o, f3 d, float amin, float amax, float time)
+{
+    const RayAux aux = rayAux(d);
+    Candidate best;
+    best.prim = NO_HIT;
+    best.a = best.invDet = best.U = best.V = best.W = 0.0f;
+    uint32_t node = 0;
+    while (node < sv.nodeCount) {
+        const float4 n0 = sv.nodes[2 * node], n1 = sv.nodes[2 * node + 1];
+        const uint32_t skip = __float_as_uint(n1.z);
+        const uint32_t prim = __float_as_uint(n1.w);
+        const bool hit = boxTest(nodeLo(n0, n1), nodeHi(n0, n1), o, aux.inv, amin, amax);
+        if (hit && prim < NODE_CHILD) {
+            Candidate c;
+            bool accepted;
+            if (prim & PRIM_SPHERE) {
+                c.invDet = c.U = c.V = c.W = 0.0f;
+                accepted = sphereTest(sphereAt<GT_FEATURES>(sv, sv.spheres[prim & ~PRIM_SPHERE], time), o, d, amin, amax, c.a);
+            } else {
+                const float4 g0 = sv.triGeom[3 * (size_t)prim], g1 = sv.triGeom[3 * (size_t)prim + 1], g2 = sv.triGeom[3 * (size_t)prim + 2];
+                f3 v0 = mk3(g0.x, g0.y, g0.z), v1 = mk3(g1.x, g1.y, g1.z), v2 = mk3(g2.x, g2.y, g2.z);
+                if (__float_as_uint(g2.w) & WPT_TRI_ANIMATE) {
+                    float animationM[16];
+                    wptanim::toMat4(animationAt(sv, sv.instances[__float_as_uint(g0.w)].animation, time), animationM);
+                    v0 = animatePoint(animationM, v0);
+                    v1 = animatePoint(animationM, v1);
+                    v2 = animatePoint(animationM, v2);
+                }
+                accepted = triangleTest(v0, v1, v2, o, aux, amin, amax, c);
+            }
+            if (accepted) {
+                c.prim = prim;
+                best = c;
+                amax = c.a;
+            }
+            node = skip; /* a leaf's subtree is the leaf itself */
+        } else {
+            node = hit ? (prim & NODE_INDEX_MASK) : skip;
+        }
+    }
+    return best;
+}
+
 __global__ void __launch_bounds__(256) wpt_ground_truth_kernel(const GroundTruthArgs args)
 {
     const uint32_t pixel = blockIdx.x * blockDim.x + threadIdx.x;
@@ -97,46 +141,7 @@ __global__ void __launch_bounds__(256) wpt_ground_truth_kernel(const GroundTruth
     pathStateInit(ps, pixel, pixel % args.width, pixel / args.width);
     blockNew<GT_FEATURES>(fa, ps, sv); /* par.t0 == par.t1: no time draw, ps.time = t0 */
 
-    /* BVH::hit (bvh.hpp:270-329): closest candidate, later candidates win ties */
-    const RayAux aux = rayAux(ps.d);
-    Candidate best;
-    best.prim = NO_HIT;
-    best.a = best.invDet = best.U = best.V = best.W = 0.0f;
-    float amax = k_maxval;
-    uint32_t node = 0;
-    while (node < sv.nodeCount) {
-        const float4 n0 = sv.nodes[2 * node], n1 = sv.nodes[2 * node + 1];
-        const uint32_t skip = __float_as_uint(n1.z);
-        const uint32_t prim = __float_as_uint(n1.w);
-        const bool hit = boxTest(nodeLo(n0, n1), nodeHi(n0, n1), ps.o, aux.inv, args.par.min_hit_distance, amax);
-        if (hit && prim < NODE_CHILD) {
-            Candidate c;
-            bool accepted;
-            if (prim & PRIM_SPHERE) {
-                c.invDet = c.U = c.V = c.W = 0.0f;
-                accepted = sphereTest(sphereAt<GT_FEATURES>(sv, sv.spheres[prim & ~PRIM_SPHERE], ps.time), ps.o, ps.d, args.par.min_hit_distance, amax, c.a);
-            } else {
-                const float4 g0 = sv.triGeom[3 * (size_t)prim], g1 = sv.triGeom[3 * (size_t)prim + 1], g2 = sv.triGeom[3 * (size_t)prim + 2];
-                f3 v0 = mk3(g0.x, g0.y, g0.z), v1 = mk3(g1.x, g1.y, g1.z), v2 = mk3(g2.x, g2.y, g2.z);
-                if (__float_as_uint(g2.w) & WPT_TRI_ANIMATE) {
-                    float animationM[16];
-                    wptanim::toMat4(animationAt(sv, sv.instances[__float_as_uint(g0.w)].animation, ps.time), animationM);
-                    v0 = animatePoint(animationM, v0);
-                    v1 = animatePoint(animationM, v1);
-                    v2 = animatePoint(animationM, v2);
-                }
-                accepted = triangleTest(v0, v1, v2, ps.o, aux, args.par.min_hit_distance, amax, c);
-            }
-            if (accepted) {
-                c.prim = prim;
-                best = c;
-                amax = c.a;
-            }
-            node = skip; /* a leaf's subtree is the leaf itself */
-        } else {
-            node = hit ? (prim & NODE_INDEX_MASK) : skip;
-        }
-    }
+    const Candidate best = closestHit(sv, ps.o, ps.d, args.par.min_hit_distance, k_maxval, ps.time);
 
     const f3 zero3 = mk3(0.0f, 0.0f, 0.0f);
     f3 wsPos = zero3, wsGNrm = zero3, wsGTan = zero3, wsMNrm = zero3, wsMTan = zero3;
@@ -237,6 +242,49 @@ __global__ void __launch_bounds__(256) wpt_ground_truth_kernel(const GroundTruth
     store2(args.array[18], pixel, psON);
     if (args.array[19])
         static_cast<int32_t*>(args.array[19])[pixel] = matInd;
+}
+
+/* wpt_selftest_hits: BVH::hit for given rays at time 0 and the finished record, in the layout of the restatement's
+ * wpt_oracle_bvh_hits: haveHit, prim, a, position, normal, tangent, texcoords, backside (all zero without a hit) */
+struct SelftestHitsArgs {
+    SceneView scene;
+    int n;
+    const float* rays8;
+    float* out15;
+};
+__global__ void __launch_bounds__(256) wpt_selftest_hits_kernel(const SelftestHitsArgs args)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= args.n)
+        return;
+    const SceneView& sv = args.scene;
+    const float* r = args.rays8 + 8 * (size_t)i;
+    const f3 o = ld3(r), d = ld3(r + 3);
+    const Candidate best = closestHit(sv, o, d, r[6], r[7], 0.0f);
+    float* out = args.out15 + 15 * (size_t)i;
+    for (int k = 0; k < 15; k++)
+        out[k] = 0.0f;
+    if (best.prim != NO_HIT) {
+        const Hit h = finishHit<GT_FEATURES>(sv, best, o, d, 0.0f);
+        out[0] = 1.0f;
+        out[1] = (float)(best.prim & ~PRIM_SPHERE);
+        out[2] = h.a;
+        out[3] = h.p.x; out[4] = h.p.y; out[5] = h.p.z;
+        out[6] = h.n.x; out[7] = h.n.y; out[8] = h.n.z;
+        out[9] = h.t.x; out[10] = h.t.y; out[11] = h.t.z;
+        out[12] = h.tc.x; out[13] = h.tc.y;
+        out[14] = h.backside ? 1.0f : 0.0f;
+    }
+}
+
+void launchSelftestHits(const SceneView& scene, int n, const float* rays8, float* out15, hipStream_t stream)
+{
+    SelftestHitsArgs args;
+    args.scene = scene;
+    args.n = n;
+    args.rays8 = rays8;
+    args.out15 = out15;
+    hipLaunchKernelGGL(wpt_selftest_hits_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, args);
 }
 
 void launchGroundTruth(const GroundTruthArgs& args, hipStream_t stream)

@@ -961,6 +961,8 @@ struct GroundTruthArgs {
     void* array[WPT_GT_ARRAY_COUNT];
 };
 void launchGroundTruth(const GroundTruthArgs& args, hipStream_t stream);
+/* test hook (wpt_selftest_hits): the ground truth kernel's walk and finishHit for n given rays (origin, direction, amin, amax) */
+void launchSelftestHits(const SceneView& scene, int n, const float* rays8, float* out15, hipStream_t stream);
 
 /* one launcher per instantiation, each defined in its own translation unit; sceneLdsBytes is the size of the scene
  * copy behind the cold path words in LDS (0 for the kernels that fetch the scene from HBM) */

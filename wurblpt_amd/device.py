@@ -603,6 +603,61 @@ def selftest_aabb(boxes, rays):
     return out.cpu().numpy()
 
 
+def selftest_triangle(form, cases):
+    """The watertight triangle test as the kernels call it (wpt_selftest_triangle_kernel).  cases (n, 17): v0 v1 v2 origin
+    direction amin amax; form 0 rayAux + triangleTest, 1 rayAuxRotated + triangleTestRotated, 2 and 3 their forms in the
+    light-pdf loop.  Returns uint32 (n, 8): accepted, the bits of a, invDet, U, V, W (zero when rejected), RayAux::k, spare."""
+    import numpy as np
+    import torch
+    tc = torch.as_tensor(np.ascontiguousarray(cases, dtype=np.float32).reshape(-1, 17), device="cuda")
+    out = torch.zeros((tc.shape[0], 8), dtype=torch.int32, device="cuda")
+    L = lib()
+    L.wpt_selftest_triangle.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.wpt_selftest_triangle(form, tc.shape[0], C.c_void_p(tc.data_ptr()), C.c_void_p(out.data_ptr())))
+    return out.cpu().numpy().view(np.uint32)
+
+
+def selftest_rayaux(dirs):
+    """The ray's constants as the kernels make them.  dirs (n, 3); returns float32 (n, 2, 9): inv (3), kx ky kz, S (3) from
+    rayAux and from rayAuxRotated (its swap applied)."""
+    import numpy as np
+    import torch
+    td = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device="cuda")
+    out = torch.zeros((td.shape[0], 2, 9), dtype=torch.float32, device="cuda")
+    L = lib()
+    L.wpt_selftest_rayaux.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.wpt_selftest_rayaux(td.shape[0], C.c_void_p(td.data_ptr()), C.c_void_p(out.data_ptr())))
+    return out.cpu().numpy()
+
+
+def selftest_sphere(spheres, rays):
+    """sphereTest as the kernels evaluate it: spheres (n, 4) centre radius, rays (n, 8) origin dir amin amax; returns float32
+    (n, 2): accepted, a."""
+    import numpy as np
+    import torch
+    ts = torch.as_tensor(np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4), device="cuda")
+    tr = torch.as_tensor(np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8), device="cuda")
+    assert ts.shape[0] == tr.shape[0]
+    out = torch.zeros((ts.shape[0], 2), dtype=torch.float32, device="cuda")
+    L = lib()
+    L.wpt_selftest_sphere.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.wpt_selftest_sphere(ts.shape[0], C.c_void_p(ts.data_ptr()), C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
+    return out.cpu().numpy()
+
+
+def selftest_hits(scene, rays8):
+    """The closest hit of a DeviceScene and its finished record for rays (n, 8) origin dir amin amax, at time 0: float32 (n, 15)
+    in the layout of the restatement's bvh_hits (haveHit, prim, a, position, normal, tangent, texcoords, backside)."""
+    import numpy as np
+    import torch
+    tr = torch.as_tensor(np.ascontiguousarray(rays8, dtype=np.float32).reshape(-1, 8), device="cuda")
+    out = torch.zeros((tr.shape[0], 15), dtype=torch.float32, device="cuda")
+    L = lib()
+    L.wpt_selftest_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.wpt_selftest_hits(scene._handle, tr.shape[0], C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
+    return out.cpu().numpy()
+
+
 def selftest_math(op, a, b=None):
     """Evaluates one arithmetic primitive of the kernel on the GPU (see wpt_selftest_kernel)."""
     import torch
