@@ -641,6 +641,20 @@ const char* wpt_kernel_name(void);
  * the kernel with the scene in LDS that holds the corners in all three rotations (WPT_WALK_SELECT_CORNERS above), otherwise ""; ", sliced xU" behind it where the launch handed its pixels out in U units each
  * (wpt_set_slices). */
 const char* wpt_kernel_form(void);
+/* Which instantiation of the single kernel renders a launch, from the facts the library decides by: a pure function that needs
+ * no device (tests).  need: the feature bits of the scene and the launch's cameras (wpt_device.h, FEAT_*; FEAT_ANIM for a moving
+ * scene, a moving camera or an exposure interval); sensor: 0 one frame, 1 transient film, 2 batch of views, 3 adaptive sampling,
+ * 4 time of flight; count: the launch counts its work; node_count, tri_count, material_count: the scene's; scene_has_wide: it was
+ * uploaded under WPT_WALK_WIDE and has the collapsed tree; variant, walk: the words of wpt_set_launch_config and wpt_set_walk.
+ * Results: wpt_kernel_name and wpt_kernel_form (without ", sliced xU") of such a launch, key = the kernel's template arguments
+ * { F, COUNT, LDSSCENE, WIDE }, the bytes of LDS behind the paths' own words that the launch asks for (0: the scene is fetched
+ * from HBM), and the word of KernelArgs::materialsInLds (1: the material records are in LDS too, 2: the LDS copy of the tree is
+ * folded).  WPT_ERR_UNSUPPORTED, with the key in the message, if the library has no such kernel.
+ * wpt_kernel_table_entry: row `index` of the table of the kernels the library has (WPT_ERR_INVALID_ARGUMENT behind its end). */
+wpt_status wpt_kernel_choice(uint32_t need, uint32_t sensor, uint32_t count, uint32_t node_count, uint32_t tri_count, uint32_t material_count,
+        uint32_t scene_has_wide, uint32_t variant, uint32_t walk, const char** name, const char** form, uint32_t key[4],
+        uint64_t* scene_lds_bytes, uint32_t* materials_in_lds);
+wpt_status wpt_kernel_table_entry(uint32_t index, uint32_t key[4], const char** name);
 /* What the reference records about a run for the CPU (wurblpt.hpp:393-400,425-435: COMPILER, CPU_MODEL), for the device:
  * marketing name and architecture of HIP device `device` ("AMD Instinct MI355X (gfx950:...)", or "" if there is none), and
  * the compiler and options the kernels were built with.  The strings live until the next call from the same thread. */

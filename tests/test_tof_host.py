@@ -457,6 +457,7 @@ def test_existing_translation_units_are_recorded_unchanged():
     assert new == ["wpt_k_basic_lds_tof", "wpt_k_full_anim_tof", "wpt_k_full_rgl_anim_tof", "wpt_k_full_tof"]
     assert all(v == "same" for u, v in verdict.items() if u not in new), verdict
     makefile = open(os.path.join(ROOT, "wurblpt_amd", "csrc", "Makefile")).read()
-    units = {w[len("$(BUILD)/"):-2] for w in makefile.split() if w.startswith("$(BUILD)/wpt_") and w.endswith(".o")}
+    units = {l.strip(" \\") for l in makefile.splitlines() if l.startswith("    wpt_")}  # UNITS, one name per line (the sliced twins, which came later, have a line of their own)
     hip_units = {u for u in units if os.path.exists(os.path.join(ROOT, "wurblpt_amd", "csrc", u + ".hip"))}
+    assert len(hip_units) == 44
     assert hip_units - {"wpt_wavefront_host"} <= set(verdict), sorted(hip_units - set(verdict))

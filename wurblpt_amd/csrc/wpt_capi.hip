@@ -15,6 +15,7 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_pathtrace.inc.h"
+#include "wpt_kernel_table.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 
@@ -313,6 +314,22 @@ const char* ldsKernelForm(bool rotated, uint32_t units)
         return f;
     }();
     return forms[(rotated ? wptk::SLICE_UNITS_MAX + 1 : 0) + (units <= wptk::SLICE_UNITS_MAX ? units : 0)].c_str();
+}
+
+/* wpt_kernel_form of a launch that is not sliced */
+const char* kernelForm(const wptk::KernelChoice& choice)
+{
+    return choice.rotated ? "rotated corners" : "";
+}
+
+/* the kernel table's row for an instantiation; there is no launch without one */
+wpt_status lookupKernel(uint32_t features, bool count, bool ldsScene, bool wide, const wptk::KernelEntry** entry)
+{
+    *entry = wptk::findKernel(features, count, ldsScene, wide);
+    if (!*entry)
+        return fail(WPT_ERR_UNSUPPORTED, "the library has no kernel wpt_pathtrace<F = " + std::to_string(features) + ", COUNT = " + std::to_string(count)
+                + ", LDSSCENE = " + std::to_string(ldsScene) + ", WIDE = " + std::to_string(wide) + ">");
+    return WPT_OK;
 }
 
 unsigned long long* sliceStatsOfCurrentDevice()
@@ -1122,7 +1139,6 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     /* an exposure interval changes every path (each camera ray draws its time), moving instances need the time too */
     if (params->t0 != params->t1)
         need |= FEAT_ANIM;
-    const bool anim = (need & FEAT_ANIM) != 0;
     dim3 grid((block_size + WG - 1) / WG);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const bool count = counters_device != nullptr;
@@ -1131,12 +1147,10 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * reference's; measurements (wpt_set_walk): WPT_WALK_COUNT_PRODUCT makes them count what the product kernel walks,
      * WPT_WALK_FULL_SHADOW switches the short cut off everywhere. */
     args.shadowWalksEnd = (g_walk & WPT_WALK_FULL_SHADOW) ? 0u : (count ? ((g_walk & WPT_WALK_COUNT_PRODUCT) ? 1u : 0u) : 1u);
-    const size_t sceneBytes = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48;
-    const size_t ldsBytes = sceneBytes + 32; /* the LDS copy: nodes, the null node, triangles */
     /* scheduler defaults from sweeps on the Cornell box (scene in LDS, short walks) and on the
      * Sponza-class scene (deep tree in HBM: traversal dominates, so long blocks may run with fewer
      * lanes and leaf tests earlier) */
-    const bool smallScene = sceneBytes <= LDS_SCENE_MAX_BYTES;
+    const bool smallScene = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48 <= LDS_SCENE_MAX_BYTES;
     /* clamped: with more than 8 eighths the traversal block would leave before doing anything */
     args.leaveEighths = g_leaveEighths ? (g_leaveEighths > 8u ? 8u : g_leaveEighths) : (smallScene ? 1u : 3u);
     args.heavyMin = g_heavyMin ? g_heavyMin : (smallScene ? 16u : 8u);
@@ -1144,18 +1158,32 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     /* variant bits 2-3: 0 = default, 1 = no kind of material ever stands back, 2 / 3 = fewer than 3 / 12 lanes */
     static const uint32_t waitBelowChoices[4] = { 6u, 0u, 3u, 12u };
     args.waitBelow = waitBelowChoices[(g_variant >> 2) & 0x3u];
-    /* kernel choice.  Low nibble of the variant word: 1 = keep the scene in HBM, 2 = all features. */
-    const uint32_t force = g_variant & 0x3u;
-    /* (the time-of-flight kernel with the scene in LDS knows spot lights and two-sided materials besides) */
-    const bool basic = (need & ~(tof ? FEAT_BASIC | FEAT_SPOT | FEAT_TWOSIDED : FEAT_BASIC)) == 0 && force != 2;
-    const bool lds = smallScene && force != 1;
-    const bool rgl = (need & FEAT_RGL) != 0; /* measured BRDFs have their own instantiation */
+    /* kernel choice (wpt_kernel_table.h) */
+    const wptk::Sensor sensor = tof ? wptk::SENSOR_TOF : adaptive ? wptk::SENSOR_ADAPTIVE : views ? wptk::SENSOR_VIEWS
+            : transient ? wptk::SENSOR_TRANSIENT : wptk::SENSOR_FRAME;
+    const wptk::KernelChoice choice = wptk::selectKernel({ need, sensor, count, scene->nodeCount, scene->triCount, uint32_t(scene->view.materialCount),
+            scene->view.wideNodes != nullptr, g_variant, g_walk });
+    const wptk::KernelEntry *kernel = nullptr, *slicedKernel = nullptr;
+    wpt_status found = lookupKernel(choice.features, choice.count, choice.ldsScene, choice.wide, &kernel);
+    /* its twin that hands pixels out in slices, for the slicing block below */
+    const bool mayBeSliced = choice.sceneInLds && sensor == wptk::SENSOR_FRAME && !count;
+    if (found == WPT_OK && mayBeSliced)
+        found = lookupKernel(choice.features | FEAT_SLICED, choice.count, choice.ldsScene, choice.wide, &slicedKernel);
+    if (found != WPT_OK)
+        return found;
+    const bool rgl = (need & FEAT_RGL) != 0;
+    args.cuCount = uint32_t(scene->cuCount);
+    args.rowStop = samples_sqrt;
+    args.carry = nullptr;
+    args.cost = nullptr;
+    args.order = nullptr;
+    args.orderCount = nullptr;
     /* Pixel pool: frames with more pixels than the device has lanes at once are handed out pixel by pixel (the launchers
      * decide); variant bit 0x10: never.  The counter is allocated and freed in stream order, so launches in flight on any
      * number of streams never share one. */
     /* Wavefront form (wpt_wavefront.inc.h): trace and shade as two kernels that hand rays through HBM.  Not for counting
      * launches and moving scenes (those instantiations exist for the single kernel only). */
-    const bool wfExists = !count && !anim && !transient && !views && !adaptive; /* (a transient film, a batch of views and an adaptive launch are always rendered by the single kernel) */
+    const bool wfExists = sensor == wptk::SENSOR_FRAME && !count && !(need & FEAT_ANIM); /* (a transient film, a batch of views and an adaptive launch are always rendered by the single kernel) */
     /* The library's own choice (measured): launches of 2^21 lanes and more whose scene has measured BRDFs --
      * long shading that pays for being sorted by kind of material, and enough lanes to fill the trace and the shade kernel one
      * after the other (tools/wf_threshold_probe.py, 16 spp, single kernel / wavefront: 115.5 / 100.7 Msamples/s at 2^20 lanes,
@@ -1165,14 +1193,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     const bool wfAuto = rgl && block_size >= (1u << 21);
     if (wfExists && (g_wfMode == 1u || (g_wfMode == 0u && wfAuto))) {
         args.pool = nullptr;
-        args.cuCount = uint32_t(scene->cuCount);
         args.materialsInLds = 0;
-        args.rowStop = samples_sqrt;
-        args.carry = nullptr;
-        args.cost = nullptr;
-        args.order = nullptr;
-        args.orderCount = nullptr;
-        const wptk::WfLaunchers& kernels = rgl ? wptk::wfFullRgl() : (basic ? wptk::wfBasic() : wptk::wfFull());
+        const wptk::WfLaunchers& kernels = rgl ? wptk::wfFullRgl() : (choice.basic ? wptk::wfBasic() : wptk::wfFull());
         uint32_t launches = 0;
         const hipError_t e = wptk::renderWavefront(args, kernels, g_wfConfig, stream, &launches);
         if (e == hipSuccess) {
@@ -1194,139 +1216,10 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         pool = nullptr;
     }
     args.pool = pool;
-    args.cuCount = uint32_t(scene->cuCount);
-    /* the material records join the scene in LDS where a quarter of a compute unit's 160 KiB holds a workgroup with them */
-    args.materialsInLds = (!(g_variant & 0x80u) && COLD_BYTES + ldsBytes + size_t(scene->view.materialCount) * sizeof(wpt_material) <= LDS_BYTES_PER_WORKGROUP_AT_FOUR) ? 1u : 0u;
-    /* The corners in LDS three times, once per rotation of (x, y, z), so that a triangle test reads them in its ray's component
-     * order and selects nothing by axis (wpt_triangle.h, triangleTestRotated): plain product launches of the kernel with the scene in
-     * LDS, where the two extra copies still leave four workgroups per compute unit.  The copies come before the material records:
-     * those then stay in HBM unless they fit as well (the Cornell box: 40 768 of 40 960 bytes with the copies; DESIGN.md section 4
-     * has both measured).  wpt_set_walk(WPT_WALK_SELECT_CORNERS) keeps the kernel that selects. */
-    const size_t rotatedBytes = ldsBytes + 2 * size_t(scene->triCount) * 48;
-    const bool rotated = basic && lds && !count && !anim && !rgl && !transient && !views && !adaptive && !(g_walk & WPT_WALK_SELECT_CORNERS)
-            && COLD_BYTES + rotatedBytes <= LDS_BYTES_PER_WORKGROUP_AT_FOUR;
-    if (rotated)
-        args.materialsInLds = (!(g_variant & 0x80u) && COLD_BYTES + rotatedBytes + size_t(scene->view.materialCount) * sizeof(wpt_material) <= LDS_BYTES_PER_WORKGROUP_AT_FOUR) ? 1u : 0u;
-    /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h); wpt_set_walk(WPT_WALK_NO_FOLD)
-     * keeps every node's own first child */
-    if (!(g_walk & WPT_WALK_NO_FOLD))
-        args.materialsInLds |= LDS_FOLD;
-    g_kernelForm.store(rotated ? "rotated corners" : "", std::memory_order_relaxed);
-    args.rowStop = samples_sqrt;
-    args.carry = nullptr;
-    args.cost = nullptr;
-    args.order = nullptr;
-    args.orderCount = nullptr;
-    /* the wide walk where the scene has that form (wpt_set_walk before the upload): product launches of the kernels that fetch
-     * the scene from HBM; counting launches and moving scenes walk the binary tree */
-    const bool wide = scene->view.wideNodes != nullptr && !count && !anim && !(basic && lds) && !transient && !views && !adaptive; /* (the kernel with the scene in LDS walks the binary tree) */
-    g_kernelName.store(wide ? "wpt_pathtrace, wide walk" : nullptr, std::memory_order_relaxed);
-    /* the transient film: the LDS kernel for the Cornell class, the all-features kernel for other scenes at rest, the moving-scene
-     * kernels for moving scenes and for measured BRDFs */
-    const bool transientLds = transient && basic && lds && !anim && !rgl;
-    if (transient && !tof)
-        g_kernelName.store(transientLds ? "wpt_pathtrace, transient, scene in LDS"
-                : rgl ? "wpt_pathtrace, transient, measured BRDFs"
-                : anim ? "wpt_pathtrace, transient, all features, moving scenes" : "wpt_pathtrace, transient, all features", std::memory_order_relaxed);
-    /* a batch of views: the kernel of its scene kind as for one frame; measured BRDFs take the moving-scene instantiation */
-    const bool viewsLds = views && basic && lds && !anim && !rgl && !count;
-    if (views)
-        g_kernelName.store(viewsLds ? "wpt_pathtrace, views, scene in LDS"
-                : rgl ? (count ? "wpt_pathtrace, views, measured BRDFs, counting" : "wpt_pathtrace, views, measured BRDFs")
-                : anim ? (count ? "wpt_pathtrace, views, all features, moving scenes, counting" : "wpt_pathtrace, views, all features, moving scenes")
-                : basic ? (count ? "wpt_pathtrace, views, basic, counting" : "wpt_pathtrace, views, basic")
-                : count ? "wpt_pathtrace, views, all features, counting" : "wpt_pathtrace, views, all features", std::memory_order_relaxed);
-    /* adaptive sampling: the kernel of its scene kind as for one frame; measured BRDFs take the moving-scene instantiation */
-    const bool adaptiveLds = adaptive && basic && lds && !anim && !rgl;
-    if (adaptive)
-        g_kernelName.store(adaptiveLds ? "wpt_pathtrace, adaptive, scene in LDS"
-                : rgl ? "wpt_pathtrace, adaptive, measured BRDFs"
-                : anim ? "wpt_pathtrace, adaptive, all features, moving scenes"
-                : basic ? "wpt_pathtrace, adaptive, basic" : "wpt_pathtrace, adaptive, all features", std::memory_order_relaxed);
-    /* the time-of-flight sensor: the same four kinds */
-    if (tof)
-        g_kernelName.store(transientLds ? "wpt_pathtrace, time of flight, scene in LDS"
-                : rgl ? "wpt_pathtrace, time of flight, measured BRDFs"
-                : anim ? "wpt_pathtrace, time of flight, all features, moving scenes" : "wpt_pathtrace, time of flight, all features", std::memory_order_relaxed);
-    bool sliced = false; /* decided below: the twins of the two kernels with the scene in LDS that hand pixels out in slices */
-    auto launch = [&](const wptk::KernelArgs& a) {
-        if (tof) {
-            if (transientLds)
-                launchBasicLdsTof(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (rgl)
-                launchFullRglAnimTof(a, grid, stream);
-            else if (anim)
-                launchFullAnimTof(a, grid, stream);
-            else
-                launchFullTof(a, grid, stream);
-        } else if (adaptive) {
-            if (adaptiveLds)
-                launchBasicLdsAdaptive(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (rgl)
-                launchFullRglAnimAdaptive(a, grid, stream);
-            else if (anim)
-                launchFullAnimAdaptive(a, grid, stream);
-            else if (basic)
-                launchBasicAdaptive(a, grid, stream);
-            else
-                launchFullAdaptive(a, grid, stream);
-        } else if (views) {
-            if (viewsLds)
-                launchBasicLdsViews(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (rgl)
-                count ? launchFullRglAnimCountViews(a, grid, stream) : launchFullRglAnimViews(a, grid, stream);
-            else if (anim)
-                count ? launchFullAnimCountViews(a, grid, stream) : launchFullAnimViews(a, grid, stream);
-            else if (basic)
-                count ? launchBasicCountViews(a, grid, stream) : launchBasicViews(a, grid, stream);
-            else
-                count ? launchFullCountViews(a, grid, stream) : launchFullViews(a, grid, stream);
-        } else if (transient) {
-            if (transientLds)
-                launchBasicLdsTransient(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (rgl)
-                launchFullRglAnimTransient(a, grid, stream);
-            else if (anim)
-                launchFullAnimTransient(a, grid, stream);
-            else
-                launchFullTransient(a, grid, stream);
-        } else if (anim) {
-            /* its own instantiation, like the measured BRDFs */
-            if (need & FEAT_RGL) {
-                if (count)
-                    launchFullRglAnimCount(a, grid, stream);
-                else
-                    launchFullRglAnim(a, grid, stream);
-            } else if (count) {
-                launchFullAnimCount(a, grid, stream);
-            } else {
-                launchFullAnim(a, grid, stream);
-            }
-        } else if (count) {
-            if (basic)
-                launchBasicCount(a, grid, stream);
-            else if (rgl)
-                launchFullRglCount(a, grid, stream);
-            else
-                launchFullCount(a, grid, stream);
-        } else if (rgl) {
-            if (wide)
-                launchFullRglWide(a, grid, stream);
-            else
-                launchFullRgl(a, grid, stream);
-        } else {
-            if (rotated)
-                (sliced ? launchBasicLdsRotatedSliced : launchBasicLdsRotated)(a, grid, rotatedBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (basic && lds)
-                (sliced ? launchBasicLdsSliced : launchBasicLds)(a, grid, ldsBytes + ((a.materialsInLds & LDS_MATERIALS) ? size_t(scene->view.materialCount) * sizeof(wpt_material) : 0), stream);
-            else if (wide) /* also for the basic feature set: the wide walk exists in the all-features instantiations */
-                launchFullWide(a, grid, stream);
-            else if (basic)
-                launchBasic(a, grid, stream);
-            else
-                launchFull(a, grid, stream);
-        }
-    };
+    args.materialsInLds = choice.materialsInLds;
+    g_kernelName.store(kernel->name, std::memory_order_relaxed);
+    g_kernelForm.store(kernelForm(choice), std::memory_order_relaxed);
+    auto launch = [&](const wptk::KernelArgs& a, const wptk::KernelEntry* k) { k->launch(a, grid, choice.sceneLdsBytes, stream); };
     /* Two passes for the kernels that fetch the scene from HBM (variant bit 0x40: never): with 2 to 64 pixels per lane the
      * end of a launch, when lanes run out of pixels one by one, is a noticeable part of it.  The first pass renders one row
      * of strata of every pixel and times it, the second renders the rest, the 8x8 tiles that took longest first
@@ -1334,9 +1227,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
      * a wave's lanes keep in step, any order but the frame's own costs that more than the shorter end gives (Cornell
      * 938 against 954). */
     const uint64_t lanesAtOnce = uint64_t(scene->cuCount) * 4u * WG;
-    const bool sceneInLds = basic && lds && !anim && !rgl;
     /* (not for a batch of views: the carry, cost and order buffers are indexed by the pixel of one frame) */
-    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !sceneInLds && !views && !adaptive && samples_sqrt >= 8
+    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !choice.sceneInLds && !views && !adaptive && samples_sqrt >= 8
             && uint64_t(block_size) >= 2u * lanesAtOnce && uint64_t(block_size) <= 64u * lanesAtOnce;
     float4* carry = nullptr;
     uint32_t *cost = nullptr, *order = nullptr, *work = nullptr;
@@ -1351,13 +1243,13 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             first.rowStop = 1;
             first.carry = carry;
             first.cost = cost;
-            launch(first);
+            launch(first, kernel);
             wptk::launchOrderBuild(first, order, work, stream);
             wptk::KernelArgs second = args;
             second.carry = carry;
             second.order = order;
             second.orderCount = work + 3 * wptk::ORDER_BUCKETS;
-            launch(second);
+            launch(second, kernel);
             passesDone = true;
         } else {
             (void)hipGetLastError();
@@ -1377,7 +1269,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
             wptk::KernelArgs ordered = args;
             ordered.order = order;
             ordered.orderCount = work + 3 * wptk::ORDER_BUCKETS;
-            launch(ordered);
+            launch(ordered, kernel);
             passesDone = true;
         } else {
             (void)hipGetLastError();
@@ -1389,7 +1281,7 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     uint32_t* sliceWords = nullptr;
     float4* sliceCarry = nullptr;
     g_lastSliceStats.store(nullptr, std::memory_order_relaxed);
-    if (sceneInLds && pool != nullptr && !(g_variant & 0x40u) && !views && !adaptive && !transient && !tof && !count
+    if (mayBeSliced && pool != nullptr && !(g_variant & 0x40u)
             && uint64_t(block_size) > lanesAtOnce && block_size <= wptk::SLICE_SLOT_MASK) {
         uint32_t units = 1, rows = samples_sqrt;
         const uint32_t forced = g_slices & 0xffu;
@@ -1413,19 +1305,17 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
                 inSlices.slices.rows = rows;
                 inSlices.slices.units = units;
                 inSlices.slices.declineOdd = (g_slices & WPT_SLICES_DECLINE_ODD) ? 1u : 0u;
-                sliced = true;
-                launch(inSlices);
-                sliced = false;
+                launch(inSlices, slicedKernel);
                 passesDone = true;
                 g_lastSliceStats.store(stats, std::memory_order_relaxed);
-                g_kernelForm.store(ldsKernelForm(rotated, units), std::memory_order_relaxed);
+                g_kernelForm.store(ldsKernelForm(choice.rotated, units), std::memory_order_relaxed);
             } else {
                 (void)hipGetLastError();
             }
         }
     }
     if (!passesDone)
-        launch(args);
+        launch(args, kernel);
     g_lastPasses.store(passesDone && !adaptive && !sliceWords ? 2u : 1u, std::memory_order_relaxed);
     const hipError_t launched = hipGetLastError();
     for (void* p : { static_cast<void*>(pool), static_cast<void*>(carry), static_cast<void*>(cost), static_cast<void*>(order), static_cast<void*>(work),
@@ -2088,6 +1978,46 @@ wpt_status wpt_slices_plan(uint32_t block_size, uint32_t lanes_at_once, uint32_t
     r = r < 2 ? 2 : r;
     *rows = r;
     *units = (samples_sqrt + r - 1) / r;
+    return WPT_OK;
+}
+
+wpt_status wpt_kernel_choice(uint32_t need, uint32_t sensor, uint32_t count, uint32_t node_count, uint32_t tri_count, uint32_t material_count,
+        uint32_t scene_has_wide, uint32_t variant, uint32_t walk, const char** name, const char** form, uint32_t key[4],
+        uint64_t* scene_lds_bytes, uint32_t* materials_in_lds)
+{
+    if (!name || !form || !key || !scene_lds_bytes || !materials_in_lds)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sensor >= wptk::SENSOR_COUNT)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "sensor: 0 frame, 1 transient, 2 views, 3 adaptive, 4 time of flight");
+    const wptk::KernelChoice choice = wptk::selectKernel({ need, wptk::Sensor(sensor), count != 0, node_count, tri_count, material_count,
+            scene_has_wide != 0, variant, walk });
+    const wptk::KernelEntry* kernel = nullptr;
+    const wpt_status found = lookupKernel(choice.features, choice.count, choice.ldsScene, choice.wide, &kernel);
+    if (found != WPT_OK)
+        return found;
+    *name = kernel->name;
+    *form = kernelForm(choice);
+    key[0] = kernel->features;
+    key[1] = kernel->count;
+    key[2] = kernel->ldsScene;
+    key[3] = kernel->wide;
+    *scene_lds_bytes = choice.sceneLdsBytes;
+    *materials_in_lds = choice.materialsInLds;
+    return WPT_OK;
+}
+
+wpt_status wpt_kernel_table_entry(uint32_t index, uint32_t key[4], const char** name)
+{
+    if (!key || !name)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (index >= wptk::KERNEL_TABLE_ROWS)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the kernel table has " + std::to_string(wptk::KERNEL_TABLE_ROWS) + " rows");
+    const wptk::KernelEntry& k = wptk::KERNEL_TABLE[index];
+    key[0] = k.features;
+    key[1] = k.count;
+    key[2] = k.ldsScene;
+    key[3] = k.wide;
+    *name = k.name;
     return WPT_OK;
 }
 

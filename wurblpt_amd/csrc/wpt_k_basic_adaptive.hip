@@ -3,10 +3,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchBasicAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    launchMaybePooled(wpt_pathtrace<FEAT_BASIC | FEAT_ADAPTIVE, false, false, 4>, args, grid, COLD_BYTES, stream);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_BASIC | FEAT_ADAPTIVE, false, false, 4, false)
 }

@@ -3,10 +3,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchBasicCount(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((wpt_pathtrace<FEAT_BASIC, true, false, 2>), grid, dim3(WG), COLD_BYTES, stream, args);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_BASIC, true, false, 2, false)
 }

@@ -3,10 +3,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchBasicLdsViews(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream)
-{
-    launchMaybePooled(wpt_pathtrace<FEAT_BASIC | FEAT_VIEWS, false, true, 4>, args, grid, COLD_BYTES + sceneLdsBytes, stream);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_BASIC | FEAT_VIEWS, false, true, 4, false)
 }

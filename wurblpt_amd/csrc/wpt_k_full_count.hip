@@ -4,10 +4,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchFullCount(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((wpt_pathtrace<FEAT_ALL, true, false, 2>), grid, dim3(WG), COLD_BYTES, stream, args);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_ALL, true, false, 2, false)
 }

@@ -8,10 +8,5 @@
  * 1477 ms) */
 
 namespace wptk {
-
-void launchFullRgl(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    launchMaybePooled(wpt_pathtrace<FEAT_ALL | FEAT_RGL, false, false, 3>, args, grid, COLD_BYTES, stream);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_ALL | FEAT_RGL, false, false, 3, false)
 }

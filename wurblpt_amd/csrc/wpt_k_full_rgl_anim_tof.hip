@@ -5,10 +5,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchFullRglAnimTof(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    launchMaybePooled(wpt_pathtrace<FEAT_ALL | FEAT_RGL | FEAT_ANIM | FEAT_TOF, false, false, 2>, args, grid, COLD_BYTES, stream);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_ALL | FEAT_RGL | FEAT_ANIM | FEAT_TOF, false, false, 2, false)
 }

@@ -5,10 +5,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchFullRglCount(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((wpt_pathtrace<FEAT_ALL | FEAT_RGL, true, false, 2>), grid, dim3(WG), COLD_BYTES, stream, args);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_ALL | FEAT_RGL, true, false, 2, false)
 }

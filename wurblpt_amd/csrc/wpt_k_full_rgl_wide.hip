@@ -5,10 +5,5 @@
 #include "wpt_pathtrace.inc.h"
 
 namespace wptk {
-
-void launchFullRglWide(const KernelArgs& args, dim3 grid, hipStream_t stream)
-{
-    launchMaybePooled(wpt_pathtrace<FEAT_ALL | FEAT_RGL, false, false, 3, true>, args, grid, COLD_BYTES, stream);
-}
-
+WPT_PATHTRACE_LAUNCHER(FEAT_ALL | FEAT_RGL, false, false, 3, true)
 }

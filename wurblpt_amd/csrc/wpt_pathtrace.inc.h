@@ -964,58 +964,21 @@ void launchGroundTruth(const GroundTruthArgs& args, hipStream_t stream);
 /* test hook (wpt_selftest_hits): the ground truth kernel's walk and finishHit for n given rays (origin, direction, amin, amax) */
 void launchSelftestHits(const SceneView& scene, int n, const float* rays8, float* out15, hipStream_t stream);
 
-/* one launcher per instantiation, each defined in its own translation unit; sceneLdsBytes is the size of the scene
- * copy behind the cold path words in LDS (0 for the kernels that fetch the scene from HBM) */
 /* wpt_k_order.hip: from the first pass's times to the second pass's order of pixels, longest first.  `work` is
  * 3 * ORDER_BUCKETS + 1 words of device memory; work[3 * ORDER_BUCKETS] receives the number of pixels in `order`. */
 constexpr uint32_t ORDER_BUCKETS = 128;
 void launchOrderBuild(const KernelArgs& args, uint32_t* order, uint32_t* work, hipStream_t stream);
-void launchBasicLds(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchBasicLdsRotated(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream); /* sceneLdsBytes: with the two rotated copies of the corners */
-/* their twins that hand pixels out in slices (FEAT_SLICED, args.slices) */
-void launchBasicLdsSliced(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchBasicLdsRotatedSliced(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchBasic(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchBasicCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFull(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullWide(const KernelArgs& args, dim3 grid, hipStream_t stream); /* the wide walk (SceneView::wideNodes) */
-void launchFullCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRgl(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglWide(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnim(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnim(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimCount(const KernelArgs& args, dim3 grid, hipStream_t stream);
-/* the transient film (FEAT_TRANSIENT, args.bins): Cornell class with the scene in LDS, all features (at rest, moving), measured BRDFs */
-void launchBasicLdsTransient(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchFullTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimTransient(const KernelArgs& args, dim3 grid, hipStream_t stream);
-/* the time-of-flight sensor (FEAT_SPOT | FEAT_TOF, args.bins): the Cornell class with the scene in LDS (two-sided materials
- * included: a ToF light has a back side), all features (at rest, moving), measured BRDFs */
-void launchBasicLdsTof(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchFullTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimTof(const KernelArgs& args, dim3 grid, hipStream_t stream);
-/* a batch of views (FEAT_VIEWS, args.views): every scene kind of the single kernel, product and counting builds; measured BRDFs
- * take the moving-scene instantiation whether the scene moves or not */
-void launchBasicLdsViews(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchBasicViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchBasicCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimCountViews(const KernelArgs& args, dim3 grid, hipStream_t stream);
-/* adaptive sampling (FEAT_ADAPTIVE, args.adaptive): every scene kind of the single kernel, one pass, no counting builds;
- * measured BRDFs take the moving-scene instantiation whether the scene moves or not */
-void launchBasicLdsAdaptive(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
-void launchBasicAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullAnimAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
-void launchFullRglAnimAdaptive(const KernelArgs& args, dim3 grid, hipStream_t stream);
+/* One launcher per instantiation of wpt_pathtrace, each defined in its own translation unit (wpt_k_basic*.hip, wpt_k_full*.hip)
+ * by one line of WPT_PATHTRACE_LAUNCHER; wpt_kernel_table.h lists them all.  sceneLdsBytes is the size of the scene copy behind
+ * the cold path words in LDS, 0 for the kernels that fetch the scene from HBM.  OCC is the unit's own business: a launcher is
+ * named by what the host chooses between. */
+template<uint32_t F, bool COUNT, bool LDSSCENE, bool WIDE>
+void launchPathtrace(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
+#define WPT_PATHTRACE_LAUNCHER(F, COUNT, LDSSCENE, OCC, WIDE)                                                                  \
+    template<> void launchPathtrace<(F), COUNT, LDSSCENE, WIDE>(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream) \
+    {                                                                                                                          \
+        launchMaybePooled(wpt_pathtrace<(F), COUNT, LDSSCENE, OCC, WIDE>, args, grid, COLD_BYTES + sceneLdsBytes, stream);     \
+    }
 /* wpt_k_adaptive_cost.hip: args.cost[p] = n_p^2 for the block's pixels, the order's measure of an adaptive launch */
 void launchAdaptiveCost(const KernelArgs& args, hipStream_t stream);
 

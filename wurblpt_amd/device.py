@@ -25,7 +25,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_last_error"]
 
 
@@ -241,6 +241,31 @@ def slices_plan(block_size, lanes_at_once, samples_sqrt):
     units, rows = C.c_uint32(), C.c_uint32()
     _check(L.wpt_slices_plan(block_size, lanes_at_once, samples_sqrt, C.byref(units), C.byref(rows)))
     return int(units.value), int(rows.value)
+
+
+SENSOR_FRAME, SENSOR_TRANSIENT, SENSOR_VIEWS, SENSOR_ADAPTIVE, SENSOR_TOF = range(5)  # wpt_kernel_choice
+
+
+def kernel_choice(need, sensor, count, node_count, tri_count, material_count, scene_has_wide=False, variant=0, walk=0):
+    """wpt_kernel_choice: (name, form, (F, count, ldsScene, wide), sceneLdsBytes, materialsInLds) of the kernel the library would
+    launch; needs no device"""
+    L = lib()
+    L.wpt_kernel_choice.argtypes = [C.c_uint32] * 9 + [C.POINTER(C.c_char_p)] * 2 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    name, form, key, lds_bytes, materials = C.c_char_p(), C.c_char_p(), (C.c_uint32 * 4)(), C.c_uint64(), C.c_uint32()
+    _check(L.wpt_kernel_choice(need, sensor, int(count), node_count, tri_count, material_count, int(scene_has_wide), variant, walk,
+                               C.byref(name), C.byref(form), key, C.byref(lds_bytes), C.byref(materials)))
+    return name.value.decode(), form.value.decode(), (key[0], bool(key[1]), bool(key[2]), bool(key[3])), int(lds_bytes.value), int(materials.value)
+
+
+def kernel_table():
+    """wpt_kernel_table_entry: [((F, count, ldsScene, wide), name)] of every kernel the library has"""
+    L = lib()
+    L.wpt_kernel_table_entry.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
+    rows = []
+    key, name = (C.c_uint32 * 4)(), C.c_char_p()
+    while L.wpt_kernel_table_entry(len(rows), key, C.byref(name)) == _abi.WPT_OK:
+        rows.append(((key[0], bool(key[1]), bool(key[2]), bool(key[3])), name.value.decode()))
+    return rows
 
 
 def last_slice_stats():
