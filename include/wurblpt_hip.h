@@ -474,6 +474,90 @@ wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera,
         uint32_t width, uint32_t height, const uint16_t* samples_sqrt_host /* [height][width] */,
         uint32_t block_start, uint32_t block_size, float* block_rgb, float* block_moments /* may be NULL */);
 
+/* ---- a frame in resumable stages (progressive sessions) ----
+ * A session renders the block's pixels of one frame in stages: every stage renders further rows of strata of every pixel, in
+ * one launch of the kernel that a plain wpt_render_block_device of the frame would take (never the wavefront form, the twin
+ * that hands pixels out in slices, or the two passes, whatever wpt_set_wavefront and wpt_set_slices say).  A pixel's samples
+ * stay one sequence from one generator: between stages a pixel carries on 32 bytes, its generator and its sums with the next
+ * stratum, so the finished frame is bit-identical to the one-shot launch however the rows are cut into stages, and a saved
+ * and restored session goes on to the same bits.  The first stage hands the pixels out in the frame's order; later stages in
+ * the frame's order again (scene in LDS) or the 8x8 tiles that took the stage before longest first (scene in HBM).
+ * A preview after r of samples_sqrt rows is (1.0f / (float)(r * samples_sqrt)) * sum per channel: the mean over the strata
+ * rendered so far, which are the lower r / samples_sqrt of every pixel's strata -- a picture to look at, not an estimate of
+ * the frame.  The preview of a finished session is its frame bit for bit, and that of a session without a stage is 0.
+ * Moving scenes, exposure intervals, measured BRDFs, lens cameras, scenes in LDS and in HBM are all covered.  Not covered,
+ * and refused with WPT_ERR_UNSUPPORTED (wpt_progress_covers has the messages): counting launches, bands, the transient film,
+ * batches of views, adaptive maps and the time-of-flight sensor.
+ * A session holds 40 bytes of device memory per pixel (carry 32, time of the last stage 4, order 4) from wpt_progress_begin to
+ * wpt_progress_end, allocated with hipMalloc.  All calls on one session are ordered on the streams they are given: use one
+ * stream for a session, or synchronise between the streams.  Sessions of one scene on different streams may run side by side.
+ * A session reads the scene's device memory in every stage: the wpt_scene must outlive it (wpt_progress_end before
+ * wpt_scene_free), and its calls are made with the scene's device current.
+ *
+ * A saved state is a header of WPT_PROGRESS_HEADER_BYTES bytes, little-endian, then the carry of the block's pixels:
+ *   offset   0  uint32  magic, WPT_PROGRESS_MAGIC ("WPTP")
+ *            4  uint32  format version, WPT_PROGRESS_STATE_VERSION
+ *            8  uint32  width            12  uint32  height          16  uint32  samples_sqrt
+ *           20  uint32  block_start      24  uint32  block_size      28  uint32  rows_done
+ *           32  uint64  tag: the caller's fingerprint of the scene; the library stores and compares it, nothing more
+ *           40  wpt_camera (140 bytes)  180  wpt_params (40 bytes)  220  uint32  reserved, 0
+ *          224  block_size records of 32 bytes, pixel block_start first: uint32[4] the pixel's generator, then float[3] the
+ *               pixel's sums per channel and uint32 its next stratum i | j << 16.  With rows_done == 0 a record is zeros; with
+ *               rows_done == samples_sqrt its three floats are the finished pixel's values (the sums times 1 / samples, as the
+ *               kernel wrote them to the frame), so that a finished state still yields its frame: the launch that renders a
+ *               pixel's last row writes the frame and stores no carry, so the session copies the block's pixels back from the
+ *               frame, and the generator's four words of such a record are stale (those of the stage before, or zeros).
+ * wpt_progress_state_info checks a state (sizes against `bytes` before anything is read, then magic, version, ranges, block
+ * within width * height, rows_done <= samples_sqrt, the reserved word, the exact length) and needs no device; wurblpt_amd/csrc/wpt_progress_state.h
+ * is that parser on its own. */
+#define WPT_PROGRESS_MAGIC 0x50545057u
+#define WPT_PROGRESS_STATE_VERSION 1u
+#define WPT_PROGRESS_HEADER_BYTES 224u
+typedef struct wpt_progress wpt_progress; /* opaque session */
+typedef struct wpt_progress_info {
+    uint32_t version, width, height, samples_sqrt, block_start, block_size, rows_done, reserved;
+    uint64_t tag;
+    uint64_t state_bytes; /* header and carry */
+} wpt_progress_info;
+
+/* WPT_OK if sessions cover such a launch, else WPT_ERR_UNSUPPORTED with the reason.  sensor: as for wpt_kernel_choice (0 one
+ * frame, 1 transient film, 2 batch of views, 3 adaptive map, 4 time of flight); counting: the launch counts its work; bands: it
+ * renders interleaved bands.  A pure function that needs no device; wpt_progress_begin is sensor 0 without counters or bands. */
+wpt_status wpt_progress_covers(uint32_t sensor, uint32_t counting, uint32_t bands);
+/* Starts a session for pixels [block_start, block_start + block_size) of a width x height frame; camera and params are copied.
+ * WPT_ERR_NO_DEVICE where there is no device, before anything else is looked at. */
+wpt_status wpt_progress_begin(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, uint64_t tag, wpt_progress** out_progress);
+/* Renders up to `rows` further rows of strata of every pixel of the block (clamped to what is left), asynchronously on
+ * `hip_stream`.  The stage that reaches samples_sqrt writes the block's pixels of `frame_device`, the FULL frame as for
+ * wpt_render_block_device; earlier stages do not touch it, and it may be NULL for them.  Refused with
+ * WPT_ERR_INVALID_ARGUMENT before anything is launched: rows == 0, a finished session, a NULL frame on the finishing stage.
+ * wpt_kernel_name reports the kernel's usual name and wpt_last_render_passes 1. */
+wpt_status wpt_progress_advance_device(wpt_progress* progress, uint32_t rows, float* frame_device, void* hip_stream);
+/* Synchronous form: the finishing stage writes block_size*3 floats to host memory `block_rgb` as wpt_render_block does; earlier
+ * stages do not touch it, and it may be NULL for them. */
+wpt_status wpt_progress_advance(wpt_progress* progress, uint32_t rows, float* block_rgb);
+uint32_t wpt_progress_rows_done(const wpt_progress* progress);  /* 0 for NULL */
+uint32_t wpt_progress_rows_total(const wpt_progress* progress); /* samples_sqrt; 0 for NULL */
+/* Writes the preview of the block's pixels into `frame_device`, the FULL frame; pixels outside the block are not written.
+ * Asynchronous on `hip_stream`. */
+wpt_status wpt_progress_preview_device(wpt_progress* progress, float* frame_device, void* hip_stream);
+/* Synchronous form: block_size*3 floats for the block's pixels to host memory `block_rgb`, as wpt_render_block lays them out. */
+wpt_status wpt_progress_preview(wpt_progress* progress, float* block_rgb);
+/* Frees the session's device memory after its last stream has finished.  NULL is allowed. */
+void wpt_progress_end(wpt_progress* progress);
+/* The state: its size, the state itself into `bytes` == that size of host memory (waits for the stream of the session's last
+ * call), and a new session from it.  wpt_progress_restore compares the state's tag, camera and params with its arguments, the
+ * structs bytewise, and names the first that differs in wpt_last_error (WPT_ERR_INVALID_ARGUMENT); a state that
+ * wpt_progress_state_info refuses is refused with that message, and so is one with a record whose next stratum is not
+ * rows_done << 16 (a damaged body), all before anything is allocated.  The frame's size, samples_sqrt and the block are the
+ * state's own: a caller that expects particular ones compares them with wpt_progress_state_info's. */
+wpt_status wpt_progress_state_bytes(const wpt_progress* progress, uint64_t* bytes);
+wpt_status wpt_progress_save(wpt_progress* progress, void* buffer_host, uint64_t bytes);
+wpt_status wpt_progress_restore(wpt_scene* scene, const void* buffer_host, uint64_t bytes, const wpt_camera* camera,
+        const wpt_params* params, uint64_t tag, wpt_progress** out_progress);
+wpt_status wpt_progress_state_info(const void* buffer_host, uint64_t bytes, wpt_progress_info* info);
+
 /* Waits for the device; WPT_ERR_HIP if a launch since the last call failed (the kernels have no waits that could run
  * out: every loop of theirs ends with its work; lanes that hand a pixel on between its slices never wait for one another). */
 wpt_status wpt_scene_check(wpt_scene* scene);

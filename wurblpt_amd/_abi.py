@@ -123,10 +123,21 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ProgressInfo(C.Structure):
+    """wpt_progress_info: the header of a saved progressive session"""
+    _fields_ = [(n, C.c_uint32) for n in ("version", "width", "height", "samples_sqrt", "block_start", "block_size", "rows_done", "reserved")] \
+        + [("tag", C.c_uint64), ("state_bytes", C.c_uint64)]
+
+
+# the saved state of a progressive session (include/wurblpt_hip.h has the layout)
+PROGRESS_MAGIC, PROGRESS_STATE_VERSION, PROGRESS_HEADER_BYTES, PROGRESS_CARRY_BYTES = 0x50545057, 1, 224, 32
+
+
 STRUCT_SIZES = {
     "wpt_bvh_node": (BvhNode, 32), "wpt_tri_geom": (TriGeom, 48), "wpt_tri_attr": (TriAttr, 96),
     "wpt_instance": (Instance, 48), "wpt_sphere": (Sphere, 48), "wpt_hotspot": (Hotspot, 116), "wpt_material": (Material, 128),
     "wpt_texture": (Texture, 88), "wpt_rgl_warp": (RglWarp, 76), "wpt_rgl_brdf": (RglBrdf, 388), "wpt_camera": (Camera, 140), "wpt_params": (Params, 40),
     "wpt_keyframe": (Keyframe, 44), "wpt_animation": (Animation, 8),
     "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
+    "wpt_progress_info": (ProgressInfo, 48),
 }

@@ -18,6 +18,8 @@
 #include "wpt_kernel_table.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
+#include "wpt_progress.h"
+#include "wpt_progress_state.h"
 
 using namespace wptd;
 using namespace wptk;
@@ -1069,6 +1071,75 @@ wpt_status wpt_scene_get_envmap_tables(const wpt_scene* scene, float* M, int32_t
     return WPT_OK;
 }
 
+/* What every launch of the single kernel sets up the same way, a plain block, bands, a batch of views or a stage of a session
+ * (wpt_progress_begin): the frame's constants, the 8x8 tiles, the features the cameras add to the scene's, the scheduler's
+ * settings.  `camera` is the first of cameraCount cameras (batch: they are a batch of views); frame, counters, the sensor's
+ * view and what a stage adds are the caller's. */
+static wpt_status launchSetUp(const wpt_scene* scene, const wpt_camera* camera, uint32_t cameraCount, bool batch, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        uint32_t band_pixels, uint32_t band_first, uint32_t band_stride, bool count, wptk::KernelArgs& args, uint32_t& need)
+{
+    args.bandPixels = band_pixels;
+    args.bandFirst = band_first;
+    args.bandStride = band_stride;
+    args.sv = scene->view;
+    args.cam = *camera;
+    args.par = *params;
+    args.width = width;
+    args.height = height;
+    args.samplesSqrt = samples_sqrt;
+    args.invWidth = 1.0f / float(width);
+    args.invHeight = 1.0f / float(height);
+    args.invSamplesSqrt = 1.0f / float(samples_sqrt);
+    args.invSamples = 1.0f / float(samples_sqrt * samples_sqrt);
+    args.blockStart = block_start;
+    args.blockSize = block_size;
+    args.fuse = (g_variant & 0x20u) ? 0u : 1u; /* variant bit 0x20: separate SHADE / NEE-END / NEW rounds (the older scheduler) */
+
+    /* a wave covers an 8x8 pixel tile when the block consists of whole groups of 8 rows */
+    args.tiled = (width % 8 == 0 && block_start % width == 0 && block_size % (8 * width) == 0
+            && (band_stride == 0 || band_pixels % (8 * width) == 0)) ? 1u : 0u;
+    if (batch) /* 8x8 tiles within each view's frame */
+        args.tiled = (width % 8 == 0 && height % 8 == 0) ? 1u : 0u;
+    /* a batch takes the union of the scene's features and every camera's */
+    need = scene->features;
+    for (uint32_t v = 0; v < cameraCount; v++) {
+        const wpt_camera* c = camera + v;
+        need |= (c->lens_radius > 0.0f || c->distortion_type != WPT_DISTORTION_NONE || c->surround_mode != WPT_SURROUND_OFF
+                || c->stereoscopic_distance > 0.0f) ? FEAT_LENS : 0u;
+        if (c->surround_mode > WPT_SURROUND_360)
+            return fail(WPT_ERR_UNSUPPORTED, "camera surround mode is not known to the kernel");
+        if (c->distortion_type > WPT_DISTORTION_OPENCV)
+            return fail(WPT_ERR_UNSUPPORTED, "lens distortion model is not known to the kernel");
+        if (c->animation >= int32_t(scene->animationCount))
+            return fail(WPT_ERR_INVALID_ARGUMENT, batch ? "camera " + std::to_string(v) + " refers to an animation outside the scene's array"
+                    : std::string("camera refers to an animation outside the scene's array"));
+        if (batch && c->animation >= 0) /* an animated camera selects the moving-scene kernels */
+            need |= FEAT_ANIM;
+    }
+    /* an exposure interval changes every path (each camera ray draws its time), moving instances need the time too */
+    if (params->t0 != params->t1)
+        need |= FEAT_ANIM;
+    /* The walk of a light ray towards the environment ends at its first accepted hit (wpt_pathtrace.inc.h: the answer it is
+     * traced for is known there).  Counting launches walk on as the reference does, so that their counters are the
+     * reference's; measurements (wpt_set_walk): WPT_WALK_COUNT_PRODUCT makes them count what the product kernel walks,
+     * WPT_WALK_FULL_SHADOW switches the short cut off everywhere. */
+    args.shadowWalksEnd = (g_walk & WPT_WALK_FULL_SHADOW) ? 0u : (count ? ((g_walk & WPT_WALK_COUNT_PRODUCT) ? 1u : 0u) : 1u);
+    /* scheduler defaults from sweeps on the Cornell box (scene in LDS, short walks) and on the
+     * Sponza-class scene (deep tree in HBM: traversal dominates, so long blocks may run with fewer
+     * lanes and leaf tests earlier) */
+    const bool smallScene = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48 <= LDS_SCENE_MAX_BYTES;
+    /* clamped: with more than 8 eighths the traversal block would leave before doing anything */
+    args.leaveEighths = g_leaveEighths ? (g_leaveEighths > 8u ? 8u : g_leaveEighths) : (smallScene ? 1u : 3u);
+    args.heavyMin = g_heavyMin ? g_heavyMin : (smallScene ? 16u : 8u);
+    args.leafBias = g_leafBias ? g_leafBias : (smallScene ? 16u : 32u);
+    /* variant bits 2-3: 0 = default, 1 = no kind of material ever stands back, 2 / 3 = fewer than 3 / 12 lanes */
+    static const uint32_t waitBelowChoices[4] = { 6u, 0u, 3u, 12u };
+    args.waitBelow = waitBelowChoices[(g_variant >> 2) & 0x3u];
+    args.cuCount = uint32_t(scene->cuCount);
+    return WPT_OK;
+}
+
 /* one launch: a block of consecutive pixels (band_stride == 0) or interleaved bands of band_pixels pixels */
 static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
@@ -1089,21 +1160,12 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     if (block_size == 0)
         return WPT_OK;
     KernelArgs args;
-    args.bandPixels = band_pixels;
-    args.bandFirst = band_first;
-    args.bandStride = band_stride;
-    args.sv = scene->view;
-    args.cam = *camera;
-    args.par = *params;
-    args.width = width;
-    args.height = height;
-    args.samplesSqrt = samples_sqrt;
-    args.invWidth = 1.0f / float(width);
-    args.invHeight = 1.0f / float(height);
-    args.invSamplesSqrt = 1.0f / float(samples_sqrt);
-    args.invSamples = 1.0f / float(samples_sqrt * samples_sqrt);
-    args.blockStart = block_start;
-    args.blockSize = block_size;
+    uint32_t need = 0;
+    const bool count = counters_device != nullptr;
+    const wpt_status setUp = launchSetUp(scene, camera, cameraCount, views != nullptr, params, width, height, samples_sqrt, block_start, block_size,
+            band_pixels, band_first, band_stride, count, args, need);
+    if (setUp != WPT_OK)
+        return setUp;
     args.frame = frame_device;
     args.counters = counters_device;
     args.schedStats = g_schedStats;
@@ -1113,51 +1175,8 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
         args.adaptive = *adaptive;
     else
         args.bins = transient ? *transient : wptk::BinsView{};
-    args.fuse = (g_variant & 0x20u) ? 0u : 1u; /* variant bit 0x20: separate SHADE / NEE-END / NEW rounds (the older scheduler) */
-
-    /* a wave covers an 8x8 pixel tile when the block consists of whole groups of 8 rows */
-    args.tiled = (width % 8 == 0 && block_start % width == 0 && block_size % (8 * width) == 0
-            && (band_stride == 0 || band_pixels % (8 * width) == 0)) ? 1u : 0u;
-    if (views) /* 8x8 tiles within each view's frame */
-        args.tiled = (width % 8 == 0 && height % 8 == 0) ? 1u : 0u;
-    /* a batch takes the union of the scene's features and every camera's */
-    uint32_t need = scene->features;
-    for (uint32_t v = 0; v < cameraCount; v++) {
-        const wpt_camera* c = camera + v;
-        need |= (c->lens_radius > 0.0f || c->distortion_type != WPT_DISTORTION_NONE || c->surround_mode != WPT_SURROUND_OFF
-                || c->stereoscopic_distance > 0.0f) ? FEAT_LENS : 0u;
-        if (c->surround_mode > WPT_SURROUND_360)
-            return fail(WPT_ERR_UNSUPPORTED, "camera surround mode is not known to the kernel");
-        if (c->distortion_type > WPT_DISTORTION_OPENCV)
-            return fail(WPT_ERR_UNSUPPORTED, "lens distortion model is not known to the kernel");
-        if (c->animation >= int32_t(scene->animationCount))
-            return fail(WPT_ERR_INVALID_ARGUMENT, views ? "camera " + std::to_string(v) + " refers to an animation outside the scene's array"
-                    : std::string("camera refers to an animation outside the scene's array"));
-        if (views && c->animation >= 0) /* an animated camera selects the moving-scene kernels */
-            need |= FEAT_ANIM;
-    }
-    /* an exposure interval changes every path (each camera ray draws its time), moving instances need the time too */
-    if (params->t0 != params->t1)
-        need |= FEAT_ANIM;
     dim3 grid((block_size + WG - 1) / WG);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const bool count = counters_device != nullptr;
-    /* The walk of a light ray towards the environment ends at its first accepted hit (wpt_pathtrace.inc.h: the answer it is
-     * traced for is known there).  Counting launches walk on as the reference does, so that their counters are the
-     * reference's; measurements (wpt_set_walk): WPT_WALK_COUNT_PRODUCT makes them count what the product kernel walks,
-     * WPT_WALK_FULL_SHADOW switches the short cut off everywhere. */
-    args.shadowWalksEnd = (g_walk & WPT_WALK_FULL_SHADOW) ? 0u : (count ? ((g_walk & WPT_WALK_COUNT_PRODUCT) ? 1u : 0u) : 1u);
-    /* scheduler defaults from sweeps on the Cornell box (scene in LDS, short walks) and on the
-     * Sponza-class scene (deep tree in HBM: traversal dominates, so long blocks may run with fewer
-     * lanes and leaf tests earlier) */
-    const bool smallScene = size_t(scene->nodeCount) * 32 + size_t(scene->triCount) * 48 <= LDS_SCENE_MAX_BYTES;
-    /* clamped: with more than 8 eighths the traversal block would leave before doing anything */
-    args.leaveEighths = g_leaveEighths ? (g_leaveEighths > 8u ? 8u : g_leaveEighths) : (smallScene ? 1u : 3u);
-    args.heavyMin = g_heavyMin ? g_heavyMin : (smallScene ? 16u : 8u);
-    args.leafBias = g_leafBias ? g_leafBias : (smallScene ? 16u : 32u);
-    /* variant bits 2-3: 0 = default, 1 = no kind of material ever stands back, 2 / 3 = fewer than 3 / 12 lanes */
-    static const uint32_t waitBelowChoices[4] = { 6u, 0u, 3u, 12u };
-    args.waitBelow = waitBelowChoices[(g_variant >> 2) & 0x3u];
     /* kernel choice (wpt_kernel_table.h) */
     const wptk::Sensor sensor = tof ? wptk::SENSOR_TOF : adaptive ? wptk::SENSOR_ADAPTIVE : views ? wptk::SENSOR_VIEWS
             : transient ? wptk::SENSOR_TRANSIENT : wptk::SENSOR_FRAME;
@@ -1172,7 +1191,6 @@ static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const
     if (found != WPT_OK)
         return found;
     const bool rgl = (need & FEAT_RGL) != 0;
-    args.cuCount = uint32_t(scene->cuCount);
     args.rowStop = samples_sqrt;
     args.carry = nullptr;
     args.cost = nullptr;
@@ -1399,6 +1417,338 @@ wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera, const wp
     }
     (void)hipFree(dBlock);
     return st;
+}
+
+} /* extern "C" */
+
+/* ---- a frame in resumable stages (wurblpt_hip.h: progressive sessions) ---- */
+
+struct wpt_progress {
+    wpt_scene* scene;
+    wptk::KernelArgs args; /* of the one-shot launch of the block; a stage sets frame, rowStop, order, orderCount and pool */
+    wptk::KernelChoice choice;
+    const wptk::KernelEntry* kernel;
+    uint32_t rowsDone;
+    uint64_t tag;
+    /* device memory for the session's lifetime: carry and cost per pixel of the frame (the kernels index them by the frame's
+     * pixel), order per pixel of the block, the order kernels' work words */
+    float4* carry;
+    uint32_t *cost, *order, *work;
+    bool frameOrderBuilt; /* scene in LDS: `order` holds the frame's own order, which every later stage takes */
+    hipStream_t lastStream;
+};
+
+namespace {
+
+void progressFree(wpt_progress* p)
+{
+    for (void* m : { static_cast<void*>(p->carry), static_cast<void*>(p->cost), static_cast<void*>(p->order), static_cast<void*>(p->work) })
+        if (m)
+            (void)hipFree(m);
+    delete p;
+}
+
+wpt_progress_info progressInfo(const wpt_progress* p)
+{
+    wpt_progress_info i;
+    memset(&i, 0, sizeof(i));
+    i.version = WPT_PROGRESS_STATE_VERSION;
+    i.width = p->args.width;
+    i.height = p->args.height;
+    i.samples_sqrt = p->args.samplesSqrt;
+    i.block_start = p->args.blockStart;
+    i.block_size = p->args.blockSize;
+    i.rows_done = p->rowsDone;
+    i.tag = p->tag;
+    i.state_bytes = uint64_t(wptp::STATE_HEADER_BYTES) + uint64_t(i.block_size) * wptp::STATE_CARRY_BYTES_PER_PIXEL;
+    return i;
+}
+
+}
+
+extern "C" {
+
+wpt_status wpt_progress_covers(uint32_t sensor, uint32_t counting, uint32_t bands)
+{
+    static const char* const sensors[] = { nullptr, "the transient film", "a batch of views", "an adaptive map", "the time-of-flight sensor" };
+    if (sensor >= wptk::SENSOR_COUNT)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "sensor must lie in 0 .. 4");
+    if (sensors[sensor])
+        return fail(WPT_ERR_UNSUPPORTED, std::string("sessions render one frame, not ") + sensors[sensor]
+                + ": what a pixel carries between stages is its generator and three sums");
+    if (counting)
+        return fail(WPT_ERR_UNSUPPORTED, "sessions do not cover counting launches: the counters of a stage would count the launch's lanes, not the rows rendered");
+    if (bands)
+        return fail(WPT_ERR_UNSUPPORTED, "sessions do not cover bands: a session renders one block of consecutive pixels");
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_begin(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, uint64_t tag, wpt_progress** out_progress)
+{
+    if (out_progress)
+        *out_progress = nullptr;
+    if (wpt_device_count() <= 0)
+        return fail(WPT_ERR_NO_DEVICE, "no HIP device is available; the path tracer has no CPU fallback");
+    if (!scene || !camera || !params || !out_progress)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
+    if (block_size == 0 || uint64_t(block_start) + block_size > uint64_t(width) * height)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block is empty or lies outside the frame");
+    /* the arguments and the kernel of the plain frame launch without counters, set up by what renderLaunch sets them up with */
+    wpt_progress* p = new wpt_progress;
+    p->scene = scene;
+    p->rowsDone = 0;
+    p->tag = tag;
+    p->carry = nullptr;
+    p->cost = p->order = p->work = nullptr;
+    p->frameOrderBuilt = false;
+    p->lastStream = nullptr;
+    KernelArgs& args = p->args;
+    memset(&args, 0, sizeof(args));
+    uint32_t need = 0;
+    const wpt_status setUp = launchSetUp(scene, camera, 1, false, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0, false, args, need);
+    if (setUp != WPT_OK) {
+        progressFree(p);
+        return setUp;
+    }
+    args.bins = wptk::BinsView{};
+    p->choice = wptk::selectKernel({ need, wptk::SENSOR_FRAME, false, scene->nodeCount, scene->triCount, uint32_t(scene->view.materialCount),
+            scene->view.wideNodes != nullptr, g_variant, g_walk });
+    const wpt_status found = lookupKernel(p->choice.features, p->choice.count, p->choice.ldsScene, p->choice.wide, &p->kernel);
+    if (found != WPT_OK) {
+        progressFree(p);
+        return found;
+    }
+    args.materialsInLds = p->choice.materialsInLds;
+    /* hipMalloc, not stream-ordered: the memory outlives the calls.  Carry and cost start as zeros: a state saved before the
+     * first stage is defined, and so is the order that a restored session builds from times it never measured. */
+    const size_t pixels = size_t(width) * height;
+    const size_t workBytes = (3 * wptk::ORDER_BUCKETS + 1) * sizeof(uint32_t);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->carry), pixels * 2 * sizeof(float4));
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&p->cost), pixels * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&p->order), size_t(block_size) * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&p->work), workBytes);
+    if (e == hipSuccess)
+        e = hipMemset(p->carry + 2 * size_t(block_start), 0, size_t(block_size) * 2 * sizeof(float4));
+    if (e == hipSuccess)
+        e = hipMemset(p->cost, 0, pixels * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        progressFree(p);
+        return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("session memory (40 bytes per pixel): ") + hipGetErrorString(e));
+    }
+    args.carry = p->carry;
+    args.cost = p->cost;
+    *out_progress = p;
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_advance_device(wpt_progress* p, uint32_t rows, float* frame_device, void* hip_stream)
+{
+    if (!p)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "progress is NULL");
+    const uint32_t total = p->args.samplesSqrt;
+    if (rows == 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "a stage renders at least one row of strata: rows is 0");
+    if (p->rowsDone >= total)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the session is finished: all " + std::to_string(total) + " rows of strata are rendered");
+    const uint32_t rowStop = rows < total - p->rowsDone ? p->rowsDone + rows : total;
+    if (rowStop == total && !frame_device)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the stage that finishes the frame needs frame_device: it is NULL");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    wptk::KernelArgs stage = p->args;
+    stage.frame = frame_device;
+    stage.rowStop = rowStop;
+    stage.schedStats = nullptr;
+    if (p->rowsDone > 0) {
+        /* a stage that resumes takes its pixels from `order` and loads what they carry: the frame's own order for the scene
+         * in LDS (any other costs those kernels more than it gains), the tiles that took the stage before longest first for
+         * the scene in HBM, as the second of the one-shot launch's two passes does */
+        if (p->choice.sceneInLds) {
+            if (!p->frameOrderBuilt)
+                wptk::launchProgressFrameOrder(p->args, p->order, p->work + 3 * wptk::ORDER_BUCKETS, stream);
+            p->frameOrderBuilt = true;
+        } else {
+            wptk::launchOrderBuild(p->args, p->order, p->work, stream);
+        }
+        stage.order = p->order;
+        stage.orderCount = p->work + 3 * wptk::ORDER_BUCKETS;
+    }
+    /* the pixel pool, as renderLaunch uses it */
+    dim3 grid((p->args.blockSize + WG - 1) / WG);
+    uint32_t* pool = nullptr;
+    const bool pooled = !(g_variant & 0x10u) && p->args.blockSize < 0x80000000u && grid.x > p->args.cuCount;
+    if (pooled && hipMallocAsync(reinterpret_cast<void**>(&pool), sizeof(uint32_t), stream) != hipSuccess) {
+        (void)hipGetLastError();
+        pool = nullptr;
+    }
+    stage.pool = pool;
+    g_kernelName.store(p->kernel->name, std::memory_order_relaxed);
+    g_kernelForm.store(kernelForm(p->choice), std::memory_order_relaxed);
+    g_lastSliceStats.store(nullptr, std::memory_order_relaxed);
+    p->kernel->launch(stage, grid, p->choice.sceneLdsBytes, stream);
+    g_lastPasses.store(1u, std::memory_order_relaxed);
+    const hipError_t launched = hipGetLastError();
+    if (pool)
+        (void)hipFreeAsync(pool, stream);
+    HIP_TRY(launched);
+    /* The launch that renders the last row writes the frame and stores no carry.  A finished session keeps the block's pixels
+     * of its frame in the carry's place instead, so that its preview and its saved state still yield the frame. */
+    if (rowStop == total) {
+        wptk::launchProgressCapture(frame_device, p->carry, p->args.blockStart, p->args.blockSize, total << 16, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    p->rowsDone = rowStop;
+    p->lastStream = stream;
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_advance(wpt_progress* p, uint32_t rows, float* block_rgb)
+{
+    if (!p)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "progress is NULL");
+    const uint32_t total = p->args.samplesSqrt;
+    const bool finishes = rows > 0 && p->rowsDone < total && rows >= total - p->rowsDone;
+    if (finishes && !block_rgb)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the stage that finishes the frame needs block_rgb: it is NULL");
+    float* dBlock = nullptr;
+    if (finishes)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), size_t(p->args.blockSize) * 3 * sizeof(float)));
+    wpt_status st = wpt_progress_advance_device(p, rows, finishes ? dBlock - size_t(p->args.blockStart) * 3 : nullptr, nullptr);
+    if (st == WPT_OK)
+        st = wpt_scene_check(p->scene);
+    if (st == WPT_OK && finishes) {
+        hipError_t e = hipMemcpy(block_rgb, dBlock, size_t(p->args.blockSize) * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    if (dBlock)
+        (void)hipFree(dBlock);
+    return st;
+}
+
+uint32_t wpt_progress_rows_done(const wpt_progress* p)
+{
+    return p ? p->rowsDone : 0u;
+}
+
+uint32_t wpt_progress_rows_total(const wpt_progress* p)
+{
+    return p ? p->args.samplesSqrt : 0u;
+}
+
+wpt_status wpt_progress_preview_device(wpt_progress* p, float* frame_device, void* hip_stream)
+{
+    if (!p || !frame_device)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    /* (a finished session's carry holds the pixels' values themselves, and a session without a stage zeros) */
+    const uint32_t total = p->args.samplesSqrt;
+    const float inv = p->rowsDone == total ? 1.0f : (p->rowsDone ? 1.0f / float(p->rowsDone * total) : 0.0f);
+    wptk::launchProgressResolve(p->carry, frame_device, p->args.blockStart, p->args.blockSize, inv, stream);
+    HIP_TRY(hipGetLastError());
+    p->lastStream = stream;
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_preview(wpt_progress* p, float* block_rgb)
+{
+    if (!p || !block_rgb)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    float* dBlock = nullptr;
+    HIP_TRY(hipStreamSynchronize(p->lastStream));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), size_t(p->args.blockSize) * 3 * sizeof(float)));
+    wpt_status st = wpt_progress_preview_device(p, dBlock - size_t(p->args.blockStart) * 3, nullptr);
+    if (st == WPT_OK) {
+        hipError_t e = hipMemcpy(block_rgb, dBlock, size_t(p->args.blockSize) * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(dBlock);
+    return st;
+}
+
+void wpt_progress_end(wpt_progress* p)
+{
+    if (!p)
+        return;
+    (void)hipStreamSynchronize(p->lastStream);
+    progressFree(p);
+}
+
+wpt_status wpt_progress_state_bytes(const wpt_progress* p, uint64_t* bytes)
+{
+    if (!p || !bytes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *bytes = progressInfo(p).state_bytes;
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_save(wpt_progress* p, void* buffer_host, uint64_t bytes)
+{
+    if (!p || !buffer_host)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const wpt_progress_info info = progressInfo(p);
+    if (bytes != info.state_bytes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the buffer must hold wpt_progress_state_bytes = " + std::to_string(info.state_bytes) + " bytes, not "
+                + std::to_string(bytes));
+    HIP_TRY(hipStreamSynchronize(p->lastStream));
+    wptp::writeStateHeader(buffer_host, info, p->args.cam, p->args.par);
+    HIP_TRY(hipMemcpy(static_cast<unsigned char*>(buffer_host) + wptp::STATE_HEADER_BYTES, p->carry + 2 * size_t(info.block_start),
+            size_t(info.block_size) * wptp::STATE_CARRY_BYTES_PER_PIXEL, hipMemcpyDeviceToHost));
+    return WPT_OK;
+}
+
+wpt_status wpt_progress_state_info(const void* buffer_host, uint64_t bytes, wpt_progress_info* info)
+{
+    if (!info)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "info is NULL");
+    if (bytes > uint64_t(SIZE_MAX))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the state is longer than its header says");
+    const char* refused = wptp::parseState(buffer_host, size_t(bytes), info);
+    return refused ? fail(WPT_ERR_INVALID_ARGUMENT, refused) : WPT_OK;
+}
+
+wpt_status wpt_progress_restore(wpt_scene* scene, const void* buffer_host, uint64_t bytes, const wpt_camera* camera, const wpt_params* params,
+        uint64_t tag, wpt_progress** out_progress)
+{
+    if (out_progress)
+        *out_progress = nullptr;
+    if (!scene || !camera || !params || !out_progress)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    wpt_progress_info info;
+    const wpt_status parsed = wpt_progress_state_info(buffer_host, bytes, &info);
+    if (parsed != WPT_OK)
+        return parsed;
+    const unsigned char* state = static_cast<const unsigned char*>(buffer_host);
+    const char* differs = info.tag != tag ? "tag" : memcmp(state + wptp::STATE_CAMERA, camera, sizeof(*camera)) != 0 ? "camera"
+            : memcmp(state + wptp::STATE_PARAMS, params, sizeof(*params)) != 0 ? "params" : nullptr;
+    if (differs)
+        return fail(WPT_ERR_INVALID_ARGUMENT, std::string("the state was saved with a different ") + differs);
+    /* the body, as far as the header says what it holds: every pixel stands at the first stratum of row rows_done */
+    const uint64_t damaged = wptp::firstDamagedRecord(state, info);
+    if (damaged < info.block_size)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "the state is damaged: the record of pixel " + std::to_string(uint64_t(info.block_start) + damaged)
+                + " does not stand at row rows_done of its strata");
+    wpt_progress* p = nullptr;
+    const wpt_status begun = wpt_progress_begin(scene, camera, params, info.width, info.height, info.samples_sqrt, info.block_start, info.block_size,
+            tag, &p);
+    if (begun != WPT_OK)
+        return begun;
+    const hipError_t e = hipMemcpy(p->carry + 2 * size_t(info.block_start), state + wptp::STATE_HEADER_BYTES,
+            size_t(info.block_size) * wptp::STATE_CARRY_BYTES_PER_PIXEL, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        progressFree(p);
+        return fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    p->rowsDone = info.rows_done;
+    *out_progress = p;
+    return WPT_OK;
 }
 
 } /* extern "C" */

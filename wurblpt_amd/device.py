@@ -26,6 +26,9 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
            "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
+           "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
+           "wpt_progress_save", "wpt_progress_restore", "wpt_progress_state_info",
            "wpt_last_error"]
 
 
@@ -75,6 +78,25 @@ def lib():
         L.wpt_render_tof_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.POINTER(_abi.TofSensor),
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.wpt_tof_accumulate_host.argtypes = [C.POINTER(_abi.TofSensor), C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_void_p]
+        if hasattr(L, "wpt_progress_begin"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_progress_covers.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+            L.wpt_progress_begin.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.wpt_progress_advance_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.wpt_progress_advance.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            L.wpt_progress_rows_done.argtypes = [C.c_void_p]
+            L.wpt_progress_rows_done.restype = C.c_uint32
+            L.wpt_progress_rows_total.argtypes = [C.c_void_p]
+            L.wpt_progress_rows_total.restype = C.c_uint32
+            L.wpt_progress_preview_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_progress_preview.argtypes = [C.c_void_p, C.c_void_p]
+            L.wpt_progress_end.argtypes = [C.c_void_p]
+            L.wpt_progress_end.restype = None
+            L.wpt_progress_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            L.wpt_progress_save.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+            L.wpt_progress_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint64,
+                                               C.POINTER(C.c_void_p)]
+            L.wpt_progress_state_info.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(_abi.ProgressInfo)]
         L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
         L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.wpt_set_walk.argtypes = [C.c_uint32]
@@ -289,6 +311,86 @@ def fold_plan(host_scene, with_words=False):
     return (int(folded.value), words) if with_words else int(folded.value)
 
 
+def progress_covers(sensor=SENSOR_FRAME, counting=False, bands=False):
+    """wpt_progress_covers: raises RuntimeError with the library's reason if progressive sessions do not cover such a launch;
+    needs no device"""
+    _check(lib().wpt_progress_covers(sensor, int(bool(counting)), int(bool(bands))))
+
+
+def progress_state_info(state):
+    """wpt_progress_state_info: the header of a saved session as a dict (version, width, height, samples_sqrt, block_start,
+    block_size, rows_done, tag, state_bytes); a state that is not a good one is refused with RuntimeError.  Needs no device."""
+    state = bytes(state)
+    info = _abi.ProgressInfo()
+    _check(lib().wpt_progress_state_info(state, len(state), C.byref(info)))
+    return {n: int(getattr(info, n)) for n, _ in info._fields_ if n != "reserved"}
+
+
+class Progressive:
+    """A progressive session of a DeviceScene (wurblpt_hip.h, wpt_progress_*): the block's pixels of one frame rendered in
+    stages of rows of strata.  The finished frame is bit for bit DeviceScene.render's; previews are pictures to look at."""
+
+    def __init__(self, scene, handle, width, height, block):
+        self.scene, self._handle = scene, handle
+        self.width, self.height, self.block = width, height, block
+
+    @property
+    def rows_done(self):
+        return int(lib().wpt_progress_rows_done(self._handle))
+
+    @property
+    def rows_total(self):
+        return int(lib().wpt_progress_rows_total(self._handle))
+
+    @property
+    def finished(self):
+        return self.rows_done == self.rows_total
+
+    def advance(self, rows, frame=None, stream=None):
+        """Renders up to `rows` further rows of strata, asynchronously on `stream` (None: the default stream).  `frame`: CUDA
+        float32 tensor [h, w, 3] that the stage which finishes the session writes the block's pixels of; earlier stages do not
+        touch it and need none.  Returns rows_done."""
+        if frame is not None:
+            assert frame.is_cuda and frame.is_contiguous() and frame.dtype.is_floating_point and frame.element_size() == 4
+            assert frame.numel() == self.width * self.height * 3
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
+        _check(lib().wpt_progress_advance_device(self._handle, rows, fptr, sptr))
+        return self.rows_done
+
+    def preview(self, out=None, stream=None):
+        """The preview as a CUDA float32 tensor [h, w, 3] (zeros outside the block; `out`: written in place, and left as it is
+        outside the block), asynchronously on `stream`."""
+        import torch
+        if out is None:
+            out = torch.zeros((self.height, self.width, 3), dtype=torch.float32, device="cuda")
+            if stream is not None:
+                stream.wait_stream(torch.cuda.current_stream())
+        assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() == self.width * self.height * 3
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(lib().wpt_progress_preview_device(self._handle, C.c_void_p(out.data_ptr()), sptr))
+        return out
+
+    def save(self):
+        """wpt_progress_save: the session's state as bytes (waits for the session's last stream)"""
+        n = C.c_uint64()
+        _check(lib().wpt_progress_state_bytes(self._handle, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().wpt_progress_save(self._handle, buf, n.value))
+        return buf.raw
+
+    def close(self):
+        if self._handle:
+            lib().wpt_progress_end(self._handle)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceScene:
     """A flattened scene resident in HBM on the current device."""
 
@@ -306,6 +408,7 @@ class DeviceScene:
         return int(folded.value)
 
     def close(self):
+        """Frees the scene.  Progressive sessions of it must be closed first: they read the scene in every stage."""
         if self._handle:
             lib().wpt_scene_free(self._handle)
             self._handle = C.c_void_p()
@@ -368,6 +471,66 @@ class DeviceScene:
             names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
             cnt = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
         return frame.cpu().numpy(), cnt
+
+    def progressive(self, samples_sqrt, block=None, params=None, width=None, height=None, tag=None, sensor=SENSOR_FRAME,
+                    with_counters=False, bands=False):
+        """wpt_progress_begin: a Progressive session for `block` (default: the whole frame).  `tag`: the caller's fingerprint of
+        the scene, kept in saved states (default: host.scene_tag of this scene).  sensor, with_counters, bands: what kind of
+        launch the session is to stand for; anything but one plain frame is refused with the library's reason."""
+        from . import host
+        progress_covers(sensor, with_counters, bands)
+        w = width or self.host.width
+        h = height or self.host.height
+        p = params if params is not None else host.default_params()
+        start, size = block if block is not None else (0, w * h)
+        handle = C.c_void_p()
+        _check(lib().wpt_progress_begin(self._handle, self.host.camera, C.byref(p), w, h, samples_sqrt, start, size,
+                                        host.scene_tag(self.host) if tag is None else tag, C.byref(handle)))
+        return Progressive(self, handle, w, h, (start, size))
+
+    def resume(self, state, params=None, tag=None, samples_sqrt=None):
+        """wpt_progress_restore: the session a Progressive.save() was taken from, for this scene's camera.  The state's tag,
+        camera and params must be the ones given here (RuntimeError names the first that differs); `samples_sqrt`, if given, is
+        compared with the state's as well."""
+        from . import host
+        state = bytes(state)
+        info = progress_state_info(state)
+        if samples_sqrt is not None and int(samples_sqrt) != info["samples_sqrt"]:
+            raise RuntimeError("wurblpt_hip: the state was saved with a different samples_sqrt (%d, not %d)" % (info["samples_sqrt"], samples_sqrt))
+        p = params if params is not None else host.default_params()
+        handle = C.c_void_p()
+        _check(lib().wpt_progress_restore(self._handle, state, len(state), self.host.camera, C.byref(p),
+                                          host.scene_tag(self.host) if tag is None else tag, C.byref(handle)))
+        return Progressive(self, handle, info["width"], info["height"], (info["block_start"], info["block_size"]))
+
+    def render_stages(self, samples_sqrt, rows_per_stage=None, seconds_per_stage=None, block=None, params=None, width=None, height=None,
+                      tag=None):
+        """Generator over the stages of one frame: yields (rows_done, preview) after every stage that does not finish the frame
+        and (samples_sqrt, frame) at the end, both CUDA tensors [h, w, 3]; the frame is DeviceScene.render's bit for bit.
+        rows_per_stage: rows of strata per stage (default 1).  seconds_per_stage: the first stage renders one row, and every
+        further one as many rows as fit that time by the measured time per row of the stage before, at least 1."""
+        import time
+        import torch
+        session = self.progressive(samples_sqrt, block, params, width, height, tag)
+        try:
+            frame = torch.zeros((session.height, session.width, 3), dtype=torch.float32, device="cuda")
+            stream = torch.cuda.current_stream()
+            rows = 1 if seconds_per_stage is not None else max(1, int(rows_per_stage or 1))
+            while not session.finished:
+                before = session.rows_done
+                torch.cuda.synchronize()
+                start = time.perf_counter()
+                session.advance(rows, frame, stream)
+                torch.cuda.synchronize()
+                self.check()
+                per_row = (time.perf_counter() - start) / (session.rows_done - before)
+                if seconds_per_stage is not None:
+                    rows = max(1, int(min(float(samples_sqrt), seconds_per_stage / per_row))) if per_row > 0 else samples_sqrt
+                if not session.finished:
+                    yield session.rows_done, session.preview(stream=stream)
+            yield session.rows_done, frame
+        finally:
+            session.close()
 
     def render_transient_into(self, frame, bins, samples_sqrt, edges, block=None, params=None, stream=None, width=None, height=None):
         """Asynchronously renders pixels [start, start+size) of the frame and of the transient film in one launch.

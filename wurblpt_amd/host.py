@@ -353,6 +353,18 @@ def mcpt(scene, samples_sqrt, t0=0.0, t1=0.0, width=None, height=None, workers=1
     return frame
 
 
+def scene_tag(scene):
+    """sceneTag() of include/wurblpt/progressive.hpp: the 64-bit fingerprint of a flattened scene that a saved progressive
+    session carries and DeviceScene.resume compares -- FNV-1a over the description's arrays (nodes, tri_geom, tri_attr, instances,
+    materials, textures, texels, hotspots, spheres, rgl_brdfs, rgl_data, animations, keyframes; each as its length in bytes, 8
+    bytes little endian, then its bytes) and the environment map's type, compat, tex, N and cube_tex.  Computed by the C++
+    function itself, so the two sides cannot drift apart."""
+    L = lib()
+    L.wpt_host_scene_tag.restype = C.c_uint64
+    L.wpt_host_scene_tag.argtypes = [C.POINTER(_abi.SceneDesc)]
+    return int(L.wpt_host_scene_tag(scene.desc))
+
+
 MESH_KINDS = {"quad": 0, "cube": 1, "cube_side": 2, "disk": 3, "sphere": 4, "cylinder": 5, "closed_cylinder": 6, "cone": 7,
               "closed_cone": 8, "torus": 9, "tetrahedron": 10, "octahedron": 11, "icosahedron": 12}
 

@@ -14,6 +14,7 @@
 #include "../../include/wurblpt/objreader.hpp"
 #include "../../include/wurblpt/postproc.hpp"
 #include "../../include/wurblpt/wurblpt.hpp"
+#include "../../include/wurblpt/progressive.hpp"
 
 using namespace WurblPT;
 
@@ -195,6 +196,12 @@ extern "C" int wpt_host_mcpt(wpt_host_scene* hs, unsigned int width, unsigned in
     mcpt(sensor, wptHostCameraObjectOf(hs), scene, samplesSqrt, t0, t1);
     memcpy(frame, sensor.result().data(), size_t(width) * height * 3 * sizeof(float));
     return 1;
+}
+
+/* sceneTag() of include/wurblpt/progressive.hpp for a description: the fingerprint a saved progressive session carries */
+extern "C" unsigned long long wpt_host_scene_tag(const wpt_scene_desc* desc)
+{
+    return sceneTag(*desc);
 }
 
 /* getGroundTruth() of include/wurblpt/wurblpt.hpp for a scene of this library.  The camera is the one the scene was
