@@ -739,6 +739,21 @@ wpt_status wpt_kernel_choice(uint32_t need, uint32_t sensor, uint32_t count, uin
         uint32_t scene_has_wide, uint32_t variant, uint32_t walk, const char** name, const char** form, uint32_t key[4],
         uint64_t* scene_lds_bytes, uint32_t* materials_in_lds);
 wpt_status wpt_kernel_table_entry(uint32_t index, uint32_t key[4], const char** name);
+/* Which passes render a launch, from the facts the library decides by: a pure function that needs no device (tests; DESIGN.md
+ * section 4 has the rule as a table).  sensor, count: as for wpt_kernel_choice; need: only its FEAT_RGL and FEAT_ANIM bits are
+ * read; scene_in_lds: the launch's kernel keeps the scene in LDS (wpt_kernel_choice: scene_lds_bytes > 0); block_size: the
+ * launch's pixels; samples_sqrt: 1 for an adaptive launch; cu_count: the device's compute units; variant, wavefront_mode,
+ * slices: the words of wpt_set_launch_config, wpt_set_wavefront (mode) and wpt_set_slices.  plan: [WPT_PLAN_WAVEFRONT] 1: the
+ * wavefront form renders the launch, and the words behind say how the single kernel does where [WPT_PLAN_WAVEFRONT_FALLS_BACK]
+ * is 1 and the memory for the wavefront form cannot be had (0: a wavefront render reports every error); [WPT_PLAN_POOLED] the
+ * pixels are handed out from the pixel pool; [WPT_PLAN_STRATEGY] one of WPT_STRATEGY_*; [WPT_PLAN_UNITS], [WPT_PLAN_ROWS] of a
+ * sliced launch (else 1 and samples_sqrt); [WPT_PLAN_PASSES] what wpt_last_render_passes reports after the single kernel.
+ * Where the memory a strategy needs cannot be had, the launch itself falls back to one pass; the plan does not say so. */
+enum { WPT_PLAN_WAVEFRONT, WPT_PLAN_WAVEFRONT_FALLS_BACK, WPT_PLAN_POOLED, WPT_PLAN_STRATEGY, WPT_PLAN_UNITS, WPT_PLAN_ROWS, WPT_PLAN_PASSES,
+    WPT_PLAN_WORDS };
+enum { WPT_STRATEGY_ONE_PASS, WPT_STRATEGY_TWO_PASSES, WPT_STRATEGY_ADAPTIVE_ORDER, WPT_STRATEGY_SLICED };
+wpt_status wpt_launch_plan(uint32_t sensor, uint32_t count, uint32_t need, uint32_t scene_in_lds, uint32_t block_size, uint32_t samples_sqrt,
+        uint32_t cu_count, uint32_t variant, uint32_t wavefront_mode, uint32_t slices, uint32_t plan[WPT_PLAN_WORDS]);
 /* What the reference records about a run for the CPU (wurblpt.hpp:393-400,425-435: COMPILER, CPU_MODEL), for the device:
  * marketing name and architecture of HIP device `device` ("AMD Instinct MI355X (gfx950:...)", or "" if there is none), and
  * the compiler and options the kernels were built with.  The strings live until the next call from the same thread. */

@@ -184,3 +184,36 @@ def test_variant_0x40_never_slices(dev, ds, references):
         dev.lib().wpt_set_launch_config(0, 0)
     assert form == "rotated corners" and (taken, continued) == (0, 0)
     assert bits_differing(got, references(8)) == 0
+
+
+def test_a_render_that_is_not_sliced_reports_no_slice_statistics(dev, ds, references):
+    """wpt_last_slice_stats is the most recent render call's: behind a sliced launch, a forced wavefront render and a stage of a
+    session both report (0, 0), and render their block of the unpooled frame bit for bit"""
+    import torch
+    rows = slice(311, 315)                                 # a block of 64 x 64 pixels: four rows across the boxes
+    block = (rows.start * W, 64 * 64)
+    ref = references(2)
+    assert ref[rows].any()
+    _, units, taken, continued, _ = render_sliced(dev, ds, 8, 4)
+    assert units == 4 and taken + continued == W * H * 3
+    dev.lib().wpt_set_wavefront(1, 0, 0, 0)
+    try:
+        wf, _ = ds.render(2, block=block)
+        name, stats = dev.lib().wpt_kernel_name(), dev.last_slice_stats()
+    finally:
+        dev.lib().wpt_set_wavefront(0, 0, 0, 0)
+    assert stats == (0, 0) and name == b"wf_trace + wf_shade"
+    assert bits_differing(wf[rows], ref[rows]) == 0
+    _, units, taken, continued, _ = render_sliced(dev, ds, 8, 4)
+    assert units == 4 and taken + continued == W * H * 3
+    frame = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
+    session = ds.progressive(2, block=block)
+    try:
+        assert session.advance(2, frame) == 2
+        torch.cuda.synchronize()
+        ds.check()
+        assert dev.last_slice_stats() == (0, 0) and dev.lib().wpt_last_render_passes() == 1
+        assert dev.lib().wpt_kernel_name() == b"wpt_pathtrace" and dev.lib().wpt_kernel_form() == b"rotated corners"
+    finally:
+        session.close()
+    assert bits_differing(frame.cpu().numpy()[rows], ref[rows]) == 0

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "../../include/wurblpt_hip.h"
 #include "wpt_pathtrace.inc.h"
 #include "wpt_kernel_table.h"
+#include "wpt_launch_plan.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 #include "wpt_progress.h"
@@ -258,6 +260,12 @@ wpt_status fail(wpt_status s, const std::string& msg)
         if (e_ != hipSuccess)                                                                      \
             return fail(WPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
     } while (0)
+#define WPT_TRY(expr)                                                                              \
+    do {                                                                                           \
+        const wpt_status s_ = (expr);                                                              \
+        if (s_ != WPT_OK)                                                                          \
+            return s_;                                                                             \
+    } while (0)
 
 } /* namespace */
 
@@ -301,12 +309,23 @@ uint32_t g_slices = 0;
 constexpr int SLICE_STATS_DEVICES = 64;
 std::atomic<unsigned long long*> g_sliceStats[SLICE_STATS_DEVICES];
 std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
-/* Units per pixel that wpt_slices_plan aims for at most: the best of the sweep over 1, 2, 4, 8 and 15 on the bench frame
- *  */
-constexpr uint32_t SLICE_UNITS_TARGET = 15;
+static_assert(wptk::PLAN_WG == uint32_t(WG) && wptk::PLAN_SLICE_SLOT_MAX == wptk::SLICE_SLOT_MASK && wptk::SLICE_UNITS_TARGET <= wptk::SLICE_UNITS_MAX
+        && wptk::PLAN_FRAME == wptk::SENSOR_FRAME && wptk::PLAN_VIEWS == wptk::SENSOR_VIEWS && wptk::PLAN_ADAPTIVE == wptk::SENSOR_ADAPTIVE
+        && wptk::PLAN_SENSORS == wptk::SENSOR_COUNT, "wpt_launch_plan.h restates the kernels' constants and the sensors");
 
-/* wpt_kernel_form of a launch of the kernels with the scene in LDS */
-const char* ldsKernelForm(bool rotated, uint32_t units)
+/* What the process's most recent render call ran, all of it at once: every path that renders stores it here and nowhere else
+ * (the wavefront form and the stages of a session too).  sliceStats: the counters a sliced launch adds to, else NULL. */
+void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned long long* sliceStats)
+{
+    g_kernelName.store(name, std::memory_order_relaxed);
+    g_kernelForm.store(form, std::memory_order_relaxed);
+    g_lastPasses.store(passes, std::memory_order_relaxed);
+    g_lastSliceStats.store(sliceStats, std::memory_order_relaxed);
+}
+
+/* wpt_kernel_form of a launch: "rotated corners" for that form of the kernel with the scene in LDS, ", sliced xU" behind it for
+ * a launch that hands its pixels out in U > 1 units */
+const char* kernelForm(bool rotated, uint32_t units = 0)
 {
     static const std::vector<std::string> forms = [] {
         std::vector<std::string> f;
@@ -316,12 +335,6 @@ const char* ldsKernelForm(bool rotated, uint32_t units)
         return f;
     }();
     return forms[(rotated ? wptk::SLICE_UNITS_MAX + 1 : 0) + (units <= wptk::SLICE_UNITS_MAX ? units : 0)].c_str();
-}
-
-/* wpt_kernel_form of a launch that is not sliced */
-const char* kernelForm(const wptk::KernelChoice& choice)
-{
-    return choice.rotated ? "rotated corners" : "";
 }
 
 /* the kernel table's row for an instantiation; there is no launch without one */
@@ -1071,11 +1084,31 @@ wpt_status wpt_scene_get_envmap_tables(const wpt_scene* scene, float* M, int32_t
     return WPT_OK;
 }
 
+} /* extern "C" */
+
+namespace {
+
+/* The frame and block checks of every render call, one text each.  samplesSqrt: NULL where the call has none (an adaptive map
+ * holds the counts); the block must lie in `frames` frames of width * height pixels (a batch of views: one per camera); prefix:
+ * what the entry point's messages begin with; session: an empty block is refused too. */
+wpt_status checkFrameBlock(uint32_t width, uint32_t height, const uint32_t* samplesSqrt, uint32_t blockStart, uint32_t blockSize,
+        uint32_t frames = 1, const char* prefix = "", bool session = false)
+{
+    if (width == 0 || height == 0 || width > 65535 || height > 65535 || (samplesSqrt && (*samplesSqrt == 0 || *samplesSqrt > 65535)))
+        return fail(WPT_ERR_INVALID_ARGUMENT, std::string(prefix) + (samplesSqrt ? "width, height and samples_sqrt" : "width and height")
+                + " must lie in 1 .. 65535");
+    /* (width * height fits 32 bits after the check above) */
+    if ((session && blockSize == 0) || uint64_t(blockStart) + blockSize > uint64_t(width) * height * frames)
+        return fail(WPT_ERR_INVALID_ARGUMENT, std::string(prefix) + (session ? "pixel block is empty or lies outside the frame"
+                : "pixel block lies outside the frame"));
+    return WPT_OK;
+}
+
 /* What every launch of the single kernel sets up the same way, a plain block, bands, a batch of views or a stage of a session
  * (wpt_progress_begin): the frame's constants, the 8x8 tiles, the features the cameras add to the scene's, the scheduler's
  * settings.  `camera` is the first of cameraCount cameras (batch: they are a batch of views); frame, counters, the sensor's
  * view and what a stage adds are the caller's. */
-static wpt_status launchSetUp(const wpt_scene* scene, const wpt_camera* camera, uint32_t cameraCount, bool batch, const wpt_params* params,
+wpt_status launchSetUp(const wpt_scene* scene, const wpt_camera* camera, uint32_t cameraCount, bool batch, const wpt_params* params,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         uint32_t band_pixels, uint32_t band_first, uint32_t band_stride, bool count, wptk::KernelArgs& args, uint32_t& need)
 {
@@ -1140,216 +1173,240 @@ static wpt_status launchSetUp(const wpt_scene* scene, const wpt_camera* camera, 
     return WPT_OK;
 }
 
-/* one launch: a block of consecutive pixels (band_stride == 0) or interleaved bands of band_pixels pixels */
-static wpt_status renderLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
-        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
-        uint32_t band_pixels, uint32_t band_first, uint32_t band_stride,
-        float* frame_device, wpt_counters* counters_device, void* hip_stream, const wptk::BinsView* transient = nullptr,
-        const wptk::ViewsView* views = nullptr, const wptk::AdaptiveView* adaptive = nullptr, bool tof = false)
+/* One launch of the path tracer: a block of consecutive pixels (bandStride == 0) or interleaved bands of bandPixels pixels, and
+ * the one sensor it renders for, whose view is the member that `sensor` names.  Every caller sets the first ten members. */
+struct LaunchRequest {
+    wpt_scene* scene;
+    const wpt_camera* camera; /* SENSOR_VIEWS: the first of views.viewCount host cameras, the block all their pixels */
+    const wpt_params* params;
+    uint32_t width, height, samplesSqrt, blockStart, blockSize;
+    float* frame; /* may be NULL for the transient film and for several time-of-flight phases */
+    void* stream;
+    wpt_counters* counters = nullptr;
+    uint32_t bandPixels = 0, bandFirst = 0, bandStride = 0;
+    wptk::Sensor sensor = wptk::SENSOR_FRAME;
+    wptk::BinsView bins = {};         /* SENSOR_TRANSIENT, SENSOR_TOF (wpt_blocks.h, accumulate) */
+    wptk::ViewsView views = {};       /* SENSOR_VIEWS */
+    wptk::AdaptiveView adaptive = {}; /* SENSOR_ADAPTIVE */
+};
+
+/* The stream-ordered scratch memory of one launch (the pool's counter, carry, cost, order, work words, slice words and carry):
+ * launches in flight on any number of streams never share any of it; freed in stream order when the owner goes out of scope,
+ * behind the read of the launch's error. */
+struct StreamScratch {
+    hipStream_t stream;
+    void* held[5] = {}; /* the counter and the four arrays of two passes: no launch asks for more */
+    uint32_t count = 0;
+    explicit StreamScratch(hipStream_t s) : stream(s) {}
+    StreamScratch(const StreamScratch&) = delete;
+    ~StreamScratch()
+    {
+        for (uint32_t i = 0; i < count; i++)
+            (void)hipFreeAsync(held[i], stream);
+    }
+    /* n elements, or NULL where the memory cannot be had: the error is cleared, the launch goes without */
+    template<typename T> T* get(size_t n)
+    {
+        void* p = nullptr;
+        assert(count < sizeof(held) / sizeof(held[0]));
+        if (hipMallocAsync(&p, n * sizeof(T), stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        return static_cast<T*>(held[count++] = p);
+    }
+};
+
+/* the single kernel of a launch, as every execution below launches it */
+struct SingleKernel {
+    const wptk::KernelEntry* kernel;
+    dim3 grid;
+    size_t sceneLdsBytes;
+    hipStream_t stream;
+    void operator()(const wptk::KernelArgs& a) const { kernel->launch(a, grid, sceneLdsBytes, stream); }
+};
+
+/* the work words of the order kernels (wpt_k_order.hip); the last is the number of entries of the order they build */
+constexpr size_t ORDER_WORK_WORDS = 3 * wptk::ORDER_BUCKETS + 1;
+
+/* `order` from the costs `measured` left per pixel, the costliest 8x8 tiles first, for `next` to take its pixels in */
+void orderByCost(const wptk::KernelArgs& measured, uint32_t* order, uint32_t* work, hipStream_t stream, wptk::KernelArgs& next)
 {
-    /* (tof: a launch for the time-of-flight sensor, which `transient` then describes -- wpt_blocks.h, accumulate) */
-    if (!scene || !camera || !params || !(frame_device || transient))
+    wptk::launchOrderBuild(measured, order, work, stream);
+    next.order = order;
+    next.orderCount = work + ORDER_WORK_WORDS - 1;
+}
+
+/* TWO_PASSES: one timed row of strata of every pixel, then the rest in the order of those times.  false, and nothing
+ * launched: the memory cannot be had. */
+bool runTwoPasses(const wptk::KernelArgs& args, const SingleKernel& run, StreamScratch& scratch)
+{
+    const size_t pixels = size_t(args.width) * args.height;
+    float4* carry;
+    uint32_t *cost, *order, *work;
+    if (!(carry = scratch.get<float4>(pixels * 2)) || !(cost = scratch.get<uint32_t>(pixels)) || !(order = scratch.get<uint32_t>(args.blockSize))
+            || !(work = scratch.get<uint32_t>(ORDER_WORK_WORDS)))
+        return false;
+    wptk::KernelArgs first = args, second = args;
+    first.rowStop = 1;
+    first.carry = second.carry = carry;
+    first.cost = cost;
+    run(first);
+    orderByCost(first, order, work, run.stream, second);
+    run(second);
+    return true;
+}
+
+/* ADAPTIVE_ORDER: one pass in the order built from the sample counts n^2 of the map.  false as above. */
+bool runAdaptiveOrder(const wptk::KernelArgs& args, const SingleKernel& run, StreamScratch& scratch)
+{
+    uint32_t *cost, *order, *work;
+    if (!(cost = scratch.get<uint32_t>(args.blockSize)) || !(order = scratch.get<uint32_t>(args.blockSize)) || !(work = scratch.get<uint32_t>(ORDER_WORK_WORDS)))
+        return false;
+    wptk::KernelArgs measure = args, ordered = args;
+    measure.cost = cost - args.blockStart; /* indexed by the frame's pixel: the block's pixels land in the allocation */
+    wptk::launchAdaptiveCost(measure, run.stream);
+    orderByCost(measure, order, work, run.stream, ordered);
+    run(ordered);
+    return true;
+}
+
+/* SLICED: one launch of the kernel's twin that hands the pixels out in plan.units units of plan.rows rows.  Returns the
+ * counters the launch adds to (wpt_last_slice_stats), or NULL and nothing launched: they or the memory cannot be had. */
+unsigned long long* runSliced(const wptk::KernelArgs& args, const SingleKernel& runTwin, const wptk::LaunchPlan& plan, StreamScratch& scratch)
+{
+    unsigned long long* stats = sliceStatsOfCurrentDevice();
+    float4* carry;
+    uint32_t* words;
+    if (!stats || !(carry = scratch.get<float4>(size_t(args.blockSize) * 2)) || !(words = scratch.get<uint32_t>(args.blockSize)))
+        return nullptr;
+    if (hipMemsetAsync(words, 0, size_t(args.blockSize) * sizeof(uint32_t), runTwin.stream) != hipSuccess
+            || hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), runTwin.stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    wptk::KernelArgs inSlices = args;
+    inSlices.slices = { words, carry, stats, plan.rows, plan.units, (g_slices & WPT_SLICES_DECLINE_ODD) ? 1u : 0u };
+    runTwin(inSlices);
+    return stats;
+}
+
+/* The single kernel by the plan's strategy, and the pool's counter where the plan has one.  Where the memory a strategy needs
+ * cannot be had (the counter first of all), one plain pass renders the launch.  Returns the launch's error. */
+hipError_t runSingleKernel(wptk::KernelArgs& args, const wptk::KernelChoice& choice, const wptk::KernelEntry* kernel,
+        const wptk::KernelEntry* slicedTwin, const wptk::LaunchPlan& plan, hipStream_t stream)
+{
+    StreamScratch scratch(stream);
+    args.pool = plan.pooled ? scratch.get<uint32_t>(1) : nullptr;
+    args.materialsInLds = choice.materialsInLds;
+    const SingleKernel run = { kernel, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
+    bool done = false;
+    unsigned long long* sliceStats = nullptr;
+    if (args.pool && plan.strategy == wptk::TWO_PASSES)
+        done = runTwoPasses(args, run, scratch);
+    else if (args.pool && plan.strategy == wptk::ADAPTIVE_ORDER)
+        done = runAdaptiveOrder(args, run, scratch);
+    else if (args.pool && plan.strategy == wptk::SLICED)
+        done = (sliceStats = runSliced(args, SingleKernel{ slicedTwin, run.grid, run.sceneLdsBytes, stream }, plan, scratch)) != nullptr;
+    if (!done)
+        run(args);
+    recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0), done ? plan.passes : 1u, sliceStats);
+    return hipGetLastError();
+}
+
+/* one launch, in five steps: check, set up, choose the kernel (wpt_kernel_table.h), plan its passes (wpt_launch_plan.h), execute */
+wpt_status renderLaunch(const LaunchRequest& rq)
+{
+    const bool planes = rq.sensor == wptk::SENSOR_TRANSIENT || rq.sensor == wptk::SENSOR_TOF, views = rq.sensor == wptk::SENSOR_VIEWS;
+    if (!rq.scene || !rq.camera || !rq.params || !(rq.frame || planes))
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    /* a batch of views: `camera` is the first of views->viewCount host cameras, the block all their pixels (wpt_render_views_device) */
-    const uint32_t cameraCount = views ? views->viewCount : 1u;
-    if (uint64_t(width) * height > 0xffffffffull
-            || uint64_t(block_start) + (band_stride ? 0u : block_size) > uint64_t(width) * height * cameraCount)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
-    if (block_size == 0)
-        return WPT_OK;
-    KernelArgs args;
+    const uint32_t cameraCount = views ? rq.views.viewCount : 1u;
+    const wpt_status checked = checkFrameBlock(rq.width, rq.height, &rq.samplesSqrt, rq.blockStart, rq.bandStride ? 0u : rq.blockSize, cameraCount);
+    if (checked != WPT_OK || rq.blockSize == 0)
+        return checked;
+    KernelArgs args = {};
     uint32_t need = 0;
-    const bool count = counters_device != nullptr;
-    const wpt_status setUp = launchSetUp(scene, camera, cameraCount, views != nullptr, params, width, height, samples_sqrt, block_start, block_size,
-            band_pixels, band_first, band_stride, count, args, need);
-    if (setUp != WPT_OK)
-        return setUp;
-    args.frame = frame_device;
-    args.counters = counters_device;
+    const bool count = rq.counters != nullptr;
+    WPT_TRY(launchSetUp(rq.scene, rq.camera, cameraCount, views, rq.params, rq.width, rq.height, rq.samplesSqrt, rq.blockStart,
+            rq.blockSize, rq.bandPixels, rq.bandFirst, rq.bandStride, count, args, need));
+    args.frame = rq.frame;
+    args.counters = rq.counters;
     args.schedStats = g_schedStats;
     if (views)
-        args.views = *views;
-    else if (adaptive)
-        args.adaptive = *adaptive;
-    else
-        args.bins = transient ? *transient : wptk::BinsView{};
-    dim3 grid((block_size + WG - 1) / WG);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    /* kernel choice (wpt_kernel_table.h) */
-    const wptk::Sensor sensor = tof ? wptk::SENSOR_TOF : adaptive ? wptk::SENSOR_ADAPTIVE : views ? wptk::SENSOR_VIEWS
-            : transient ? wptk::SENSOR_TRANSIENT : wptk::SENSOR_FRAME;
-    const wptk::KernelChoice choice = wptk::selectKernel({ need, sensor, count, scene->nodeCount, scene->triCount, uint32_t(scene->view.materialCount),
-            scene->view.wideNodes != nullptr, g_variant, g_walk });
-    const wptk::KernelEntry *kernel = nullptr, *slicedKernel = nullptr;
+        args.views = rq.views;
+    else if (rq.sensor == wptk::SENSOR_ADAPTIVE)
+        args.adaptive = rq.adaptive;
+    else if (planes)
+        args.bins = rq.bins;
+    args.rowStop = rq.samplesSqrt;
+    const wptk::KernelChoice choice = wptk::selectKernel({ need, rq.sensor, count, rq.scene->nodeCount, rq.scene->triCount,
+            uint32_t(rq.scene->view.materialCount), rq.scene->view.wideNodes != nullptr, g_variant, g_walk });
+    const wptk::KernelEntry *kernel = nullptr, *slicedTwin = nullptr;
     wpt_status found = lookupKernel(choice.features, choice.count, choice.ldsScene, choice.wide, &kernel);
-    /* its twin that hands pixels out in slices, for the slicing block below */
-    const bool mayBeSliced = choice.sceneInLds && sensor == wptk::SENSOR_FRAME && !count;
-    if (found == WPT_OK && mayBeSliced)
-        found = lookupKernel(choice.features | FEAT_SLICED, choice.count, choice.ldsScene, choice.wide, &slicedKernel);
+    /* its twin that hands pixels out in slices, for a SLICED plan */
+    if (found == WPT_OK && choice.sceneInLds && rq.sensor == wptk::SENSOR_FRAME && !count)
+        found = lookupKernel(choice.features | FEAT_SLICED, choice.count, choice.ldsScene, choice.wide, &slicedTwin);
     if (found != WPT_OK)
         return found;
     const bool rgl = (need & FEAT_RGL) != 0;
-    args.rowStop = samples_sqrt;
-    args.carry = nullptr;
-    args.cost = nullptr;
-    args.order = nullptr;
-    args.orderCount = nullptr;
-    /* Pixel pool: frames with more pixels than the device has lanes at once are handed out pixel by pixel (the launchers
-     * decide); variant bit 0x10: never.  The counter is allocated and freed in stream order, so launches in flight on any
-     * number of streams never share one. */
-    /* Wavefront form (wpt_wavefront.inc.h): trace and shade as two kernels that hand rays through HBM.  Not for counting
-     * launches and moving scenes (those instantiations exist for the single kernel only). */
-    const bool wfExists = sensor == wptk::SENSOR_FRAME && !count && !(need & FEAT_ANIM); /* (a transient film, a batch of views and an adaptive launch are always rendered by the single kernel) */
-    /* The library's own choice (measured): launches of 2^21 lanes and more whose scene has measured BRDFs --
-     * long shading that pays for being sorted by kind of material, and enough lanes to fill the trace and the shade kernel one
-     * after the other (tools/wf_threshold_probe.py, 16 spp, single kernel / wavefront: 115.5 / 100.7 Msamples/s at 2^20 lanes,
-     * 118.0 / 116.4 at 1.97 M, 113.6 / 126.9 at 4.1 M, 114.0 / 135.3 at 8.3 M).  Scenes whose time is the walk stay with the
-     * single kernel: the wavefront trace meets the same wall of the memory system (Sponza-class 120.6 against 158, 10 M
-     * triangles 38 against 63 in round 3) and pays for the rays' way through HBM on top. */
-    const bool wfAuto = rgl && block_size >= (1u << 21);
-    if (wfExists && (g_wfMode == 1u || (g_wfMode == 0u && wfAuto))) {
-        args.pool = nullptr;
-        args.materialsInLds = 0;
-        const wptk::WfLaunchers& kernels = rgl ? wptk::wfFullRgl() : (choice.basic ? wptk::wfBasic() : wptk::wfFull());
-        uint32_t launches = 0;
-        const hipError_t e = wptk::renderWavefront(args, kernels, g_wfConfig, stream, &launches);
+    hipStream_t stream = static_cast<hipStream_t>(rq.stream);
+    const wptk::LaunchPlan plan = wptk::planLaunch({ rq.sensor, count, rgl, (need & FEAT_ANIM) != 0, choice.sceneInLds, rq.blockSize, rq.samplesSqrt,
+            uint32_t(rq.scene->cuCount), g_variant, g_wfMode, g_slices });
+    if (plan.wavefront) {
+        uint32_t launches = 0; /* of trace and shade, two kernels that hand rays through HBM (wpt_wavefront.inc.h) */
+        const hipError_t e = wptk::renderWavefront(args, rgl ? wptk::wfFullRgl() : (choice.basic ? wptk::wfBasic() : wptk::wfFull()), g_wfConfig, stream, &launches);
         if (e == hipSuccess) {
-            g_lastPasses.store(launches, std::memory_order_relaxed);
-            g_kernelName.store("wf_trace + wf_shade", std::memory_order_relaxed);
-            g_kernelForm.store("", std::memory_order_relaxed);
+            recordLaunch("wf_trace + wf_shade", "", launches, nullptr);
             return WPT_OK;
         }
-        /* The library's own choice must not fail where the single kernel would not: without the memory for the records
-         * (256 B per lane) the frame is rendered by the single kernel below.  A forced wavefront render reports the error. */
-        if (g_wfMode == 1u || e != hipErrorOutOfMemory)
+        /* the library's own choice must not fail where the single kernel would not: without the memory for the records (256 B
+         * per lane) that one renders the frame; a forced wavefront render reports the error */
+        if (!plan.wavefrontFallBack || e != hipErrorOutOfMemory)
             return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
         (void)hipGetLastError();
     }
-    uint32_t* pool = nullptr;
-    const bool pooled = !count && !(g_variant & 0x10u) && block_size < 0x80000000u && grid.x > uint32_t(scene->cuCount);
-    if (pooled && hipMallocAsync(reinterpret_cast<void**>(&pool), sizeof(uint32_t), stream) != hipSuccess) {
-        (void)hipGetLastError();
-        pool = nullptr;
-    }
-    args.pool = pool;
-    args.materialsInLds = choice.materialsInLds;
-    g_kernelName.store(kernel->name, std::memory_order_relaxed);
-    g_kernelForm.store(kernelForm(choice), std::memory_order_relaxed);
-    auto launch = [&](const wptk::KernelArgs& a, const wptk::KernelEntry* k) { k->launch(a, grid, choice.sceneLdsBytes, stream); };
-    /* Two passes for the kernels that fetch the scene from HBM (variant bit 0x40: never): with 2 to 64 pixels per lane the
-     * end of a launch, when lanes run out of pixels one by one, is a noticeable part of it.  The first pass renders one row
-     * of strata of every pixel and times it, the second renders the rest, the 8x8 tiles that took longest first
-     * (Sponza-class frame +2.9 %, 10 M triangles +1.8 %).  Not for the scene in LDS: there the launch is bound by how well
-     * a wave's lanes keep in step, any order but the frame's own costs that more than the shorter end gives (Cornell
-     * 938 against 954). */
-    const uint64_t lanesAtOnce = uint64_t(scene->cuCount) * 4u * WG;
-    /* (not for a batch of views: the carry, cost and order buffers are indexed by the pixel of one frame) */
-    const bool twoPasses = pool != nullptr && !(g_variant & 0x40u) && !choice.sceneInLds && !views && !adaptive && samples_sqrt >= 8
-            && uint64_t(block_size) >= 2u * lanesAtOnce && uint64_t(block_size) <= 64u * lanesAtOnce;
-    float4* carry = nullptr;
-    uint32_t *cost = nullptr, *order = nullptr, *work = nullptr;
-    bool passesDone = false;
-    if (twoPasses) {
-        const size_t pixels = size_t(width) * height;
-        if (hipMallocAsync(reinterpret_cast<void**>(&carry), pixels * 2 * sizeof(float4), stream) == hipSuccess
-                && hipMallocAsync(reinterpret_cast<void**>(&cost), pixels * sizeof(uint32_t), stream) == hipSuccess
-                && hipMallocAsync(reinterpret_cast<void**>(&order), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
-                && hipMallocAsync(reinterpret_cast<void**>(&work), (3 * wptk::ORDER_BUCKETS + 1) * sizeof(uint32_t), stream) == hipSuccess) {
-            wptk::KernelArgs first = args;
-            first.rowStop = 1;
-            first.carry = carry;
-            first.cost = cost;
-            launch(first, kernel);
-            wptk::launchOrderBuild(first, order, work, stream);
-            wptk::KernelArgs second = args;
-            second.carry = carry;
-            second.order = order;
-            second.orderCount = work + 3 * wptk::ORDER_BUCKETS;
-            launch(second, kernel);
-            passesDone = true;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    /* Adaptive sampling: one pass that hands out the costly pixels first -- the order of the second pass above, built from
-     * the sample counts n^2 instead of a first pass's times (variant bit 0x40: the plain order).  Any scene kind: a pixel's
-     * work is known before the launch here.  The order changes which lane renders a pixel when, never a bit of it. */
-    if (adaptive && pool != nullptr && !(g_variant & 0x40u)) {
-        if (hipMallocAsync(reinterpret_cast<void**>(&cost), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
-                && hipMallocAsync(reinterpret_cast<void**>(&order), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
-                && hipMallocAsync(reinterpret_cast<void**>(&work), (3 * wptk::ORDER_BUCKETS + 1) * sizeof(uint32_t), stream) == hipSuccess) {
-            wptk::KernelArgs measure = args;
-            measure.cost = cost - block_start; /* indexed by the frame's pixel: the block's pixels land in the allocation */
-            wptk::launchAdaptiveCost(measure, stream);
-            wptk::launchOrderBuild(measure, order, work, stream);
-            wptk::KernelArgs ordered = args;
-            ordered.order = order;
-            ordered.orderCount = work + 3 * wptk::ORDER_BUCKETS;
-            launch(ordered, kernel);
-            passesDone = true;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    /* Pixels in slices for the kernels with the scene in LDS (wpt_pathtrace.inc.h, SlicesView; variant bit 0x40: never): the
-     * frame's own order and one launch, which is what the two passes above cost these kernels, but the launch ends on a
-     * fraction of a pixel.  Pooled, plain product launches only.  Without the memory for it the plain kernel renders the frame. */
-    uint32_t* sliceWords = nullptr;
-    float4* sliceCarry = nullptr;
-    g_lastSliceStats.store(nullptr, std::memory_order_relaxed);
-    if (mayBeSliced && pool != nullptr && !(g_variant & 0x40u)
-            && uint64_t(block_size) > lanesAtOnce && block_size <= wptk::SLICE_SLOT_MASK) {
-        uint32_t units = 1, rows = samples_sqrt;
-        const uint32_t forced = g_slices & 0xffu;
-        if (forced == 0) {
-            wpt_slices_plan(block_size, uint32_t(lanesAtOnce), samples_sqrt, &units, &rows);
-        } else if (forced >= 2) {
-            rows = (samples_sqrt + forced - 1) / forced;
-            units = (samples_sqrt + rows - 1) / rows;
-        }
-        /* (the pool's counter runs past its last index by less than the lanes of the launch) */
-        unsigned long long* stats = nullptr;
-        if (units >= 2 && uint64_t(units) * block_size + 2 * lanesAtOnce < 0x100000000ull && (stats = sliceStatsOfCurrentDevice()) != nullptr) {
-            if (hipMallocAsync(reinterpret_cast<void**>(&sliceCarry), size_t(block_size) * 2 * sizeof(float4), stream) == hipSuccess
-                    && hipMallocAsync(reinterpret_cast<void**>(&sliceWords), size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
-                    && hipMemsetAsync(sliceWords, 0, size_t(block_size) * sizeof(uint32_t), stream) == hipSuccess
-                    && hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), stream) == hipSuccess) {
-                wptk::KernelArgs inSlices = args;
-                inSlices.slices.words = sliceWords;
-                inSlices.slices.carry = sliceCarry;
-                inSlices.slices.stats = stats;
-                inSlices.slices.rows = rows;
-                inSlices.slices.units = units;
-                inSlices.slices.declineOdd = (g_slices & WPT_SLICES_DECLINE_ODD) ? 1u : 0u;
-                launch(inSlices, slicedKernel);
-                passesDone = true;
-                g_lastSliceStats.store(stats, std::memory_order_relaxed);
-                g_kernelForm.store(ldsKernelForm(choice.rotated, units), std::memory_order_relaxed);
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    }
-    if (!passesDone)
-        launch(args, kernel);
-    g_lastPasses.store(passesDone && !adaptive && !sliceWords ? 2u : 1u, std::memory_order_relaxed);
-    const hipError_t launched = hipGetLastError();
-    for (void* p : { static_cast<void*>(pool), static_cast<void*>(carry), static_cast<void*>(cost), static_cast<void*>(order), static_cast<void*>(work),
-            static_cast<void*>(sliceWords), static_cast<void*>(sliceCarry) })
-        if (p)
-            (void)hipFreeAsync(p, stream);
-    HIP_TRY(launched);
+    HIP_TRY(runSingleKernel(args, choice, kernel, slicedTwin, plan, stream));
     return WPT_OK;
 }
+
+/* Device memory of a host entry point for a block's pixels only, not a frame's: the launch gets a pointer biased so that pixel
+ * `blockStart` lands at offset 0.  Freed at scope exit. */
+struct StagedBlock {
+    void* device = nullptr;
+    size_t bytes = 0;
+    StagedBlock() = default;
+    StagedBlock(const StagedBlock&) = delete;
+    ~StagedBlock() { (void)hipFree(device); }
+    hipError_t allocate(size_t n) { return hipMalloc(&device, bytes = n); }
+    hipError_t allocatePixels(size_t pixels, size_t planes = 1) { return allocate(pixels * 3 * sizeof(float) * planes); }
+    hipError_t upload(const void* host) { return hipMemcpy(device, host, bytes, hipMemcpyHostToDevice); }
+    hipError_t download(void* host) const { return device ? hipMemcpy(host, device, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+    /* NULL without memory: an output the caller did not ask for */
+    float* biased(uint32_t blockStart) const { return device ? static_cast<float*>(device) - size_t(blockStart) * 3 : nullptr; }
+};
+
+/* The end of a host entry point: behind a launch that went well, waits for the device and reports what its kernels ran into
+ * (wpt_scene_check; check == NULL: the launch is not the scene's), then copies the staged blocks that exist to their host arrays. */
+wpt_status finishStaged(wpt_status launched, wpt_scene* check, const StagedBlock& a, void* hostA, const StagedBlock* b = nullptr, void* hostB = nullptr)
+{
+    const wpt_status st = launched == WPT_OK && check ? wpt_scene_check(check) : launched;
+    hipError_t e = st == WPT_OK ? a.download(hostA) : hipSuccess;
+    if (st == WPT_OK && e == hipSuccess && b)
+        e = b->download(hostB);
+    return e == hipSuccess ? st : fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+}
+
+} /* namespace */
+
+extern "C" {
 
 wpt_status wpt_render_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         float* frame_device, wpt_counters* counters_device, void* hip_stream)
 {
-    return renderLaunch(scene, camera, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0, frame_device, counters_device,
-            hip_stream);
+    LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, block_start, block_size, frame_device, hip_stream };
+    rq.counters = counters_device;
+    return renderLaunch(rq);
 }
 
 wpt_status wpt_render_bands_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
@@ -1363,8 +1420,12 @@ wpt_status wpt_render_bands_device(wpt_scene* scene, const wpt_camera* camera, c
     const uint64_t mine = first_band < bands ? (bands - first_band + band_stride - 1) / band_stride : 0;
     if (bandPixels > 0xffffffffull || mine * bandPixels > 0xffffffffull)
         return fail(WPT_ERR_INVALID_ARGUMENT, "bands too large");
-    return renderLaunch(scene, camera, params, width, height, samples_sqrt, 0, uint32_t(mine * bandPixels), uint32_t(bandPixels), first_band,
-            band_stride, frame_device, counters_device, hip_stream);
+    LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, 0, uint32_t(mine * bandPixels), frame_device, hip_stream };
+    rq.bandPixels = uint32_t(bandPixels);
+    rq.bandFirst = first_band;
+    rq.bandStride = band_stride;
+    rq.counters = counters_device;
+    return renderLaunch(rq);
 }
 
 wpt_status wpt_render_bands(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
@@ -1401,22 +1462,10 @@ wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera, const wp
         return fail(WPT_ERR_INVALID_ARGUMENT, "block_rgb is NULL");
     if (block_size == 0)
         return WPT_OK;
-    /* a frame-sized address space would waste memory for small blocks: allocate the block only
-     * and bias the frame pointer so that pixel `block_start` lands at offset 0 */
-    float* dBlock = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), size_t(block_size) * 3 * sizeof(float)));
-    float* biased = dBlock - size_t(block_start) * 3;
-    wpt_status st = wpt_render_block_device(scene, camera, params, width, height, samples_sqrt, block_start, block_size,
-            biased, nullptr, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(scene);
-    if (st == WPT_OK) {
-        hipError_t e = hipMemcpy(block_rgb, dBlock, size_t(block_size) * 3 * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dBlock);
-    return st;
+    StagedBlock block;
+    HIP_TRY(block.allocatePixels(block_size));
+    return finishStaged(wpt_render_block_device(scene, camera, params, width, height, samples_sqrt, block_start, block_size,
+            block.biased(block_start), nullptr, nullptr), scene, block, block_rgb);
 }
 
 } /* extern "C" */
@@ -1492,21 +1541,12 @@ wpt_status wpt_progress_begin(wpt_scene* scene, const wpt_camera* camera, const 
         return fail(WPT_ERR_NO_DEVICE, "no HIP device is available; the path tracer has no CPU fallback");
     if (!scene || !camera || !params || !out_progress)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    if (block_size == 0 || uint64_t(block_start) + block_size > uint64_t(width) * height)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block is empty or lies outside the frame");
+    WPT_TRY(checkFrameBlock(width, height, &samples_sqrt, block_start, block_size, 1, "", true));
     /* the arguments and the kernel of the plain frame launch without counters, set up by what renderLaunch sets them up with */
-    wpt_progress* p = new wpt_progress;
+    wpt_progress* p = new wpt_progress{}; /* (zeros: no row done, no memory yet, the null stream) */
     p->scene = scene;
-    p->rowsDone = 0;
     p->tag = tag;
-    p->carry = nullptr;
-    p->cost = p->order = p->work = nullptr;
-    p->frameOrderBuilt = false;
-    p->lastStream = nullptr;
     KernelArgs& args = p->args;
-    memset(&args, 0, sizeof(args));
     uint32_t need = 0;
     const wpt_status setUp = launchSetUp(scene, camera, 1, false, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0, false, args, need);
     if (setUp != WPT_OK) {
@@ -1525,7 +1565,7 @@ wpt_status wpt_progress_begin(wpt_scene* scene, const wpt_camera* camera, const 
     /* hipMalloc, not stream-ordered: the memory outlives the calls.  Carry and cost start as zeros: a state saved before the
      * first stage is defined, and so is the order that a restored session builds from times it never measured. */
     const size_t pixels = size_t(width) * height;
-    const size_t workBytes = (3 * wptk::ORDER_BUCKETS + 1) * sizeof(uint32_t);
+    const size_t workBytes = ORDER_WORK_WORDS * sizeof(uint32_t);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->carry), pixels * 2 * sizeof(float4));
     if (e == hipSuccess)
         e = hipMalloc(reinterpret_cast<void**>(&p->cost), pixels * sizeof(uint32_t));
@@ -1565,38 +1605,23 @@ wpt_status wpt_progress_advance_device(wpt_progress* p, uint32_t rows, float* fr
     stage.frame = frame_device;
     stage.rowStop = rowStop;
     stage.schedStats = nullptr;
-    if (p->rowsDone > 0) {
-        /* a stage that resumes takes its pixels from `order` and loads what they carry: the frame's own order for the scene
-         * in LDS (any other costs those kernels more than it gains), the tiles that took the stage before longest first for
-         * the scene in HBM, as the second of the one-shot launch's two passes does */
-        if (p->choice.sceneInLds) {
-            if (!p->frameOrderBuilt)
-                wptk::launchProgressFrameOrder(p->args, p->order, p->work + 3 * wptk::ORDER_BUCKETS, stream);
-            p->frameOrderBuilt = true;
-        } else {
-            wptk::launchOrderBuild(p->args, p->order, p->work, stream);
-        }
+    if (p->rowsDone > 0 && !p->choice.sceneInLds) {
+        /* a stage that resumes takes its pixels from `order` and loads what they carry: for the scene in HBM the tiles that
+         * took the stage before longest first, as the second of the one-shot launch's two passes does */
+        orderByCost(p->args, p->order, p->work, stream, stage);
+    } else if (p->rowsDone > 0) {
+        /* ... and the frame's own order for the scene in LDS (any other costs those kernels more than it gains) */
+        if (!p->frameOrderBuilt)
+            wptk::launchProgressFrameOrder(p->args, p->order, p->work + ORDER_WORK_WORDS - 1, stream);
+        p->frameOrderBuilt = true;
         stage.order = p->order;
-        stage.orderCount = p->work + 3 * wptk::ORDER_BUCKETS;
+        stage.orderCount = p->work + ORDER_WORK_WORDS - 1;
     }
-    /* the pixel pool, as renderLaunch uses it */
-    dim3 grid((p->args.blockSize + WG - 1) / WG);
-    uint32_t* pool = nullptr;
-    const bool pooled = !(g_variant & 0x10u) && p->args.blockSize < 0x80000000u && grid.x > p->args.cuCount;
-    if (pooled && hipMallocAsync(reinterpret_cast<void**>(&pool), sizeof(uint32_t), stream) != hipSuccess) {
-        (void)hipGetLastError();
-        pool = nullptr;
-    }
-    stage.pool = pool;
-    g_kernelName.store(p->kernel->name, std::memory_order_relaxed);
-    g_kernelForm.store(kernelForm(p->choice), std::memory_order_relaxed);
-    g_lastSliceStats.store(nullptr, std::memory_order_relaxed);
-    p->kernel->launch(stage, grid, p->choice.sceneLdsBytes, stream);
-    g_lastPasses.store(1u, std::memory_order_relaxed);
-    const hipError_t launched = hipGetLastError();
-    if (pool)
-        (void)hipFreeAsync(pool, stream);
-    HIP_TRY(launched);
+    /* planned as a frame launch without counters (with the variant word of this moment) whose strategy the session has fixed:
+     * one pass, in the order set up above */
+    const bool pooled = wptk::planLaunch({ wptk::SENSOR_FRAME, false, false, false, p->choice.sceneInLds, stage.blockSize, total, stage.cuCount,
+            g_variant, 2u, 1u }).pooled;
+    HIP_TRY(runSingleKernel(stage, p->choice, p->kernel, nullptr, { false, false, pooled, wptk::ONE_PASS, 1, total, 1 }, stream));
     /* The launch that renders the last row writes the frame and stores no carry.  A finished session keeps the block's pixels
      * of its frame in the carry's place instead, so that its preview and its saved state still yield the frame. */
     if (rowStop == total) {
@@ -1616,20 +1641,10 @@ wpt_status wpt_progress_advance(wpt_progress* p, uint32_t rows, float* block_rgb
     const bool finishes = rows > 0 && p->rowsDone < total && rows >= total - p->rowsDone;
     if (finishes && !block_rgb)
         return fail(WPT_ERR_INVALID_ARGUMENT, "the stage that finishes the frame needs block_rgb: it is NULL");
-    float* dBlock = nullptr;
+    StagedBlock block;
     if (finishes)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), size_t(p->args.blockSize) * 3 * sizeof(float)));
-    wpt_status st = wpt_progress_advance_device(p, rows, finishes ? dBlock - size_t(p->args.blockStart) * 3 : nullptr, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(p->scene);
-    if (st == WPT_OK && finishes) {
-        hipError_t e = hipMemcpy(block_rgb, dBlock, size_t(p->args.blockSize) * 3 * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    if (dBlock)
-        (void)hipFree(dBlock);
-    return st;
+        HIP_TRY(block.allocatePixels(p->args.blockSize));
+    return finishStaged(wpt_progress_advance_device(p, rows, block.biased(p->args.blockStart), nullptr), p->scene, block, block_rgb);
 }
 
 uint32_t wpt_progress_rows_done(const wpt_progress* p)
@@ -1660,17 +1675,10 @@ wpt_status wpt_progress_preview(wpt_progress* p, float* block_rgb)
 {
     if (!p || !block_rgb)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    float* dBlock = nullptr;
+    StagedBlock block;
     HIP_TRY(hipStreamSynchronize(p->lastStream));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), size_t(p->args.blockSize) * 3 * sizeof(float)));
-    wpt_status st = wpt_progress_preview_device(p, dBlock - size_t(p->args.blockStart) * 3, nullptr);
-    if (st == WPT_OK) {
-        hipError_t e = hipMemcpy(block_rgb, dBlock, size_t(p->args.blockSize) * 3 * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dBlock);
-    return st;
+    HIP_TRY(block.allocatePixels(p->args.blockSize));
+    return finishStaged(wpt_progress_preview_device(p, block.biased(p->args.blockStart), nullptr), nullptr, block, block_rgb);
 }
 
 void wpt_progress_end(wpt_progress* p)
@@ -1790,108 +1798,57 @@ wpt_status transientEdges(const float* edges, uint32_t binCount, wptk::BinsView&
     return WPT_OK;
 }
 
-/* one transient launch: the planes' block is zeroed, rendered into and scaled, all in stream order; `bins` is plane 0's
- * pixel 0 with `stride` floats between planes (a full frame's, or a block's behind a biased pointer) */
+/* One launch into planes of accumulated values, the transient film's or the time-of-flight sensor's.  `table`, the sensor's
+ * words, goes to the device as rq.bins.edges; where the kernels accumulate into the planes (`accumulated`), the planes' block is
+ * zeroed before the render and scaled by 1 / samples behind it, all in stream order.  rq.bins.bins is plane 0's pixel 0 with
+ * rq.bins.stride floats between planes (a full frame's, or a block's behind a biased pointer); what: the sensor, for messages. */
+wpt_status planesLaunch(LaunchRequest rq, const float* table, size_t tableFloats, bool accumulated, const char* what)
+{
+    const wptk::BinsView& bv = rq.bins;
+    hipStream_t stream = static_cast<hipStream_t>(rq.stream);
+    float* dTable = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dTable), tableFloats * sizeof(float), stream));
+    hipError_t e = hipMemcpyAsync(dTable, table, tableFloats * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && accumulated)
+        e = hipMemset2DAsync(bv.bins + size_t(rq.blockStart) * 3, bv.stride * sizeof(float), 0, size_t(rq.blockSize) * 3 * sizeof(float), bv.binCount,
+                stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(dTable, stream);
+        return fail(WPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    rq.bins.edges = dTable;
+    wpt_status st = renderLaunch(rq);
+    if (st == WPT_OK && accumulated) {
+        const uint64_t n = uint64_t(rq.blockSize) * 3 * bv.binCount;
+        const uint32_t blocks = uint32_t(std::min<uint64_t>((n + 255) / 256, 65536));
+        hipLaunchKernelGGL(wpt_transient_finish_kernel, dim3(blocks), dim3(256), 0, stream, bv.bins, bv.stride, rq.blockStart, rq.blockSize,
+                bv.binCount, 1.0f / float(rq.samplesSqrt * rq.samplesSqrt));
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    (void)hipFreeAsync(dTable, stream);
+    return st;
+}
+
+/* one transient launch; `bins` and `stride` as planesLaunch takes them */
 wpt_status transientLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const float* edges, uint32_t binCount,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* frame, float* bins,
         size_t stride, hipStream_t stream)
 {
-    wptk::BinsView bv;
-    const wpt_status checked = transientEdges(edges, binCount, bv);
-    if (checked != WPT_OK)
-        return checked;
+    LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, block_start, block_size, frame, stream };
+    WPT_TRY(transientEdges(edges, binCount, rq.bins));
     if (!scene || !camera || !params || !bins)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    if (uint64_t(width) * height > 0xffffffffull || uint64_t(block_start) + block_size > uint64_t(width) * height)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
-    if (block_size == 0)
-        return WPT_OK;
-    float* dEdges = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dEdges), (size_t(binCount) + 1) * sizeof(float), stream));
-    hipError_t e = hipMemcpyAsync(dEdges, edges, (size_t(binCount) + 1) * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-        e = hipMemset2DAsync(bins + size_t(block_start) * 3, stride * sizeof(float), 0, size_t(block_size) * 3 * sizeof(float), binCount, stream);
-    if (e != hipSuccess) {
-        (void)hipFreeAsync(dEdges, stream);
-        return fail(WPT_ERR_HIP, std::string("transient film: ") + hipGetErrorString(e));
-    }
-    bv.edges = dEdges;
-    bv.bins = bins;
-    bv.stride = stride;
-    bv.width = width;
-    wpt_status st = renderLaunch(scene, camera, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0, frame, nullptr,
-            stream, &bv);
-    if (st == WPT_OK) {
-        const uint64_t n = uint64_t(block_size) * 3 * binCount;
-        const uint32_t blocks = uint32_t(std::min<uint64_t>((n + 255) / 256, 65536));
-        hipLaunchKernelGGL(wpt_transient_finish_kernel, dim3(blocks), dim3(256), 0, stream, bins, stride, block_start, block_size, binCount,
-                1.0f / float(samples_sqrt * samples_sqrt));
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("transient film: ") + hipGetErrorString(e));
-    }
-    (void)hipFreeAsync(dEdges, stream);
-    return st;
+    const wpt_status inFrame = checkFrameBlock(width, height, &samples_sqrt, block_start, block_size);
+    if (inFrame != WPT_OK || block_size == 0)
+        return inFrame;
+    rq.sensor = wptk::SENSOR_TRANSIENT;
+    rq.bins.bins = bins;
+    rq.bins.stride = stride;
+    rq.bins.width = width;
+    return planesLaunch(rq, edges, size_t(binCount) + 1, true, "transient film");
 }
-
-} /* namespace */
-
-extern "C" {
-
-wpt_status wpt_render_transient_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
-        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
-        uint32_t block_size, float* frame_device, float* bins_device, void* hip_stream)
-{
-    return transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
-            frame_device, bins_device, size_t(width) * height * 3, static_cast<hipStream_t>(hip_stream));
-}
-
-wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
-        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
-        uint32_t block_size, float* block_rgb, float* block_bins)
-{
-    wptk::BinsView bv;
-    const wpt_status checked = transientEdges(edges_host, bin_count, bv);
-    if (checked != WPT_OK)
-        return checked;
-    if (!block_bins)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "block_bins is NULL");
-    if (block_size == 0)
-        return WPT_OK;
-    /* device memory for the block only, behind pointers biased so that pixel `block_start` lands at offset 0 */
-    const size_t blockFloats = size_t(block_size) * 3;
-    float *dBlock = nullptr, *dBins = nullptr;
-    if (block_rgb)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dBlock), blockFloats * sizeof(float)));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBins), blockFloats * bin_count * sizeof(float));
-    wpt_status st = e == hipSuccess ? WPT_OK : fail(WPT_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (st == WPT_OK)
-        st = transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
-                dBlock ? dBlock - size_t(block_start) * 3 : nullptr, dBins - size_t(block_start) * 3, blockFloats, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(scene);
-    if (st == WPT_OK && block_rgb) {
-        e = hipMemcpy(block_rgb, dBlock, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    if (st == WPT_OK) {
-        e = hipMemcpy(block_bins, dBins, blockFloats * bin_count * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    if (dBlock)
-        (void)hipFree(dBlock);
-    if (dBins)
-        (void)hipFree(dBins);
-    return st;
-}
-
-} /* extern "C" */
-
-namespace {
 
 /* what a batch of views is refused for before anything needs the scene or a device */
 wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void* frames, uint32_t width, uint32_t height)
@@ -1911,70 +1868,6 @@ wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void*
     return WPT_OK;
 }
 
-} /* namespace */
-
-extern "C" {
-
-wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
-        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device, void* hip_stream)
-{
-    const wpt_status checked = viewsCheck(cameras_host, view_count, frames_device, width, height);
-    if (checked != WPT_OK)
-        return checked;
-    if (!scene || !params)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (uint32_t v = 0; v < view_count; v++)
-        if (cameras_host[v].animation >= int32_t(scene->animationCount))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
-    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    /* the cameras go to device memory once per batch, in stream order */
-    const size_t camBytes = size_t(view_count) * sizeof(wpt_camera);
-    wpt_camera* dCams = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dCams), camBytes, stream));
-    const hipError_t e = hipMemcpyAsync(dCams, cameras_host, camBytes, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) {
-        (void)hipFreeAsync(dCams, stream);
-        return fail(WPT_ERR_HIP, std::string("views: ") + hipGetErrorString(e));
-    }
-    wptk::ViewsView vv;
-    vv.cams = dCams;
-    vv.viewPixels = width * height;
-    vv.viewCount = view_count;
-    const wpt_status st = renderLaunch(scene, cameras_host, params, width, height, samples_sqrt, 0, view_count * width * height, 0, 0, 0,
-            frames_device, counters_device, hip_stream, nullptr, &vv);
-    (void)hipFreeAsync(dCams, stream);
-    return st;
-}
-
-wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
-        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
-{
-    const wpt_status checked = viewsCheck(cameras_host, view_count, frames_host, width, height);
-    if (checked != WPT_OK)
-        return checked;
-    if (!scene)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    const size_t bytes = size_t(view_count) * width * height * 3 * sizeof(float);
-    float* dFrames = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dFrames), bytes));
-    wpt_status st = wpt_render_views_device(scene, cameras_host, view_count, params, width, height, samples_sqrt, dFrames, nullptr, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(scene);
-    if (st == WPT_OK) {
-        const hipError_t e = hipMemcpy(frames_host, dFrames, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dFrames);
-    return st;
-}
-
-} /* extern "C" */
-
-namespace {
-
 /* what an adaptive render is refused for before anything needs the scene or a device (every 16-bit count is valid) */
 wpt_status adaptiveCheck(uint32_t width, uint32_t height, const void* map, uint32_t blockStart, uint32_t blockSize, const void* frame)
 {
@@ -1982,80 +1875,8 @@ wpt_status adaptiveCheck(uint32_t width, uint32_t height, const void* map, uint3
         return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: the sample-count map is NULL");
     if (!frame)
         return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: the frame is NULL");
-    if (width == 0 || height == 0 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: width and height must lie in 1 .. 65535");
-    if (uint64_t(blockStart) + blockSize > uint64_t(width) * height)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "adaptive: pixel block lies outside the frame");
-    return WPT_OK;
+    return checkFrameBlock(width, height, nullptr, blockStart, blockSize, 1, "adaptive: ");
 }
-
-} /* namespace */
-
-extern "C" {
-
-wpt_status wpt_render_adaptive_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
-        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_device, uint32_t block_start, uint32_t block_size,
-        float* frame_device, float* moments_device, void* hip_stream)
-{
-    const wpt_status checked = adaptiveCheck(width, height, samples_sqrt_device, block_start, block_size, frame_device);
-    if (checked != WPT_OK)
-        return checked;
-    wptk::AdaptiveView av;
-    av.samplesSqrt = samples_sqrt_device;
-    av.moments = moments_device;
-    /* (the launch's own samples_sqrt is unused by the adaptive kernels: 1 passes renderLaunch's checks) */
-    return renderLaunch(scene, camera, params, width, height, 1, block_start, block_size, 0, 0, 0, frame_device, nullptr, hip_stream,
-            nullptr, nullptr, &av);
-}
-
-wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
-        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_host, uint32_t block_start, uint32_t block_size,
-        float* block_rgb, float* block_moments)
-{
-    const wpt_status checked = adaptiveCheck(width, height, samples_sqrt_host, block_start, block_size, block_rgb);
-    if (checked != WPT_OK)
-        return checked;
-    if (block_size == 0)
-        return WPT_OK;
-    /* device memory for the block only, behind pointers biased so that pixel `block_start` lands at offset 0; the caller's
-     * values go there first, so that the pixels with n = 0 come back as they were */
-    const size_t blockFloats = size_t(block_size) * 3;
-    uint16_t* dMap = nullptr;
-    float *dBlock = nullptr, *dMoments = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dMap), size_t(block_size) * sizeof(uint16_t));
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&dBlock), blockFloats * sizeof(float));
-    if (e == hipSuccess && block_moments)
-        e = hipMalloc(reinterpret_cast<void**>(&dMoments), blockFloats * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMemcpy(dMap, samples_sqrt_host + block_start, size_t(block_size) * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(dBlock, block_rgb, blockFloats * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && block_moments)
-        e = hipMemcpy(dMoments, block_moments, blockFloats * sizeof(float), hipMemcpyHostToDevice);
-    wpt_status st = e == hipSuccess ? WPT_OK
-            : fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("adaptive: ") + hipGetErrorString(e));
-    if (st == WPT_OK)
-        st = wpt_render_adaptive_block_device(scene, camera, params, width, height, dMap - block_start, block_start, block_size,
-                dBlock - size_t(block_start) * 3, dMoments ? dMoments - size_t(block_start) * 3 : nullptr, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(scene);
-    if (st == WPT_OK) {
-        e = hipMemcpy(block_rgb, dBlock, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && block_moments)
-            e = hipMemcpy(block_moments, dMoments, blockFloats * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    for (void* p : { static_cast<void*>(dMap), static_cast<void*>(dBlock), static_cast<void*>(dMoments) })
-        if (p)
-            (void)hipFree(p);
-    return st;
-}
-
-} /* extern "C" */
-
-namespace {
 
 /* refuses a bad time-of-flight call before a device is needed */
 wpt_status tofCheck(const void* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor, const void* planes)
@@ -2084,15 +1905,10 @@ wpt_status tofLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_param
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* planes, size_t stride,
         hipStream_t stream)
 {
-    const wpt_status checked = tofCheck(scene, camera, params, sensor, planes);
-    if (checked != WPT_OK)
-        return checked;
-    if (width == 0 || height == 0 || samples_sqrt == 0 || samples_sqrt > 65535 || width > 65535 || height > 65535)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "width, height and samples_sqrt must lie in 1 .. 65535");
-    if (uint64_t(width) * height > 0xffffffffull || uint64_t(block_start) + block_size > uint64_t(width) * height)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "pixel block lies outside the frame");
-    if (block_size == 0)
-        return WPT_OK;
+    WPT_TRY(tofCheck(scene, camera, params, sensor, planes));
+    const wpt_status inFrame = checkFrameBlock(width, height, &samples_sqrt, block_start, block_size);
+    if (inFrame != WPT_OK || block_size == 0)
+        return inFrame;
     const uint32_t phases = sensor->phase_count;
     float consts[wpttof::C_TAU + WPT_TOF_MAX_PHASES] = {};
     consts[wpttof::C_PIXEL_AREA] = sensor->pixel_area;
@@ -2101,39 +1917,127 @@ wpt_status tofLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_param
     consts[wpttof::C_FRAC_MODFREQ_C] = sensor->frac_modfreq_c;
     for (uint32_t j = 0; j < phases; j++)
         consts[wpttof::C_TAU + j] = sensor->tau[j];
-    float* dConsts = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dConsts), sizeof(consts), stream));
-    hipError_t e = hipMemcpyAsync(dConsts, consts, sizeof(consts), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && phases > 1)
-        e = hipMemset2DAsync(planes + size_t(block_start) * 3, stride * sizeof(float), 0, size_t(block_size) * 3 * sizeof(float), phases, stream);
-    if (e != hipSuccess) {
-        (void)hipFreeAsync(dConsts, stream);
-        return fail(WPT_ERR_HIP, std::string("time-of-flight sensor: ") + hipGetErrorString(e));
-    }
-    wptk::BinsView bv = wptk::BinsView{};
-    bv.edges = dConsts;
-    bv.bins = planes;
-    bv.stride = stride;
-    bv.binCount = phases;
-    bv.width = width;
-    wpt_status st = renderLaunch(scene, camera, params, width, height, samples_sqrt, block_start, block_size, 0, 0, 0,
-            phases == 1 ? planes : nullptr, nullptr, stream, &bv, nullptr, nullptr, true);
-    if (st == WPT_OK && phases > 1) {
-        const uint64_t n = uint64_t(block_size) * 3 * phases;
-        const uint32_t blocks = uint32_t(std::min<uint64_t>((n + 255) / 256, 65536));
-        hipLaunchKernelGGL(wpt_transient_finish_kernel, dim3(blocks), dim3(256), 0, stream, planes, stride, block_start, block_size, phases,
-                1.0f / float(samples_sqrt * samples_sqrt));
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("time-of-flight sensor: ") + hipGetErrorString(e));
-    }
-    (void)hipFreeAsync(dConsts, stream);
-    return st;
+    LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, block_start, block_size, phases == 1 ? planes : nullptr, stream };
+    rq.sensor = wptk::SENSOR_TOF;
+    rq.bins.bins = planes;
+    rq.bins.stride = stride;
+    rq.bins.binCount = phases;
+    rq.bins.width = width;
+    return planesLaunch(rq, consts, sizeof(consts) / sizeof(consts[0]), phases > 1, "time-of-flight sensor");
 }
 
 } /* namespace */
 
 extern "C" {
+
+wpt_status wpt_render_transient_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
+        uint32_t block_size, float* frame_device, float* bins_device, void* hip_stream)
+{
+    return transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
+            frame_device, bins_device, size_t(width) * height * 3, static_cast<hipStream_t>(hip_stream));
+}
+
+wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const float* edges_host, uint32_t bin_count, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start,
+        uint32_t block_size, float* block_rgb, float* block_bins)
+{
+    wptk::BinsView bv;
+    WPT_TRY(transientEdges(edges_host, bin_count, bv));
+    if (!block_bins)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "block_bins is NULL");
+    if (block_size == 0)
+        return WPT_OK;
+    StagedBlock block, bins;
+    if (block_rgb)
+        HIP_TRY(block.allocatePixels(block_size));
+    const hipError_t e = bins.allocatePixels(block_size, bin_count);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return finishStaged(transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
+            block.biased(block_start), bins.biased(block_start), size_t(block_size) * 3, nullptr), scene, block, block_rgb, &bins, block_bins);
+}
+
+wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device, void* hip_stream)
+{
+    WPT_TRY(viewsCheck(cameras_host, view_count, frames_device, width, height));
+    if (!scene || !params)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t v = 0; v < view_count; v++)
+        if (cameras_host[v].animation >= int32_t(scene->animationCount))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
+    WPT_TRY(checkFrameBlock(width, height, &samples_sqrt, 0, 0));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    /* the cameras go to device memory once per batch, in stream order */
+    const size_t camBytes = size_t(view_count) * sizeof(wpt_camera);
+    wpt_camera* dCams = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dCams), camBytes, stream));
+    const hipError_t e = hipMemcpyAsync(dCams, cameras_host, camBytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(dCams, stream);
+        return fail(WPT_ERR_HIP, std::string("views: ") + hipGetErrorString(e));
+    }
+    LaunchRequest rq = { scene, cameras_host, params, width, height, samples_sqrt, 0, view_count * width * height, frames_device, hip_stream };
+    rq.counters = counters_device;
+    rq.sensor = wptk::SENSOR_VIEWS;
+    rq.views = { dCams, width * height, view_count };
+    const wpt_status st = renderLaunch(rq);
+    (void)hipFreeAsync(dCams, stream);
+    return st;
+}
+
+wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
+{
+    WPT_TRY(viewsCheck(cameras_host, view_count, frames_host, width, height));
+    if (!scene)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    StagedBlock frames;
+    HIP_TRY(frames.allocatePixels(size_t(view_count) * width * height));
+    return finishStaged(wpt_render_views_device(scene, cameras_host, view_count, params, width, height, samples_sqrt, frames.biased(0), nullptr,
+            nullptr), scene, frames, frames_host);
+}
+
+wpt_status wpt_render_adaptive_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_device, uint32_t block_start, uint32_t block_size,
+        float* frame_device, float* moments_device, void* hip_stream)
+{
+    WPT_TRY(adaptiveCheck(width, height, samples_sqrt_device, block_start, block_size, frame_device));
+    /* (the launch's own samples_sqrt is unused by the adaptive kernels: 1 passes renderLaunch's checks) */
+    LaunchRequest rq = { scene, camera, params, width, height, 1, block_start, block_size, frame_device, hip_stream };
+    rq.sensor = wptk::SENSOR_ADAPTIVE;
+    rq.adaptive = { samples_sqrt_device, moments_device };
+    return renderLaunch(rq);
+}
+
+wpt_status wpt_render_adaptive_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, const uint16_t* samples_sqrt_host, uint32_t block_start, uint32_t block_size,
+        float* block_rgb, float* block_moments)
+{
+    WPT_TRY(adaptiveCheck(width, height, samples_sqrt_host, block_start, block_size, block_rgb));
+    if (block_size == 0)
+        return WPT_OK;
+    /* device memory for the block only, behind pointers biased so that pixel `block_start` lands at offset 0; the caller's
+     * values go there first, so that the pixels with n = 0 come back as they were */
+    StagedBlock map, block, moments;
+    hipError_t e = map.allocate(size_t(block_size) * sizeof(uint16_t));
+    if (e == hipSuccess)
+        e = block.allocatePixels(block_size);
+    if (e == hipSuccess && block_moments)
+        e = moments.allocatePixels(block_size);
+    if (e == hipSuccess)
+        e = map.upload(samples_sqrt_host + block_start);
+    if (e == hipSuccess)
+        e = block.upload(block_rgb);
+    if (e == hipSuccess && block_moments)
+        e = moments.upload(block_moments);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("adaptive: ") + hipGetErrorString(e));
+    return finishStaged(wpt_render_adaptive_block_device(scene, camera, params, width, height, static_cast<uint16_t*>(map.device) - block_start,
+            block_start, block_size, block.biased(block_start), moments.biased(block_start), nullptr), scene,
+            block, block_rgb, &moments, block_moments);
+}
 
 wpt_status wpt_render_tof_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* planes_device,
@@ -2146,26 +2050,13 @@ wpt_status wpt_render_tof_block_device(wpt_scene* scene, const wpt_camera* camer
 wpt_status wpt_render_tof_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_tof_sensor* sensor,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_planes)
 {
-    const wpt_status checked = tofCheck(scene, camera, params, sensor, block_planes);
-    if (checked != WPT_OK)
-        return checked;
+    WPT_TRY(tofCheck(scene, camera, params, sensor, block_planes));
     if (block_size == 0)
         return WPT_OK;
-    /* device memory for the block only, behind a pointer biased so that pixel `block_start` lands at offset 0 */
-    const size_t blockFloats = size_t(block_size) * 3;
-    float* dPlanes = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dPlanes), blockFloats * sensor->phase_count * sizeof(float)));
-    wpt_status st = tofLaunch(scene, camera, params, sensor, width, height, samples_sqrt, block_start, block_size,
-            dPlanes - size_t(block_start) * 3, blockFloats, nullptr);
-    if (st == WPT_OK)
-        st = wpt_scene_check(scene);
-    if (st == WPT_OK) {
-        const hipError_t e = hipMemcpy(block_planes, dPlanes, blockFloats * sensor->phase_count * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            st = fail(WPT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dPlanes);
-    return st;
+    StagedBlock planes;
+    HIP_TRY(planes.allocatePixels(block_size, sensor->phase_count));
+    return finishStaged(tofLaunch(scene, camera, params, sensor, width, height, samples_sqrt, block_start, block_size, planes.biased(block_start),
+            size_t(block_size) * 3, nullptr), scene, planes, block_planes);
 }
 
 wpt_status wpt_tof_accumulate_host(const wpt_tof_sensor* sensor, uint32_t phase, float radiance_w, float opl_w, int is_tof_light, float acc[3])
@@ -2308,26 +2199,7 @@ wpt_status wpt_slices_plan(uint32_t block_size, uint32_t lanes_at_once, uint32_t
 {
     if (!units || !rows)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    /* as for two passes: with fewer than 2 pixels per lane the launch has no end to shorten, with more than 64 its end is a
-     * small part of it; a pixel of fewer than 8 rows of strata is a small unit already */
-    *units = 1;
-    *rows = samples_sqrt > 0 ? samples_sqrt : 1u;
-    if (lanes_at_once == 0 || samples_sqrt < 8 || uint64_t(block_size) < 2ull * lanes_at_once || uint64_t(block_size) > 64ull * lanes_at_once)
-        return WPT_OK;
-    /* What the units buy is the end of the launch, which is a share of the frame's time that falls with the pixels per lane
-     * (10 % at 4, measured); what they cost is a write-back and an invalidation of the L2 per unit, 1 to 2 ns of the launch
-     * each.  With the frame's time per sample (0.77 ns) the difference is largest at about samples_sqrt * sqrt(0.5 / pixels
-     * per lane) units: 11 for the bench frame, 2 at 16 pixels per lane and 256 spp, none at 64 pixels per lane and 64 spp,
-     * which is what those frames measured. */
-    const double perLane = double(block_size) / double(lanes_at_once);
-    uint32_t target = uint32_t(std::sqrt(0.5 * double(samples_sqrt) * double(samples_sqrt) / perLane));
-    target = target > SLICE_UNITS_TARGET ? SLICE_UNITS_TARGET : target;
-    if (target < 2)
-        return WPT_OK;
-    uint32_t r = (samples_sqrt + target - 1) / target;
-    r = r < 2 ? 2 : r;
-    *rows = r;
-    *units = (samples_sqrt + r - 1) / r;
+    wptk::slicesPlan(block_size, lanes_at_once, samples_sqrt, units, rows);
     return WPT_OK;
 }
 
@@ -2346,13 +2218,29 @@ wpt_status wpt_kernel_choice(uint32_t need, uint32_t sensor, uint32_t count, uin
     if (found != WPT_OK)
         return found;
     *name = kernel->name;
-    *form = kernelForm(choice);
+    *form = kernelForm(choice.rotated);
     key[0] = kernel->features;
     key[1] = kernel->count;
     key[2] = kernel->ldsScene;
     key[3] = kernel->wide;
     *scene_lds_bytes = choice.sceneLdsBytes;
     *materials_in_lds = choice.materialsInLds;
+    return WPT_OK;
+}
+
+wpt_status wpt_launch_plan(uint32_t sensor, uint32_t count, uint32_t need, uint32_t scene_in_lds, uint32_t block_size, uint32_t samples_sqrt,
+        uint32_t cu_count, uint32_t variant, uint32_t wavefront_mode, uint32_t slices, uint32_t plan[WPT_PLAN_WORDS])
+{
+    if (!plan)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sensor >= wptk::SENSOR_COUNT)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "sensor: 0 frame, 1 transient, 2 views, 3 adaptive, 4 time of flight");
+    if (wavefront_mode > 2u)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "wavefront mode must be 0, 1 or 2");
+    const wptk::LaunchPlan p = wptk::planLaunch({ sensor, count != 0, (need & FEAT_RGL) != 0, (need & FEAT_ANIM) != 0, scene_in_lds != 0,
+            block_size, samples_sqrt, cu_count, variant, wavefront_mode, slices });
+    const uint32_t words[WPT_PLAN_WORDS] = { p.wavefront, p.wavefrontFallBack, p.pooled, p.strategy, p.units, p.rows, p.passes };
+    memcpy(plan, words, sizeof(words));
     return WPT_OK;
 }
 

@@ -25,7 +25,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
            "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
            "wpt_progress_save", "wpt_progress_restore", "wpt_progress_state_info",
@@ -288,6 +288,23 @@ def kernel_table():
     while L.wpt_kernel_table_entry(len(rows), key, C.byref(name)) == _abi.WPT_OK:
         rows.append(((key[0], bool(key[1]), bool(key[2]), bool(key[3])), name.value.decode()))
     return rows
+
+
+STRATEGIES = ("one pass", "two passes", "adaptive order", "sliced")  # WPT_STRATEGY_*
+PLAN_WORDS = ("wavefront", "wavefront_falls_back", "pooled", "strategy", "units", "rows", "passes")  # WPT_PLAN_*, WPT_PLAN_WORDS of them
+
+
+def launch_plan(sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_count, variant=0, wavefront_mode=0, slices=0):
+    """wpt_launch_plan: which passes render such a launch, as a dict: wavefront, wavefront_falls_back, pooled (bools), strategy (one of
+    STRATEGIES), units, rows, passes; needs no device"""
+    w = (C.c_uint32 * len(PLAN_WORDS))()
+    _check(lib().wpt_launch_plan(*[C.c_uint32(int(v)) for v in (sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_count, variant,
+                                                                wavefront_mode, slices)], w))
+    plan = dict(zip(PLAN_WORDS, (int(v) for v in w)))
+    for k in ("wavefront", "wavefront_falls_back", "pooled"):
+        plan[k] = bool(plan[k])
+    plan["strategy"] = STRATEGIES[plan["strategy"]]
+    return plan
 
 
 def last_slice_stats():
