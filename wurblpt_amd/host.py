@@ -193,6 +193,23 @@ def random_triangles(n, seed, width, height, with_texcoords=True, aperture=0.0):
     return HostScene(h, width, height, "random_triangles(%d,%d)" % (n, seed))
 
 
+def lds_edge_scene(triangles, materials, light=0, seed=1, width=40, height=32):
+    """A lit, closed room with seeded clutter for the capacity edges of the kernels that keep the scene in LDS: tri_count is
+    exactly `triangles` (>= 14: 12 of the room, 2 of the ceiling light, the rest clutter with edges 0.2 to 0.6 of the room's),
+    node_count 2 * triangles - 1 and material_count exactly `materials`.  light 0: a LightDiffuse, one record; 1: a LightSpot
+    and 2: a LightTof, each the front side of a MaterialTwoSided with a black back side -- three records (front, back, then the
+    wrapper, which is the record the light's triangles name), all counted in `materials`.  The K = materials - 1 (or - 3)
+    records in front of the light's are the surfaces': Lambertians of pairwise different colours, with K >= 3 record K - 2 a
+    GGX and K - 3 a glass record.  Clutter triangle c has record K - 1 - c % K and the room's quads go on from there, so the
+    highest records are the ones in use and, where there are more records than surfaces, the low ones belong to no triangle.
+    Lights 1 and 2 make twins: the same geometry and records but for the light's front side."""
+    L = lib()
+    L.wpt_host_lds_edge_scene.restype = C.c_void_p
+    L.wpt_host_lds_edge_scene.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_uint, C.c_uint]
+    h = L.wpt_host_lds_edge_scene(triangles, materials, light, seed, width, height)
+    return HostScene(h, width, height, "lds_edge_scene(%d,%d,light=%d,seed=%d)" % (triangles, materials, light, seed))
+
+
 def sponza_like(width, height, seed=1, detail=1.0, tex_size=1024, env_width=2048, importance_n=512):
     """BASELINE config 3 stand-in: seeded Sponza-class courtyard (about 262 k triangles at
     detail 1.0), textured Lambertian / ModPhong / two-sided / GGX / mirror materials, normal

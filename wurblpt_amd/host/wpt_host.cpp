@@ -222,6 +222,171 @@ void buildStage(Scene& scene)
     scene.take(new Sphere(vec3(1.8f, 2.2f, 0.2f), 0.12f, amber), HotSpot);
 }
 
+/* Scenes for the capacity edges of the kernels that keep the scene in LDS (tests/test_lds_edge_scenes.py): exactly `triangles`
+ * triangles and `materials` flattened material records, every surface lit and in view.
+ *   geometry   the closed room [-1, 1]^3 (6 quads, 12 triangles), a ceiling light (1 quad, the only hot spot) and
+ *              triangles - 14 seeded clutter triangles inside the room whose edges are 0.2 to 0.6 of the room's.  The seed decides
+ *              the clutter alone, whatever the materials and the light.  Whether the tree has first children that repeat their
+ *              parent's box (wpt_fold.h), and at which nodes, is the seed's doing: tests/test_lds_edge_scenes.py states them for
+ *              the seeds it uses
+ *   light      0 LightDiffuse (1 record), 1 MaterialTwoSided(LightSpot, black Lambertian), 2 MaterialTwoSided(LightTof, black
+ *              Lambertian) (3 records: front, back, wrapper -- the wrapper is the record the light's triangles name, the last)
+ *   materials  K = materials - 1 (- 3) surface records 0 .. K - 1: Lambertians of pairwise different colours, with K >= 3
+ *              record K - 2 a GGX and K - 3 a glass record.  Clutter triangle c has record K - 1 - c % K and wall quad q record
+ *              K - 1 - (triangles - 14 + q) % K: the highest records are the ones used, and where there are more records than
+ *              surfaces the low ones belong to no triangle.  With lights 1 and 2 every colour's fourth component is its first
+ *              (the near infrared channel is attenuated like the red one: what tests/test_gpu_tof.py asks of a twin). */
+bool buildLdsEdgeScene(Scene& scene, unsigned int triangles, unsigned int materials, int light, unsigned int seed,
+        std::vector<const Material*>& unusedMaterials, std::string& error)
+{
+    const unsigned int lightRecords = (light == 0 ? 1 : 3);
+    if (triangles < 14 || light < 0 || light > 2 || materials < lightRecords + 1) {
+        error = "lds_edge_scene: at least 14 triangles, a light 0 .. 2 and one material record beside the light's (1, or 3 for lights 1 and 2)";
+        return false;
+    }
+    const unsigned int K = materials - lightRecords;
+    const unsigned int clutter = triangles - 14;
+    const bool nir = (light != 0);
+    std::mt19937 rng(seed);
+    auto u01 = [&rng]() { return float(rng() >> 8) * (1.0f / 16777216.0f); };
+    auto frac = [](float x) { return x - floorf(x); };
+
+    /* surface records: the red channel increases with the record's index, so no two colours are the same */
+    std::vector<Material*> surface(K);
+    for (unsigned int k = 0; k < K; k++) {
+        const vec3 c(0.3f + 0.4f * float(k + 1) / float(K + 1), 0.3f + 0.4f * frac(0.6180340f * k + 0.3f), 0.3f + 0.4f * frac(0.7548777f * k + 0.6f));
+        const vec4 c4(c, c.r());
+        if (K >= 3 && k == K - 2)
+            surface[k] = nir ? new MaterialGGX(c4, vec2(0.15f)) : new MaterialGGX(c, vec2(0.15f));
+        else if (K >= 3 && k == K - 3)
+            surface[k] = nir ? new MaterialGlass(vec4(0.2f), 1.5f) : new MaterialGlass(vec3(0.2f), 1.5f);
+        else
+            surface[k] = nir ? new MaterialLambertian(c4) : new MaterialLambertian(c);
+        scene.take(surface[k]);
+    }
+    Material* lightMaterial;
+    if (light == 0) {
+        lightMaterial = scene.take(new LightDiffuse(vec3(2.0f)));
+    } else {
+        Material* front = light == 1 ? scene.take(new LightSpot(radians(150.0f), vec3(2.0f))) : scene.take(new LightTof(2.0f, radians(150.0f)));
+        Material* back = scene.take(new MaterialLambertian(vec4(0.0f)));
+        lightMaterial = scene.take(new MaterialTwoSided(front, back));
+    }
+
+    /* the triangles of each record; a triangle's three normals are the geometric normal of its winding */
+    struct Bucket {
+        std::vector<vec3> pos, nrm;
+        std::vector<unsigned int> ind;
+    };
+    std::vector<Bucket> buckets(K);
+    auto addTriangle = [](Bucket& b, const vec3& p0, const vec3& p1, const vec3& p2) {
+        const vec3 n = normalize(cross(p1 - p0, p2 - p0));
+        for (const vec3& p : { p0, p1, p2 }) {
+            b.ind.push_back(b.pos.size());
+            b.pos.push_back(p);
+            b.nrm.push_back(n);
+        }
+    };
+    auto recordOf = [K](unsigned int s) { return K - 1 - s % K; };
+
+    const float inside = 0.97f; /* clutter stays off the walls */
+    auto makeTriangle = [&](const vec3& centre, float lo, float hi, vec3 v[3]) {
+        /* two edges of lengths in [lo, hi] from one corner, 50 to 70 degrees apart: the third is at least 2 lo sin(25 degrees) =
+         * 0.845 lo and at most 2 hi sin(35 degrees) = 1.147 hi long */
+        vec3 d1;
+        do
+            d1 = vec3(u01() * 2.0f - 1.0f, u01() * 2.0f - 1.0f, u01() * 2.0f - 1.0f);
+        while (dot(d1, d1) < 0.01f || dot(d1, d1) > 1.0f);
+        d1 = normalize(d1);
+        vec3 h;
+        do
+            h = vec3(u01() * 2.0f - 1.0f, u01() * 2.0f - 1.0f, u01() * 2.0f - 1.0f);
+        while (dot(h, h) < 0.01f || dot(h, h) > 1.0f || fabsf(dot(normalize(h), d1)) > 0.9f);
+        const vec3 e = normalize(h - dot(h, d1) * d1);
+        const float angle = radians(50.0f + 20.0f * u01());
+        const vec3 d2 = cosf(angle) * d1 + sinf(angle) * e;
+        const float l1 = lo + (hi - lo) * u01(), l2 = lo + (hi - lo) * u01();
+        v[0] = centre - (l1 * d1 + l2 * d2) / 3.0f;
+        v[1] = v[0] + l1 * d1;
+        v[2] = v[0] + l2 * d2;
+        /* moved back into the room where it sticks out: a translation keeps the edges */
+        for (int a = 0; a < 3; a++) {
+            const float mn = min(min(v[0][a], v[1][a]), v[2][a]), mx = max(max(v[0][a], v[1][a]), v[2][a]);
+            const float shift = mn < -inside ? -inside - mn : mx > inside ? inside - mx : 0.0f;
+            for (int k = 0; k < 3; k++)
+                v[k][a] += shift;
+        }
+    };
+    /* edges of 0.2 .. 0.6 of the room's 2: two of 0.48 .. 0.62, the third then 0.405 .. 0.712 */
+    for (unsigned int c = 0; c < clutter; c++) {
+        vec3 v[3];
+        /* centres in the room's far two thirds, the camera's end stays free */
+        makeTriangle(vec3(1.6f * u01() - 0.8f, 1.6f * u01() - 0.8f, 1.3f * u01() - 0.9f), 0.48f, 0.62f, v);
+        addTriangle(buckets[recordOf(c)], v[0], v[1], v[2]);
+    }
+
+    /* the room, seen from inside: floor, ceiling, back, front, left, right */
+    const float quads[6][4][3] = {
+        { { -1, -1, 1 }, { 1, -1, 1 }, { 1, -1, -1 }, { -1, -1, -1 } },
+        { { -1, 1, -1 }, { 1, 1, -1 }, { 1, 1, 1 }, { -1, 1, 1 } },
+        { { -1, -1, -1 }, { 1, -1, -1 }, { 1, 1, -1 }, { -1, 1, -1 } },
+        { { 1, -1, 1 }, { -1, -1, 1 }, { -1, 1, 1 }, { 1, 1, 1 } },
+        { { -1, -1, 1 }, { -1, -1, -1 }, { -1, 1, -1 }, { -1, 1, 1 } },
+        { { 1, -1, -1 }, { 1, -1, 1 }, { 1, 1, 1 }, { 1, 1, -1 } },
+    };
+    for (unsigned int q = 0; q < 6; q++) {
+        vec3 p[4];
+        for (int k = 0; k < 4; k++)
+            p[k] = vec3(quads[q][k][0], quads[q][k][1], quads[q][k][2]);
+        Bucket& b = buckets[recordOf(clutter + q)];
+        addTriangle(b, p[0], p[1], p[2]);
+        addTriangle(b, p[0], p[2], p[3]);
+    }
+
+    /* one instance per record in the records' order: flatten() numbers a material at its first use */
+    for (unsigned int k = 0; k < K; k++) {
+        if (buckets[k].ind.empty())
+            unusedMaterials.push_back(surface[k]);
+        else
+            scene.take(new MeshInstance(scene.take(new Mesh(buckets[k].pos, buckets[k].nrm, {}, buckets[k].ind)), surface[k]));
+    }
+    Bucket lamp;
+    const float ly = 0.985f, lr = 0.8f;
+    addTriangle(lamp, vec3(-lr, ly, -lr), vec3(lr, ly, -lr), vec3(lr, ly, lr));
+    addTriangle(lamp, vec3(-lr, ly, -lr), vec3(lr, ly, lr), vec3(-lr, ly, lr));
+    scene.take(new MeshInstance(scene.take(new Mesh(lamp.pos, lamp.nrm, {}, lamp.ind)), lightMaterial), HotSpot);
+    return true;
+}
+
+/* Puts the records of `unused` in front of a flattened scene's material records.  flatten() describes a material where an instance
+ * first uses it; a material that no instance uses gets its record here, and every index of a record moves up. */
+bool prependMaterials(const Scene& scene, FlatScene& flat, const std::vector<const Material*>& unused, std::string& error)
+{
+    FlattenContext ctx;
+    std::vector<wpt_material> records(unused.size());
+    std::vector<int> sceneIndex(unused.size());
+    for (size_t i = 0; i < unused.size(); i++) {
+        if (!unused[i]->describe(records[i], ctx) || !ctx.textures.empty()) {
+            error = "lds_edge_scene: a material without textures was expected";
+            return false;
+        }
+        sceneIndex[i] = scene.materialIndex(unused[i]);
+    }
+    const int shift = int(unused.size());
+    for (wpt_material& m : flat.materials)
+        if (m.type == WPT_MAT_TWOSIDED) {
+            m.tex[0] += shift;
+            m.tex[1] += shift;
+        }
+    for (wpt_instance& inst : flat.instances)
+        inst.material += shift;
+    for (wpt_tri_geom& g : flat.triGeom)
+        g.material += shift;
+    flat.materials.insert(flat.materials.begin(), records.begin(), records.end());
+    flat.materialSceneIndex.insert(flat.materialSceneIndex.begin(), sceneIndex.begin(), sceneIndex.end());
+    return true;
+}
+
 wpt_host_scene* finishSceneOf(wpt_host_scene* hs, Scene& scene, unsigned int width, unsigned int height, float vfovRadians,
         const vec3& from, const vec3& at, float aperture, float focusDist)
 {
@@ -445,6 +610,29 @@ wpt_host_scene* wpt_host_random_triangles(unsigned int n, unsigned int seed, int
     wpt_host_scene* hs = new wpt_host_scene;
     buildRandomTriangles(hs->scene, n, seed, withTexcoords != 0);
     return finishScene(hs, width, height, radians(60.0f), vec3(0.3f, 0.4f, 3.5f), vec3(0.0f, 0.0f, 0.0f), aperture, 3.5f);
+}
+
+/* buildLdsEdgeScene with its camera: inside the room at its near end, looking along -z at the far wall */
+wpt_host_scene* wpt_host_lds_edge_scene(unsigned int triangles, unsigned int materials, int light, unsigned int seed,
+        unsigned int width, unsigned int height)
+{
+    wpt_host_scene* hs = new wpt_host_scene;
+    std::vector<const Material*> unused;
+    if (!buildLdsEdgeScene(hs->scene, triangles, materials, light, seed, unused, hs->error)) {
+        fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
+        delete hs;
+        return nullptr;
+    }
+    hs = finishScene(hs, width, height, radians(75.0f), vec3(0.07f, -0.13f, 0.93f), vec3(0.0f, -0.1f, -1.0f));
+    if (!hs)
+        return nullptr;
+    if (!prependMaterials(hs->scene, hs->flat, unused, hs->error)) {
+        fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
+        delete hs;
+        return nullptr;
+    }
+    hs->desc = hs->flat.desc();
+    return hs;
 }
 
 /* Gives the scene's camera a lens distortion: model 1 = RadialAndPlanar(k1, k2, p1, p2), 2 = RadialOnly(k1, k2, k3),
