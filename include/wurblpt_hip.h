@@ -665,7 +665,8 @@ wpt_status wpt_set_walk(uint32_t flags);
  *   wpt_scene_folded_links  of an uploaded scene, counted at the upload (0 for a scene that does not fit LDS)
  *   wpt_fold_plan           the same count from a description, a pure function that needs no device, whatever the scene's size;
  *                           lds_words (or NULL): node_count words, word 7 of every node's copy in LDS with the folds applied
- *                           (an index: where a ray that passes the box goes, node_count = out of the tree; >= 2^31: a leaf) */
+ *                           (an index: where a ray that passes the box goes, node_count = out of the tree; >= 2^31: a leaf);
+ *                           the words are those of the description's own depth-first order with its own triangle indices */
 wpt_status wpt_scene_folded_links(const wpt_scene* scene, uint32_t* folded);
 wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t* lds_words);
 /* Pixels in slices (results do not depend on it; process-global like the hooks above).  A pooled, plain product launch of the

@@ -392,6 +392,47 @@ def test_bvh_storage_order_never_changes_results(dev, oracle, top):
         assert bits_equal(gt_dev[name], gt_ref[name]), name
 
 
+@pytest.fixture(scope="module")
+def smallest_hbm_scene(oracle):
+    """lds_edge_cases.scene(184, 2) -- 367 nodes, 20 576 bytes: the smallest mesh scene the kernels fetch from HBM -- with the
+    oracle's frame, counters and ground truth, computed once and read-only"""
+    from tests import lds_edge_cases as cases
+    sc = cases.scene(184, 2)
+    ref, rc = oracle.render(sc, cases.S)
+    gt = oracle.ground_truth(sc)
+    for a in [ref] + list(gt.values()):
+        a.setflags(write=False)
+    return sc, ref, rc, gt
+
+
+@pytest.mark.parametrize("top", [1, 3, 7, 366, 367, 368])
+def test_bvh_storage_order_with_the_tree_next_to_the_nodes_in_front(dev, smallest_hbm_scene, top):
+    """The boundary test_bvh_storage_order_never_changes_results does not reach: a tree of n = 367 nodes with 1, 3, 7 and n - 1
+    nodes allowed in front (whole levels, and all but the last node's worth), and with n and n + 1, where nothing goes in front.
+    Frame, counters and ground truth are the oracle's whatever the storage order."""
+    from tests import lds_edge_cases as cases
+    sc, ref, rc, gt_ref = smallest_hbm_scene
+    assert sc.d.node_count == 367 and 32 * sc.d.node_count + 48 * sc.d.tri_count == 20576
+    assert cases.side(sc, cases.choice(sc, dev.SENSOR_FRAME)) == "HBM"
+    chosen = dev.kernel_choice(cases.need(sc), dev.SENSOR_FRAME, True, sc.d.node_count, sc.d.tri_count, sc.d.material_count)
+    assert chosen[2][1] and not chosen[2][2]        # the counting kernel, the scene in HBM
+    dev.lib().wpt_set_top_nodes(top)
+    try:
+        ds = dev.DeviceScene(sc)
+    finally:
+        dev.lib().wpt_set_top_nodes(65536)
+    try:
+        got, gc = ds.render(cases.S, with_counters=True)
+        assert (dev.lib().wpt_kernel_name().decode(), dev.lib().wpt_kernel_form().decode()) == chosen[:2]
+        assert got.shape == (cases.H, cases.W, 3) and bits_equal(got, ref) and gc == rc
+        gt_dev = dev.ground_truth(ds)
+        assert len(gt_ref) == 20 and set(gt_dev) == set(gt_ref)
+        for name in gt_ref:
+            assert bits_equal(gt_dev[name], gt_ref[name]), name
+    finally:
+        ds.close()
+
+
 @pytest.mark.parametrize("material", [0, 2, 3, 5, 6, 7])
 def test_furnace_scenes_bit_exact(dev, oracle, material):
     """wurblpt-furnace-test.cpp with a tessellated sphere (Lambertian, ModPhong diffuse and

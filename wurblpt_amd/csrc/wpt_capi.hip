@@ -1,7 +1,9 @@
 /*
- * wpt_capi.hip -- the C ABI of include/wurblpt_hip.h: scene upload (validation, conversion of
- * the BVH to the device's stackless node form, environment importance tables), kernel
- * selection and launch.  The kernel itself is in wpt_pathtrace.inc.h.
+ * wpt_capi.hip -- the C ABI of include/wurblpt_hip.h: scene upload, kernel selection and launch.  What an uploaded scene looks
+ * like -- validation, the stackless node form and its storage order, the wide form, the triangles' order, the texel and
+ * measured-BRDF pools, the environment's tables -- is decided by the pure host functions of wpt_scene_layout.h; wpt_scene_upload
+ * copies what they return and runs the three kernels that finish a scene on the device.  Which kernel renders a launch is
+ * wpt_kernel_table.h, which passes wpt_launch_plan.h.  The kernel itself is in wpt_pathtrace.inc.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -11,6 +13,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,6 +21,7 @@
 #include "wpt_pathtrace.inc.h"
 #include "wpt_kernel_table.h"
 #include "wpt_launch_plan.h"
+#include "wpt_scene_layout.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 #include "wpt_progress.h"
@@ -312,6 +316,8 @@ std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
 static_assert(wptk::PLAN_WG == uint32_t(WG) && wptk::PLAN_SLICE_SLOT_MAX == wptk::SLICE_SLOT_MASK && wptk::SLICE_UNITS_TARGET <= wptk::SLICE_UNITS_MAX
         && wptk::PLAN_FRAME == wptk::SENSOR_FRAME && wptk::PLAN_VIEWS == wptk::SENSOR_VIEWS && wptk::PLAN_ADAPTIVE == wptk::SENSOR_ADAPTIVE
         && wptk::PLAN_SENSORS == wptk::SENSOR_COUNT, "wpt_launch_plan.h restates the kernels' constants and the sensors");
+static_assert(wptl::NODE_CHILD == NODE_CHILD && wptl::NODE_INDEX_MASK == NODE_INDEX_MASK && wptl::PRIM_SPHERE == PRIM_SPHERE && wptl::WIDE_STACK == WIDE_STACK
+        && wptl::WIDE_NONE == WIDE_NONE && wptl::LDS_SCENE_MAX_BYTES == LDS_SCENE_MAX_BYTES, "wpt_scene_layout.h restates the kernels' node words and limits");
 
 /* What the process's most recent render call ran, all of it at once: every path that renders stores it here and nowhere else
  * (the wavefront form and the stages of a session too).  sliceStats: the counters a sliced launch adds to, else NULL. */
@@ -382,6 +388,94 @@ template<typename T> wpt_status uploadArray(wpt_scene* s, const T* src, size_t c
     return WPT_OK;
 }
 
+wpt_status uploadQuads(wpt_scene* s, const std::vector<wptl::Quad>& quads, const float4** dst)
+{
+    static_assert(sizeof(wptl::Quad) == sizeof(float4), "the layout's quadwords are the device's");
+    return uploadArray(s, reinterpret_cast<const float4*>(quads.data()), quads.size(), dst);
+}
+
+wpt_status layoutStatus(const wptl::Status& st)
+{
+    return st.code == WPT_OK ? WPT_OK : fail(st.code, st.message);
+}
+
+wpt_status hipStatus(hipError_t e, const char* what)
+{
+    if (e == hipSuccess)
+        return WPT_OK;
+    return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+/* what wpt_scene_upload owns until its last line, and its temporary device buffers: freed on every way out */
+struct SceneFree {
+    void operator()(wpt_scene* s) const { wpt_scene_free(s); }
+};
+struct DeviceFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+using DeviceTemp = std::unique_ptr<void, DeviceFree>;
+
+wpt_status deviceTemp(size_t bytes, const char* what, DeviceTemp* mem)
+{
+    void* p = nullptr;
+    WPT_TRY(hipStatus(hipMalloc(&p, bytes > 0 ? bytes : 16), what));
+    mem->reset(p);
+    return WPT_OK;
+}
+
+/* device memory that lives as long as the scene */
+wpt_status sceneAlloc(wpt_scene* s, size_t bytes, const char* what, void** p)
+{
+    WPT_TRY(hipStatus(hipMalloc(p, bytes > 0 ? bytes : 16), what));
+    s->allocations.push_back(*p);
+    return WPT_OK;
+}
+
+/* the pool of decoded texels that devTex indexes (wptl::texelOffsets), filled from the caller's raw pool by one launch per image */
+wpt_status decodeTexels(wpt_scene* s, const wpt_scene_desc* desc, const std::vector<wpt_texture>& devTex, size_t texelCount)
+{
+    void* pool = nullptr;
+    WPT_TRY(sceneAlloc(s, texelCount * sizeof(float4), "hipMalloc for the decoded texel pool", &pool));
+    s->view.texels4 = static_cast<const float4*>(pool);
+    if (texelCount == 0)
+        return WPT_OK;
+    DeviceTemp raw;
+    WPT_TRY(deviceTemp(desc->texel_bytes, "texel decode", &raw));
+    WPT_TRY(hipStatus(hipMemcpy(raw.get(), desc->texels, desc->texel_bytes, hipMemcpyHostToDevice), "texel decode"));
+    for (uint32_t i = 0; i < desc->texture_count; i++) {
+        const wpt_texture& t = desc->textures[i];
+        if (t.type != WPT_TEX_IMAGE)
+            continue;
+        const size_t n = size_t(t.width) * t.height;
+        hipLaunchKernelGGL(wpt_expand_texels_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, 0,
+                static_cast<const uint8_t*>(raw.get()), t, static_cast<float4*>(pool) + devTex[i].texel_offset);
+        WPT_TRY(hipStatus(hipGetLastError(), "texel decode"));
+    }
+    return hipStatus(hipDeviceSynchronize(), "texel decode");
+}
+
+/* SceneView::hotspotFace from the view's hot spots and triangles as uploaded */
+wpt_status hotspotFaces(wpt_scene* s)
+{
+    void* face = nullptr;
+    WPT_TRY(sceneAlloc(s, size_t(s->view.hotspotCount) * sizeof(float4), "hot spot faces", &face));
+    hipLaunchKernelGGL(wpt_hotspot_face_kernel, dim3((s->view.hotspotCount + 255) / 256), dim3(256), 0, 0, s->view, static_cast<float4*>(face));
+    WPT_TRY(hipStatus(hipDeviceSynchronize(), "hot spot faces"));
+    s->view.hotspotFace = static_cast<const float4*>(face);
+    return WPT_OK;
+}
+
+/* per-bin importance of the environment (envmap.hpp:128-140) from the device's own L() over the view as it is */
+wpt_status envImportance(const SceneView& view, int N, std::vector<float>* importance)
+{
+    const size_t bins = size_t(N) * N;
+    DeviceTemp dImp;
+    WPT_TRY(deviceTemp(bins * sizeof(float), "hipMalloc for the importance map", &dImp));
+    hipLaunchKernelGGL(wpt_env_importance_kernel, dim3((bins + 255) / 256), dim3(256), 0, 0, view, N, static_cast<float*>(dImp.get()));
+    importance->resize(bins);
+    return hipStatus(hipMemcpy(importance->data(), dImp.get(), bins * sizeof(float), hipMemcpyDeviceToHost), "importance map");
+}
+
 uint32_t sceneFeatures(const wpt_scene_desc* d)
 {
     uint32_t f = 0;
@@ -420,182 +514,12 @@ uint32_t sceneFeatures(const wpt_scene_desc* d)
     return f;
 }
 
+/* wptl::validate, its message kept for wpt_last_error */
 wpt_status validate(const wpt_scene_desc* d)
 {
-    if (!d)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "scene description is NULL");
-    if (d->abi_version != WPT_ABI_VERSION)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "scene description has a different ABI version");
-    if (d->node_count == 0 || !d->nodes)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "scene has no BVH nodes (run Scene::updateBVH)");
-    /* every index the kernel will follow must stay inside its array: a bad index would be an
-     * out-of-bounds access on the GPU */
-    for (uint32_t i = 0; i < d->node_count; i++) {
-        const wpt_bvh_node& n = d->nodes[i];
-        if (n.kind == WPT_NODE_INNER) {
-            if (n.link >= d->node_count || n.link <= i || i + 1 >= d->node_count)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "BVH inner node links outside the node array");
-        } else if (n.kind == WPT_NODE_TRIANGLE) {
-            if (n.link >= d->tri_count || n.link >= PRIM_SPHERE)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "BVH leaf references a triangle outside the array");
-        } else if (n.kind == WPT_NODE_SPHERE) {
-            if (n.link >= d->sphere_count || n.link >= (NODE_CHILD & ~PRIM_SPHERE))
-                return fail(WPT_ERR_INVALID_ARGUMENT, "BVH leaf references a sphere outside the array");
-        } else if (n.kind != WPT_NODE_EMPTY) {
-            return fail(WPT_ERR_UNSUPPORTED, "BVH node kind is not known to the kernel");
-        }
-    }
-    {
-        /* ... and the links must describe ONE depth-first tree over all nodes: the first child of an inner node is the
-         * next node, its second child (link) starts where the first child's subtree ends.  Links that are merely in
-         * range could share children (the device form would grow without bound) or leave nodes unreachable (the walk
-         * would run into records nobody wrote).  One reverse pass: end[i] = first node behind the subtree of node i. */
-        std::vector<uint32_t> end(d->node_count);
-        for (uint32_t i = d->node_count; i-- > 0;) {
-            const wpt_bvh_node& n = d->nodes[i];
-            if (n.kind == WPT_NODE_INNER) {
-                if (n.link != end[i + 1])
-                    return fail(WPT_ERR_INVALID_ARGUMENT, "BVH nodes are not one depth-first tree (second child does not follow the first child's subtree)");
-                end[i] = end[n.link];
-            } else {
-                end[i] = i + 1;
-            }
-        }
-        if (end[0] != d->node_count)
-            return fail(WPT_ERR_INVALID_ARGUMENT, "BVH nodes are not one depth-first tree (nodes behind the root's subtree)");
-    }
-    for (uint32_t i = 0; i < d->tri_count; i++) {
-        if (d->tri_geom[i].instance >= d->instance_count || d->tri_geom[i].material >= d->material_count)
-            return fail(WPT_ERR_INVALID_ARGUMENT, "triangle references an instance or material outside the arrays");
-    }
-    for (uint32_t i = 0; i < d->material_count; i++) {
-        const wpt_material& m = d->materials[i];
-        if (m.type > WPT_MAT_LIGHT_SPOT)
-            return fail(WPT_ERR_UNSUPPORTED, "material type is not known to the kernel");
-        if ((m.flags & WPT_MATF_TOF_LIGHT) && m.type != WPT_MAT_LIGHT_SPOT)
-            return fail(WPT_ERR_INVALID_ARGUMENT, "only a spot light can be a time-of-flight light (WPT_MATF_TOF_LIGHT)");
-        if (m.type == WPT_MAT_RGL) {
-            if (m.tex[0] < 0 || uint32_t(m.tex[0]) >= d->rgl_count)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "material references a measured BRDF outside the array");
-            if (m.normal_tex >= int32_t(d->texture_count))
-                return fail(WPT_ERR_INVALID_ARGUMENT, "material references a normal map outside the array");
-            continue;
-        }
-        if (m.type == WPT_MAT_TWOSIDED) {
-            if (m.tex[0] < 0 || m.tex[1] < 0 || uint32_t(m.tex[0]) >= d->material_count || uint32_t(m.tex[1]) >= d->material_count)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "two-sided material references a material outside the array");
-        } else {
-            for (int k = 0; k < 5; k++)
-                if (m.tex[k] >= int32_t(d->texture_count))
-                    return fail(WPT_ERR_INVALID_ARGUMENT, "material references a texture outside the array");
-        }
-        if (m.normal_tex >= int32_t(d->texture_count))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "material references a normal map outside the array");
-    }
-    for (uint32_t i = 0; i < d->texture_count; i++) {
-        const wpt_texture& t = d->textures[i];
-        if (t.type > WPT_TEX_TRANSFORMER)
-            return fail(WPT_ERR_UNSUPPORTED, "texture type is not known to the kernel");
-        if (t.type == WPT_TEX_TRANSFORMER && (t.child < 0 || uint32_t(t.child) >= d->texture_count || uint32_t(t.child) >= i))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "texture transformer references a texture outside the array");
-        if (t.type == WPT_TEX_IMAGE) {
-            size_t cs = t.texel_type == WPT_TEXEL_U8 ? 1 : t.texel_type == WPT_TEXEL_U16 ? 2 : 4;
-            if (t.width == 0 || t.height == 0 || t.comps < 1 || t.comps > 4 || t.texel_type > WPT_TEXEL_F32
-                    || t.texel_offset + size_t(t.width) * t.height * t.comps * cs > d->texel_bytes)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "image texture lies outside the texel pool");
-        }
-    }
-    if (d->rgl_count > 0 && (!d->rgl_brdfs || !d->rgl_data))
-        return fail(WPT_ERR_INVALID_ARGUMENT, "measured BRDF arrays are NULL");
-    for (uint32_t i = 0; i < d->rgl_count; i++) {
-        /* every table of the model must lie inside the pool (the kernel indexes it with data-dependent offsets) */
-        const wpt_rgl_brdf& b = d->rgl_brdfs[i];
-        const wpt_rgl_warp* warps[5] = { &b.ndf, &b.sigma, &b.vndf, &b.luminance, &b.rgb };
-        const uint32_t wantDims[5] = { 0, 0, 2, 2, 3 };
-        for (int k = 0; k < 5; k++) {
-            const wpt_rgl_warp& w = *warps[k];
-            if (w.dims != wantDims[k] || w.size_x < 2 || w.size_y < 2)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "measured BRDF table has an unexpected shape");
-            uint64_t slices = 1;
-            for (uint32_t dim = 0; dim < w.dims; dim++) {
-                if (w.param_size[dim] < 1 || uint64_t(w.param_values[dim]) + w.param_size[dim] > d->rgl_data_count)
-                    return fail(WPT_ERR_INVALID_ARGUMENT, "measured BRDF parameter grid lies outside the pool");
-                slices *= w.param_size[dim];
-            }
-            const uint64_t n = uint64_t(w.size_x) * w.size_y;
-            const bool cdf = k == 2 || k == 3;
-            if (uint64_t(w.data) + slices * n > d->rgl_data_count
-                    || (cdf && (w.marginal_cdf == WPT_RGL_NONE || w.conditional_cdf == WPT_RGL_NONE
-                            || uint64_t(w.marginal_cdf) + slices * w.size_y > d->rgl_data_count
-                            || uint64_t(w.conditional_cdf) + slices * n > d->rgl_data_count)))
-                return fail(WPT_ERR_INVALID_ARGUMENT, "measured BRDF table lies outside the pool");
-        }
-    }
-    if (d->sphere_count > 0 && !d->spheres)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "sphere array is NULL");
-    for (uint32_t i = 0; i < d->sphere_count; i++) {
-        if (d->spheres[i].material >= d->material_count)
-            return fail(WPT_ERR_INVALID_ARGUMENT, "sphere references a material outside the array");
-        if (d->spheres[i].animation >= int32_t(d->animation_count))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "sphere refers to an animation outside the array");
-    }
-    for (uint32_t i = 0; i < d->hotspot_count; i++) {
-        const wpt_hotspot& h = d->hotspots[i];
-        if (h.kind > WPT_HOTSPOT_SPHERE)
-            return fail(WPT_ERR_UNSUPPORTED, "hot spot kind is not known to the kernel");
-        if (h.prim >= (h.kind == WPT_HOTSPOT_SPHERE ? d->sphere_count : d->tri_count))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "hot spot references a primitive outside the array");
-    }
-    if (d->animation_count > 0 && (!d->animations || (d->keyframe_count > 0 && !d->keyframes)))
-        return fail(WPT_ERR_INVALID_ARGUMENT, "animation arrays are NULL");
-    for (uint32_t i = 0; i < d->animation_count; i++) {
-        const wpt_animation& a = d->animations[i];
-        if (uint64_t(a.first_keyframe) + a.keyframe_count > d->keyframe_count)
-            return fail(WPT_ERR_INVALID_ARGUMENT, "animation refers to key frames outside the array");
-        for (uint32_t k = 1; k < a.keyframe_count; k++)
-            if (!(d->keyframes[a.first_keyframe + k - 1].t < d->keyframes[a.first_keyframe + k].t))
-                return fail(WPT_ERR_INVALID_ARGUMENT, "key frames must be sorted by ascending time");
-    }
-    for (uint32_t i = 0; i < d->instance_count; i++) {
-        const wpt_instance& inst = d->instances[i];
-        if (inst.animation >= int32_t(d->animation_count) || ((inst.flags & WPT_TRI_ANIMATE) && inst.animation < 0))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "mesh instance refers to an animation outside the array");
-    }
-    for (uint32_t i = 0; i < d->tri_count; i++) {
-        const wpt_tri_geom& g = d->tri_geom[i];
-        if ((g.flags & WPT_TRI_ANIMATE) && (g.instance >= d->instance_count || d->instances[g.instance].animation < 0))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "animated triangle without an animated instance");
-    }
-    for (uint32_t i = 0; i < d->hotspot_count; i++)
-        if (d->hotspots[i].animation >= int32_t(d->animation_count))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "hot spot refers to an animation outside the array");
-    if (d->envmap.type > WPT_ENV_CUBE)
-        return fail(WPT_ERR_UNSUPPORTED, "environment map type is not known to the kernel");
-    if (d->envmap.type == WPT_ENV_EQUIRECT && (d->envmap.tex < 0 || uint32_t(d->envmap.tex) >= d->texture_count))
-        return fail(WPT_ERR_INVALID_ARGUMENT, "environment map references a texture outside the array");
-    if (d->envmap.type == WPT_ENV_CUBE) {
-        for (int k = 0; k < 6; k++)
-            if (d->envmap.cube_tex[k] < 0 || uint32_t(d->envmap.cube_tex[k]) >= d->texture_count)
-                return fail(WPT_ERR_INVALID_ARGUMENT, "environment cube map references a texture outside the array");
-    }
-    return WPT_OK;
+    return layoutStatus(wptl::validate(d));
 }
 
-/* Nodes whose link the LDS copy of a tree folds (wpt_fold.h: they go past one or more first children with their own box),
- * counted with the rule the kernels' prologue applies over device nodes (8 words each) in the order the kernels see them.
- * words (or NULL): every node's word 7 in LDS. */
-uint32_t countFoldedLinks(const uint32_t* nodes, uint32_t nodeCount, uint32_t* words)
-{
-    uint32_t folded = 0;
-    for (uint32_t i = 0; i < nodeCount; i++) {
-        uint32_t links;
-        const uint32_t word = wptf::foldLdsWord(nodes, nodeCount, i, true, &links);
-        folded += links > 0 ? 1u : 0u;
-        if (words)
-            words[i] = word;
-    }
-    return folded;
-}
 
 } /* namespace */
 
@@ -626,364 +550,90 @@ wpt_status wpt_current_device(int* device)
     return WPT_OK;
 }
 
+/* Lay out, copy, release: one array at a time (wpt_scene_layout.h says what each looks like; DESIGN.md section 3 has the table),
+ * then the three kernels that finish the scene on the device, each reading the view as it is at that moment. */
 wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
 {
     if (!out_scene)
         return fail(WPT_ERR_INVALID_ARGUMENT, "out_scene is NULL");
     *out_scene = nullptr;
-    wpt_status st = validate(desc);
-    if (st != WPT_OK)
-        return st;
+    WPT_TRY(validate(desc));
     if (wpt_device_count() <= 0)
         return fail(WPT_ERR_NO_DEVICE, "no HIP device is available; the path tracer has no CPU fallback");
-    wpt_scene* s = new wpt_scene;
+    /* the process's hooks, read once: what the scene looks like on the device is a function of the description and these two */
+    const uint32_t walk = g_walk, topNodes = g_topNodes;
+    std::unique_ptr<wpt_scene, SceneFree> owner(new wpt_scene);
+    wpt_scene* s = owner.get();
+    SceneView& view = s->view;
     HIP_TRY(hipGetDevice(&s->device));
     s->features = sceneFeatures(desc);
     s->nodeCount = desc->node_count;
     s->triCount = desc->tri_count;
-    memset(&s->view, 0, sizeof(s->view));
-    const float4* nodes = nullptr;
-    const float4* geom = nullptr;
-    const float4* attr = nullptr;
-    std::vector<uint32_t> triNew; /* triangle index of the caller -> index on the device */
-#define UP(call)                  \
-    do {                          \
-        st = (call);              \
-        if (st != WPT_OK) {       \
-            wpt_scene_free(s);    \
-            return st;            \
-        }                         \
-    } while (0)
+    memset(&view, 0, sizeof(view));
+    const std::vector<uint32_t> triNew = wptl::triangleOrder(desc, (walk & WPT_WALK_TRIANGLES_AS_GIVEN) != 0);
     {
-        /* Device node form.  The reference pops a stack to find the next node after a subtree
-         * (bvh.hpp:296,305); in depth-first order that node is the first one behind the subtree, so
-         * its index is stored per node ("skip"), an inner node also carries the index of its first
-         * child, and the kernel needs neither a stack nor any particular storage order.
-         *
-         * Storage order.  Every ray starts at the root, so the top of the tree is what all waves
-         * of an XCD keep fetching; in depth-first order those nodes lie scattered over the whole
-         * array (the right child of the root is half the array away), each dragging a 128-byte
-         * line of rarely visited neighbours into the XCD's 4 MiB L2.  For trees larger than an L2
-         * the nodes of the top levels are therefore stored first, level by level (WPT_TOP_NODES
-         * nodes, 2 MiB by default, contiguous and dense), and the subtrees below them after that,
-         * each depth-first as before (a walk that descends to a first child then reads the next
-         * 32 bytes).  The visiting order is the tree's, not the array's: results do not change. */
-        const uint32_t n = desc->node_count;
-        if (n > NODE_INDEX_MASK)
-            return fail(WPT_ERR_UNSUPPORTED, "more than 2^30 - 1 BVH nodes");
-        /* Storage order of the triangles: that of their leaves in the tree's depth-first order, so that the leaves of a subtree --
-         * which a ray tests one after the other, and neighbouring rays test too -- read neighbouring 48-byte records (a 128-byte
-         * line holds the triangles of two or three sibling leaves) instead of wherever the meshes' own order put them.  Triangle
-         * indices are identities only (leaf -> record, hot spot -> record, the candidate a light ray must end on): no value
-         * depends on them.  wpt_set_walk(WPT_WALK_TRIANGLES_AS_GIVEN) keeps the caller's order (measurements). */
-        triNew.assign(desc->tri_count, 0xffffffffu);
-        {
-            uint32_t next = 0;
-            if (!(g_walk & WPT_WALK_TRIANGLES_AS_GIVEN))
-                for (uint32_t i = 0; i < n; i++)
-                    if (desc->nodes[i].kind == WPT_NODE_TRIANGLE && triNew[desc->nodes[i].link] == 0xffffffffu)
-                        triNew[desc->nodes[i].link] = next++;
-            for (uint32_t t = 0; t < desc->tri_count; t++) /* triangles no leaf refers to (or all, in the caller's order) */
-                if (triNew[t] == 0xffffffffu)
-                    triNew[t] = next++;
-        }
-        /* end[i] = first depth-first index behind the subtree of node i (validated above) */
-        std::vector<uint32_t> end(n);
-        for (uint32_t i = n; i-- > 0;)
-            end[i] = desc->nodes[i].kind == WPT_NODE_INNER ? end[desc->nodes[i].link] : i + 1;
-        const uint64_t slotCount = n;
-        std::vector<uint32_t> place(size_t(n) + 1); /* depth-first index -> storage index; place[n] ends the walk */
-        place[n] = n;
-        uint32_t topNodes = g_topNodes;
-        if (n <= topNodes) /* the whole tree is no larger than the part that would go in front: nothing to gain */
-            topNodes = 0;
-        {
-            uint32_t cursor = 0;
-            std::vector<uint32_t> level, next;
-            if (topNodes > 0) {
-                level.push_back(0);
-                while (!level.empty() && cursor + level.size() <= topNodes) {
-                    next.clear();
-                    for (uint32_t i : level) {
-                        place[i] = cursor;
-                        cursor += 1;
-                        if (desc->nodes[i].kind == WPT_NODE_INNER) {
-                            next.push_back(i + 1);
-                            next.push_back(desc->nodes[i].link);
-                        }
-                    }
-                    level.swap(next);
-                }
-            } else {
-                level.push_back(0);
-            }
-            /* the subtrees that did not make it into the top part, depth-first each, in depth-first order of their roots
-             * (blocks of 2 - 6 levels stored level by level instead were measured: 52.3 - 51.8 against 52.7 Msamples/s on the
-             * 10 M triangle scene, no difference on the Sponza-class one; locality of the nodes is not what that scene lacks) */
-            std::sort(level.begin(), level.end());
-            for (uint32_t root : level)
-                for (uint32_t i = root; i < end[root]; i++) {
-                    place[i] = cursor;
-                    cursor += 1;
-                }
-            if (cursor != slotCount) {
-                wpt_scene_free(s);
-                return fail(WPT_ERR_INVALID_ARGUMENT, "BVH conversion: the links do not reach every node exactly once");
-            }
-        }
-        /* one node of padding: kernels that fetch aligned pairs of nodes read the whole last pair */
-        std::vector<float4> dev(size_t(slotCount) * 2 + 2, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        s->view.nodeCount = n;
-        for (uint32_t i = 0; i < n; i++) {
-            const wpt_bvh_node& nd = desc->nodes[i];
-            const uint32_t skip = place[end[i]];
-            const uint32_t word = nd.kind == WPT_NODE_INNER ? (NODE_CHILD | place[i + 1]) : nd.kind == WPT_NODE_TRIANGLE ? triNew[nd.link]
-                : nd.kind == WPT_NODE_SPHERE ? (PRIM_SPHERE | nd.link) : (NODE_CHILD | skip);
-            float sk, wd;
-            memcpy(&sk, &skip, 4);
-            memcpy(&wd, &word, 4);
-            dev[2 * size_t(place[i])] = make_float4(nd.lo[0], nd.hi[0], nd.lo[1], nd.lo[2]); /* nodeLo / nodeHi (wpt_device.h) */
-            dev[2 * size_t(place[i]) + 1] = make_float4(nd.hi[1], nd.hi[2], sk, wd);
-            for (int a = 0; a < 3; a++)
-                if (nd.lo[a] != nd.lo[a] || nd.hi[a] != nd.hi[a])
-                    s->view.boxesMayBeNan = 1u;
-        }
-        UP(uploadArray(s, dev.data(), dev.size(), &nodes));
+        wptl::DeviceNodes nodes;
+        WPT_TRY(layoutStatus(wptl::deviceNodes(desc, triNew, topNodes, &nodes)));
+        view.nodeCount = desc->node_count;
+        view.boxesMayBeNan = nodes.boxesMayBeNan;
+        WPT_TRY(uploadQuads(s, nodes.quads, &view.nodes));
         s->foldedLinks = 0;
-        if (size_t(n) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES) /* the trees that are walked from LDS */
-            s->foldedLinks = countFoldedLinks(reinterpret_cast<const uint32_t*>(dev.data()), n, nullptr);
-        if (g_walk & WPT_WALK_WIDE) {
-            /* The wide form (wpt_pathtrace.inc.h): the binary tree collapsed by one level.  Wide nodes are made for the root and
-             * for every inner node that is an entry of a wide node, in depth-first order (a wide node's first inner entry follows
-             * it).  The walk's argument needs finite boxes and every child's box within its parent's; its stack needs the tree's
-             * worst case to fit.  A tree that fails any of the three has no wide form and is walked as it is. */
-            bool ok = true;
-            for (uint32_t i = 0; i < n && ok; i++) {
-                const wpt_bvh_node& nd = desc->nodes[i];
-                for (int a = 0; a < 3; a++)
-                    ok = ok && std::isfinite(nd.lo[a]) && std::isfinite(nd.hi[a]);
-                if (nd.kind == WPT_NODE_INNER) {
-                    const uint32_t child[2] = { i + 1, nd.link };
-                    for (int k = 0; k < 2; k++)
-                        for (int a = 0; a < 3; a++)
-                            ok = ok && desc->nodes[child[k]].lo[a] >= nd.lo[a] && desc->nodes[child[k]].hi[a] <= nd.hi[a];
-                }
-            }
-            std::vector<float4> wide;
-            std::vector<uint32_t> made;        /* binary node of each wide node, in order of creation */
-            std::vector<uint32_t> entries;     /* 4 per wide node: binary nodes, 0xffffffff = none */
-            if (ok) {
-                std::vector<uint32_t> todo(1, 0u); /* depth first: a stack of binary nodes to make wide nodes for */
-                while (!todo.empty()) {
-                    const uint32_t x = todo.back();
-                    todo.pop_back();
-                    made.push_back(x);
-                    uint32_t entry[4] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu };
-                    int count = 0;
-                    if (desc->nodes[x].kind == WPT_NODE_INNER) {
-                        const uint32_t child[2] = { x + 1, desc->nodes[x].link };
-                        for (int k = 0; k < 2; k++) {
-                            if (desc->nodes[child[k]].kind == WPT_NODE_INNER) {
-                                entry[count++] = child[k] + 1;
-                                entry[count++] = desc->nodes[child[k]].link;
-                            } else {
-                                entry[count++] = child[k];
-                            }
-                        }
-                    } else {
-                        entry[count++] = x; /* a tree of one leaf */
-                    }
-                    for (int k = 0; k < 4; k++)
-                        entries.push_back(entry[k]);
-                    for (int k = count - 1; k >= 0; k--) /* the first inner entry is made next */
-                        if (desc->nodes[entry[k]].kind == WPT_NODE_INNER && entry[k] != x)
-                            todo.push_back(entry[k]);
-                }
-                ok = made.size() <= NODE_INDEX_MASK;
-            }
-            if (ok) {
-                /* wide index of every binary node that has one; creation order is a pre-order, so a reverse pass sees children first */
-                std::vector<uint32_t> wideOf(n, 0xffffffffu);
-                for (size_t w = 0; w < made.size(); w++)
-                    wideOf[made[w]] = uint32_t(w);
-                std::vector<uint32_t> depth(made.size(), 0u); /* entries that can wait on the stack while the walk is below this wide node */
-                for (size_t w = made.size(); w-- > 0;) {
-                    int count = 0;
-                    while (count < 4 && entries[4 * w + count] != 0xffffffffu)
-                        count++;
-                    uint32_t worst = 0;
-                    for (int k = 0; k < count; k++) {
-                        const uint32_t e = entries[4 * w + k];
-                        const uint32_t below = (desc->nodes[e].kind == WPT_NODE_INNER && e != made[w]) ? depth[wideOf[e]] : 0u;
-                        worst = std::max(worst, uint32_t(count - 1 - k) + below);
-                    }
-                    depth[w] = worst;
-                }
-                ok = depth[0] <= WIDE_STACK;
-                wide.resize(made.size() * 8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                for (size_t w = 0; w < made.size() && ok; w++) {
-                    float q[8][4];
-                    uint32_t ref[4] = { WIDE_NONE, WIDE_NONE, WIDE_NONE, WIDE_NONE };
-                    for (int r = 0; r < 8; r++)
-                        for (int k = 0; k < 4; k++)
-                            q[r][k] = 0.0f;
-                    for (int k = 0; k < 4; k++) {
-                        const uint32_t e = entries[4 * w + k];
-                        if (e == 0xffffffffu)
-                            continue;
-                        const wpt_bvh_node& nd = desc->nodes[e];
-                        for (int a = 0; a < 3; a++) {
-                            q[a][k] = nd.lo[a];
-                            q[3 + a][k] = nd.hi[a];
-                        }
-                        if (nd.kind == WPT_NODE_INNER)
-                            ref[k] = NODE_CHILD | wideOf[e];
-                        else if (nd.kind == WPT_NODE_TRIANGLE)
-                            ref[k] = triNew[nd.link];
-                        else if (nd.kind == WPT_NODE_SPHERE)
-                            ref[k] = PRIM_SPHERE | nd.link;
-                    }
-                    memcpy(q[6], ref, 16);
-                    for (int r = 0; r < 8; r++)
-                        wide[8 * w + r] = make_float4(q[r][0], q[r][1], q[r][2], q[r][3]);
-                }
-            }
-            if (ok)
-                UP(uploadArray(s, wide.data(), wide.size(), &s->view.wideNodes));
-        }
+        if (size_t(desc->node_count) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES) /* the trees that are walked from LDS */
+            s->foldedLinks = wptl::countFoldedLinks(reinterpret_cast<const uint32_t*>(nodes.quads.data()), desc->node_count, nullptr);
+    }
+    if (walk & WPT_WALK_WIDE) {
+        const std::vector<wptl::Quad> wide = wptl::wideNodes(desc, triNew);
+        if (!wide.empty()) /* a tree without a wide form is walked as it is */
+            WPT_TRY(uploadQuads(s, wide, &view.wideNodes));
     }
     {
-        std::vector<wpt_tri_geom> g(desc->tri_count);
-        for (uint32_t t = 0; t < desc->tri_count; t++)
-            g[triNew[t]] = desc->tri_geom[t];
-        UP(uploadArray(s, reinterpret_cast<const float4*>(g.data()), size_t(desc->tri_count) * 3, &geom));
+        const std::vector<wpt_tri_geom> g = wptl::permuted(desc->tri_geom, triNew);
+        WPT_TRY(uploadArray(s, reinterpret_cast<const float4*>(g.data()), size_t(desc->tri_count) * 3, &view.triGeom));
     }
     {
-        std::vector<wpt_tri_attr> a(desc->tri_count);
-        for (uint32_t t = 0; t < desc->tri_count; t++)
-            a[triNew[t]] = desc->tri_attr[t];
-        UP(uploadArray(s, reinterpret_cast<const float4*>(a.data()), size_t(desc->tri_count) * 6, &attr));
+        const std::vector<wpt_tri_attr> a = wptl::permuted(desc->tri_attr, triNew);
+        WPT_TRY(uploadArray(s, reinterpret_cast<const float4*>(a.data()), size_t(desc->tri_count) * 6, &view.triAttr));
     }
-    s->view.nodes = nodes;
-    s->view.triGeom = geom;
-    s->view.triAttr = attr;
-    UP(uploadArray(s, desc->instances, desc->instance_count, &s->view.instances));
-    UP(uploadArray(s, desc->materials, desc->material_count, &s->view.materials));
-    s->view.materialCount = desc->material_count;
+    WPT_TRY(uploadArray(s, desc->instances, desc->instance_count, &view.instances));
+    WPT_TRY(uploadArray(s, desc->materials, desc->material_count, &view.materials));
+    view.materialCount = desc->material_count;
     {
-        /* Image textures are decoded once, here, into one pool of RGBA float4 texels (16 bytes
-         * per texel whatever the file format was: HBM is large, instructions per lookup are
-         * not); the device copies of the texture records index that pool. */
-        std::vector<wpt_texture> devTex(desc->textures, desc->textures + desc->texture_count);
         size_t texelCount = 0;
-        for (wpt_texture& t : devTex) {
-            if (t.type == WPT_TEX_IMAGE) {
-                t.texel_offset = texelCount;
-                texelCount += size_t(t.width) * t.height;
-            }
-        }
-        UP(uploadArray(s, devTex.data(), devTex.size(), &s->view.textures));
-        void* pool = nullptr;
-        hipError_t e = hipMalloc(&pool, texelCount > 0 ? texelCount * sizeof(float4) : 16);
-        if (e != hipSuccess) {
-            wpt_scene_free(s);
-            return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("hipMalloc for the decoded texel pool: ") + hipGetErrorString(e));
-        }
-        s->allocations.push_back(pool);
-        s->view.texels4 = static_cast<const float4*>(pool);
-        if (texelCount > 0) {
-            uint8_t* raw = nullptr;
-            e = hipMalloc(reinterpret_cast<void**>(&raw), desc->texel_bytes > 0 ? desc->texel_bytes : 16);
-            if (e == hipSuccess)
-                e = hipMemcpy(raw, desc->texels, desc->texel_bytes, hipMemcpyHostToDevice);
-            for (uint32_t i = 0; e == hipSuccess && i < desc->texture_count; i++) {
-                const wpt_texture& t = desc->textures[i];
-                if (t.type != WPT_TEX_IMAGE)
-                    continue;
-                const size_t n = size_t(t.width) * t.height;
-                hipLaunchKernelGGL(wpt_expand_texels_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, 0,
-                        raw, t, static_cast<float4*>(pool) + devTex[i].texel_offset);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess)
-                e = hipDeviceSynchronize();
-            (void)hipFree(raw);
-            if (e != hipSuccess) {
-                wpt_scene_free(s);
-                return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("texel decode: ") + hipGetErrorString(e));
-            }
-        }
+        const std::vector<wpt_texture> devTex = wptl::texelOffsets(desc, &texelCount);
+        WPT_TRY(uploadArray(s, devTex.data(), devTex.size(), &view.textures));
+        WPT_TRY(decodeTexels(s, desc, devTex, texelCount));
     }
     {
-        std::vector<wpt_hotspot> h(desc->hotspots, desc->hotspots + desc->hotspot_count);
-        for (wpt_hotspot& hs : h)
-            if (hs.kind != WPT_HOTSPOT_SPHERE)
-                hs.prim = triNew[hs.prim];
-        UP(uploadArray(s, h.data(), h.size(), &s->view.hotspots));
+        const std::vector<wpt_hotspot> h = wptl::remappedHotspots(desc, triNew);
+        WPT_TRY(uploadArray(s, h.data(), h.size(), &view.hotspots));
     }
-    UP(uploadArray(s, desc->spheres, desc->sphere_count, &s->view.spheres));
-    UP(uploadArray(s, desc->rgl_brdfs, desc->rgl_count, &s->view.rglBrdfs));
+    WPT_TRY(uploadArray(s, desc->spheres, desc->sphere_count, &view.spheres));
+    WPT_TRY(uploadArray(s, desc->rgl_brdfs, desc->rgl_count, &view.rglBrdfs));
     {
-        /* The measured BRDFs' pool, and behind it one interleaved table per BRDF whose colour and luminance warps share their
-         * grids (wpt_rgl.h, rglColourInterleaved): red, green, blue and luminance of a grid point side by side, so that the up to
-         * 128 look-ups an evaluation makes into those two warps come from 8 cache lines instead of 32.  The values are the
-         * pool's own; which copy a look-up reads changes no bit. */
-        std::vector<float> pool(desc->rgl_data, desc->rgl_data + desc->rgl_data_count);
-        std::vector<uint32_t> rgbl(desc->rgl_count, WPT_RGL_NONE);
-        for (uint32_t i = 0; i < desc->rgl_count; i++) {
-            const wpt_rgl_brdf& b = desc->rgl_brdfs[i];
-            if (!wptrgl::rglInterleavable(b))
-                continue;
-            const size_t size = size_t(b.rgb.size_x) * b.rgb.size_y;
-            const size_t slices = size_t(b.luminance.param_size[0]) * b.luminance.param_size[1];
-            const size_t at = (pool.size() + 3) & ~size_t(3); /* 16-byte records */
-            if (at + slices * size * 4 > 0xfffffff0ull)
-                continue;
-            pool.resize(at + slices * size * 4);
-            for (size_t sl = 0; sl < slices; sl++)
-                for (size_t e = 0; e < size; e++) {
-                    float* t = pool.data() + at + (sl * size + e) * 4;
-                    for (size_t c = 0; c < 3; c++)
-                        t[c] = desc->rgl_data[b.rgb.data + (sl * 3 + c) * size + e];
-                    t[3] = desc->rgl_data[b.luminance.data + sl * size + e];
-                }
-            rgbl[i] = uint32_t(at);
-        }
-        UP(uploadArray(s, pool.data(), pool.size(), &s->view.rglData));
-        UP(uploadArray(s, rgbl.data(), rgbl.size(), &s->view.rglRgbl));
+        const wptl::RglPool rgl = wptl::rglPool(desc);
+        WPT_TRY(uploadArray(s, rgl.pool.data(), rgl.pool.size(), &view.rglData));
+        WPT_TRY(uploadArray(s, rgl.rgbl.data(), rgl.rgbl.size(), &view.rglRgbl));
     }
-    UP(uploadArray(s, desc->animations, desc->animation_count, &s->view.animations));
-    UP(uploadArray(s, desc->keyframes, desc->keyframe_count, &s->view.keyframes));
+    WPT_TRY(uploadArray(s, desc->animations, desc->animation_count, &view.animations));
+    WPT_TRY(uploadArray(s, desc->keyframes, desc->keyframe_count, &view.keyframes));
     s->animationCount = desc->animation_count;
-    s->view.sphereCount = desc->sphere_count;
+    view.sphereCount = desc->sphere_count;
     for (int k = 0; k < 6; k++)
-        s->view.envCube[k] = desc->envmap.cube_tex[k];
+        view.envCube[k] = desc->envmap.cube_tex[k];
     {
         hipDeviceProp_t prop;
         s->cuCount = hipGetDeviceProperties(&prop, s->device) == hipSuccess ? prop.multiProcessorCount : 256;
     }
-    s->view.triCount = desc->tri_count;
-    s->view.hotspotCount = desc->hotspot_count;
-    s->view.invHotspotCount = desc->hotspot_count ? 1.0f / float(desc->hotspot_count) : 0.0f;
-    if (desc->hotspot_count > 0) {
-        float4* face = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&face), size_t(desc->hotspot_count) * sizeof(float4));
-        if (e == hipSuccess) {
-            s->allocations.push_back(face);
-            hipLaunchKernelGGL(wpt_hotspot_face_kernel, dim3((desc->hotspot_count + 255) / 256), dim3(256), 0, 0, s->view, face);
-            e = hipDeviceSynchronize();
-        }
-        if (e != hipSuccess) {
-            wpt_scene_free(s);
-            return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("hot spot faces: ") + hipGetErrorString(e));
-        }
-        s->view.hotspotFace = face;
-    }
-    s->view.envType = desc->envmap.type;
-    s->view.envCompat = desc->envmap.compat;
-    s->view.envTex = desc->envmap.tex;
-    s->view.envN = 0;
-    s->view.envLog2N = -1;
+    view.triCount = desc->tri_count;
+    view.hotspotCount = desc->hotspot_count;
+    view.invHotspotCount = desc->hotspot_count ? 1.0f / float(desc->hotspot_count) : 0.0f;
+    if (desc->hotspot_count > 0)
+        WPT_TRY(hotspotFaces(s));
+    view.envType = desc->envmap.type;
+    view.envCompat = desc->envmap.compat;
+    view.envTex = desc->envmap.tex;
+    view.envN = 0;
+    view.envLog2N = -1;
     if (desc->envmap.type != WPT_ENV_NONE && desc->envmap.N > 0) {
         const int N = desc->envmap.N;
         const size_t bins = size_t(N) * N;
@@ -992,74 +642,26 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
             s->envMs.assign(desc->envmap.Ms, desc->envmap.Ms + bins);
             s->envMcs.assign(desc->envmap.Mcs, desc->envmap.Mcs + bins);
         } else {
-            /* EnvironmentMap::initializeImportanceSampling (envmap.hpp:121-158): the per-bin
-             * importance comes from the device's own L(); sum, sort and prefix sum run on the
-             * host in the reference's sequential order */
-            float* dImp = nullptr;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&dImp), bins * sizeof(float));
-            if (e != hipSuccess) {
-                wpt_scene_free(s);
-                return fail(WPT_ERR_OUT_OF_MEMORY, "hipMalloc for the importance map failed");
-            }
-            hipLaunchKernelGGL(wpt_env_importance_kernel, dim3((bins + 255) / 256), dim3(256), 0, 0, s->view, N, dImp);
-            s->envM.resize(bins);
-            e = hipMemcpy(s->envM.data(), dImp, bins * sizeof(float), hipMemcpyDeviceToHost);
-            (void)hipFree(dImp);
-            if (e != hipSuccess) {
-                wpt_scene_free(s);
-                return fail(WPT_ERR_HIP, std::string("importance map: ") + hipGetErrorString(e));
-            }
-            float total = 0.0f;
-            for (size_t i = 0; i < bins; i++)
-                total += s->envM[i];
-            for (size_t i = 0; i < bins; i++)
-                s->envM[i] /= total;
-            s->envMs.resize(bins);
-            for (size_t i = 0; i < bins; i++)
-                s->envMs[i] = int32_t(i);
-            const std::vector<float>& M = s->envM;
-            std::sort(s->envMs.begin(), s->envMs.end(), [&M](unsigned int i, unsigned int j) { return M[i] > M[j]; });
-            s->envMcs.resize(bins);
-            float sum = 0.0f;
-            for (size_t i = 0; i < bins; i++) {
-                sum += M[s->envMs[i]];
-                s->envMcs[i] = sum;
-            }
+            /* the per-bin importance comes from the device's own L(); the tables from it on the host */
+            std::vector<float> importance;
+            WPT_TRY(envImportance(view, N, &importance));
+            wptl::EnvTables t = wptl::envTablesFromImportance(importance.data(), bins);
+            s->envM.swap(t.M);
+            s->envMs.swap(t.Ms);
+            s->envMcs.swap(t.Mcs);
         }
-        UP(uploadArray(s, s->envM.data(), bins, &s->view.envM));
-        UP(uploadArray(s, s->envMs.data(), bins, &s->view.envMs));
-        UP(uploadArray(s, s->envMcs.data(), bins, &s->view.envMcs));
-        {
-            /* start table for the sampling search (envD in wpt_device.h); only for a non-decreasing
-             * cumulative table, which is what the construction gives -- a caller's own table that is
-             * not gets the plain bisection */
-            bool monotone = true;
-            for (size_t i = 1; i < bins && monotone; i++)
-                monotone = !(s->envMcs[i] < s->envMcs[i - 1]);
-            if (monotone) {
-                const uint32_t K = 65536;
-                std::vector<int32_t> lut(K + 1);
-                size_t i = 0;
-                for (uint32_t k = 0; k < K; k++) {
-                    const float t = float(k) / float(K);
-                    while (i < bins && s->envMcs[i] < t)
-                        i++;
-                    lut[k] = int32_t(i < bins ? i : bins - 1);
-                }
-                lut[K] = int32_t(bins - 1);
-                UP(uploadArray(s, lut.data(), lut.size(), &s->view.envLut));
-                s->view.envLutSize = K;
-            }
+        WPT_TRY(uploadArray(s, s->envM.data(), bins, &view.envM));
+        WPT_TRY(uploadArray(s, s->envMs.data(), bins, &view.envMs));
+        WPT_TRY(uploadArray(s, s->envMcs.data(), bins, &view.envMcs));
+        const std::vector<int32_t> lut = wptl::envStartTable(s->envMcs.data(), bins);
+        if (!lut.empty()) { /* a caller's own table that is not monotone gets the plain bisection */
+            WPT_TRY(uploadArray(s, lut.data(), lut.size(), &view.envLut));
+            view.envLutSize = wptl::ENV_LUT_SIZE;
         }
-        s->view.envN = N;
-        s->view.envLog2N = -1;
-        if (N > 0 && (N & (N - 1)) == 0)
-            for (int b = 0; b < 31; b++)
-                if ((1 << b) == N)
-                    s->view.envLog2N = b;
+        view.envN = N;
+        view.envLog2N = wptl::envLog2(N);
     }
-#undef UP
-    *out_scene = s;
+    *out_scene = owner.release();
     return WPT_OK;
 }
 
@@ -2296,23 +1898,12 @@ wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t*
 {
     if (!folded)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    const wpt_status st = validate(desc);
-    if (st != WPT_OK)
-        return st;
-    /* the device nodes of wpt_scene_upload, depth-first (the storage order of every tree that fits LDS) */
-    const uint32_t n = desc->node_count;
-    std::vector<uint32_t> end(n), words(size_t(n) * 8);
-    for (uint32_t i = n; i-- > 0;)
-        end[i] = desc->nodes[i].kind == WPT_NODE_INNER ? end[desc->nodes[i].link] : i + 1;
-    for (uint32_t i = 0; i < n; i++) {
-        const wpt_bvh_node& nd = desc->nodes[i];
-        const float box[6] = { nd.lo[0], nd.hi[0], nd.lo[1], nd.lo[2], nd.hi[1], nd.hi[2] };
-        memcpy(&words[8 * size_t(i)], box, sizeof(box));
-        words[8 * size_t(i) + 6] = end[i];
-        words[8 * size_t(i) + 7] = nd.kind == WPT_NODE_INNER ? (NODE_CHILD | (i + 1)) : nd.kind == WPT_NODE_TRIANGLE ? nd.link
-                : nd.kind == WPT_NODE_SPHERE ? (PRIM_SPHERE | nd.link) : (NODE_CHILD | end[i]);
-    }
-    *folded = countFoldedLinks(words.data(), n, lds_words);
+    WPT_TRY(validate(desc));
+    /* the device nodes of wpt_scene_upload with nothing in front (depth-first: the storage order of every tree that fits LDS)
+     * and the triangles as given */
+    wptl::DeviceNodes nodes;
+    WPT_TRY(layoutStatus(wptl::deviceNodes(desc, wptl::triangleOrder(desc, true), 0, &nodes)));
+    *folded = wptl::countFoldedLinks(reinterpret_cast<const uint32_t*>(nodes.quads.data()), desc->node_count, lds_words);
     return WPT_OK;
 }
 
