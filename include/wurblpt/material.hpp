@@ -71,6 +71,8 @@ public:
         Material(nullptr), _frontSideMaterial(frontSideMaterial), _backSideMaterial(backSideMaterial)
     {
     }
+    const Material* frontSideMaterial() const { return _frontSideMaterial; }
+    const Material* backSideMaterial() const { return _backSideMaterial; }
     virtual bool describe(wpt_material& out, FlattenContext& ctx) const override
     {
         out = wptEmptyMaterial(WPT_MAT_TWOSIDED);

@@ -15,6 +15,7 @@
 
 #include "../wurblpt_hip.h"
 #include "array.hpp"
+#include "sensor.hpp"
 
 namespace WurblPT {
 
@@ -84,6 +85,27 @@ inline Array<float> uniformRationalQuantization(const Array<float>& img, float m
 inline Array<float> scaleLuminance(const Array<float>& img, float factor, float clamp = 1.0f)
 {
     return postprocdetail::floatResult(2, img, factor, clamp);
+}
+
+/* The groups of a light-groups render weighted into one frame: an RGB weight per group sets its lamps' intensity and colour
+ * after the render.  out = (((0 + w[0] * group 0) + w[1] * group 1) + ...) per channel in float (wpt_postproc_mix_planes_host in
+ * wurblpt_hip.h, the same bits as the device's mix); runs on the CPU.  `weights`: groupCount() * 3 floats. */
+inline Array<float> mixLightGroups(const SensorRGBLightGroups& sensor, const std::vector<float>& weights)
+{
+    const unsigned int K = sensor.groupCount();
+    if (weights.size() != size_t(K) * 3)
+        throw std::invalid_argument("mixLightGroups: an RGB weight per group (" + std::to_string(K) + " * 3 floats)");
+    const size_t pixels = sensor.result().elementCount();
+    std::vector<float> planes(size_t(K) * pixels * 3);
+    for (unsigned int g = 0; g < K; g++) {
+        const std::vector<float> rgb = postprocdetail::packRgb(sensor.group(g));
+        std::copy(rgb.begin(), rgb.end(), planes.begin() + size_t(g) * pixels * 3);
+    }
+    Array<float> r(sensor.width(), sensor.height(), 3);
+    r.globalTagList() = sensor.result().globalTagList();
+    if (pixels > 0 && wpt_postproc_mix_planes_host(planes.data(), K, pixels * 3, pixels, weights.data(), static_cast<float*>(r.data())) != WPT_OK)
+        throw std::runtime_error(std::string("mixLightGroups failed: ") + wpt_last_error());
+    return r;
 }
 
 }

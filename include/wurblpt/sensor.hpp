@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <limits>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -14,6 +15,8 @@
 #include "array.hpp"
 
 namespace WurblPT {
+
+class Material;
 
 class Sensor
 {
@@ -106,6 +109,62 @@ public:
     const Array<float>& result() const { return _frame; }
     const Array<float>& bin(unsigned int k) const { return _bins.at(k); }
     Array<float>& bin(unsigned int k) { return _bins.at(k); }
+};
+
+/* Light groups (a capability of this port, not of the reference): mcpt() renders the frame and groupCount() frames in one
+ * pass, group(g) holding the light of the emitters assigned to group g.  Nothing that steers a path reads an emitted radiance,
+ * so group(g) is bit-identical to a SensorRGB render of the scene in which only group g's emitters emit; both gates apply to the
+ * groups as to the frame.  assign() takes the Material an emitting hitable was given (a MaterialTwoSided assigns both its
+ * children, unless a child has an assignment of its own); emitters that were not assigned, and the environment unless
+ * assignEnvironment() says otherwise, go to group 0.
+ * mixLightGroups() (postproc.hpp) weights the groups into one frame afterwards.  The groups cost groupCount() * width *
+ * height * 12 bytes. */
+class SensorRGBLightGroups final : public Sensor
+{
+private:
+    Array<float> _frame;
+    std::vector<Array<float>> _groups;
+    std::map<const Material*, unsigned int> _groupOf;
+    unsigned int _envGroup;
+
+public:
+    constexpr static unsigned int maxGroups = 255; /* WPT_LIGHT_GROUPS_MAX */
+    const float minDistToLight, maxDistToLight;
+    const float minPathLen, maxPathLen;
+
+    SensorRGBLightGroups(unsigned int width, unsigned int height, unsigned int groupCount, float minDistToLight = 0.0f,
+            float maxDistToLight = std::numeric_limits<float>::max(), float minPathLen = 0.0f,
+            float maxPathLen = std::numeric_limits<float>::max()) :
+        _frame(width, height, 3), _envGroup(0), minDistToLight(minDistToLight), maxDistToLight(maxDistToLight), minPathLen(minPathLen),
+        maxPathLen(maxPathLen)
+    {
+        if (groupCount < 1 || groupCount > maxGroups)
+            throw std::invalid_argument("SensorRGBLightGroups: 1 to " + std::to_string(maxGroups) + " groups");
+        _groups.reserve(groupCount);
+        for (unsigned int g = 0; g < groupCount; g++)
+            _groups.emplace_back(width, height, 3);
+    }
+    void assign(const Material* material, unsigned int g)
+    {
+        if (!material || g >= groupCount())
+            throw std::invalid_argument("SensorRGBLightGroups: group " + std::to_string(g) + " of " + std::to_string(groupCount()));
+        _groupOf[material] = g;
+    }
+    void assignEnvironment(unsigned int g)
+    {
+        if (g >= groupCount())
+            throw std::invalid_argument("SensorRGBLightGroups: group " + std::to_string(g) + " of " + std::to_string(groupCount()));
+        _envGroup = g;
+    }
+    virtual unsigned int width() const override { return _frame.dimension(0); }
+    virtual unsigned int height() const override { return _frame.dimension(1); }
+    virtual ArrayContainer* pixelArray() override { return &_frame; }
+    unsigned int groupCount() const { return _groups.size(); }
+    unsigned int environmentGroup() const { return _envGroup; }
+    const std::map<const Material*, unsigned int>& assignments() const { return _groupOf; }
+    const Array<float>& result() const { return _frame; }
+    const Array<float>& group(unsigned int g) const { return _groups.at(g); }
+    Array<float>& group(unsigned int g) { return _groups.at(g); }
 };
 
 }

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <stdexcept>
 #include <chrono>
 #include <string>
@@ -78,11 +79,18 @@ inline wpt_params makeParams(const Parameters& params, const SensorRGB& sensor)
 inline void mcptTransient(MPICoordinator& mpiCoordinator, SensorRGBTransient& sensor, const Camera& camera, const Scene& scene,
         unsigned int samplesSqrt, float t0, float t1, const Parameters& params);
 
+inline void mcptLightGroups(MPICoordinator& mpiCoordinator, SensorRGBLightGroups& sensor, const Camera& camera, const Scene& scene,
+        unsigned int samplesSqrt, float t0, float t1, const Parameters& params);
+
 inline void mcpt(MPICoordinator& mpiCoordinator, Sensor& sensor, const Camera& camera, const Scene& scene,
         unsigned int samplesSqrt, float t0 = 0.0f, float t1 = 0.0f, const Parameters& params = Parameters())
 {
     if (scene.bvhNeedsUpdate(t0, t1))
         mcptFatal("Scene::updateBVH(t0, t1) must run before mcpt()");
+    if (SensorRGBLightGroups* groups = dynamic_cast<SensorRGBLightGroups*>(&sensor)) {
+        mcptLightGroups(mpiCoordinator, *groups, camera, scene, samplesSqrt, t0, t1, params);
+        return;
+    }
     if (SensorRGBTransient* transient = dynamic_cast<SensorRGBTransient*>(&sensor)) {
         mcptTransient(mpiCoordinator, *transient, camera, scene, samplesSqrt, t0, t1, params);
         return;
@@ -499,6 +507,144 @@ inline void mcptTransient(MPICoordinator& mpiCoordinator, SensorRGBTransient& se
         sensor.bin(k).globalTagList().set("WURBLPT/TRANSIENT_MIN_PATH_LEN", edge);
         snprintf(edge, sizeof(edge), "%.9g", edges[k + 1]);
         sensor.bin(k).globalTagList().set("WURBLPT/TRANSIENT_MAX_PATH_LEN", edge); /* exclusive */
+    }
+}
+
+/* The table a light-groups launch takes (wurblpt_hip.h): the group of every flattened material record.  The sensor's
+ * assignments name Materials; a record is found through Scene::materialIndex().  A MaterialTwoSided's assignment goes to both
+ * its children first, assignments of other materials after it; what nobody assigned is in group 0. */
+inline std::vector<uint8_t> lightGroupsTable(const SensorRGBLightGroups& sensor, const Scene& scene, const FlatScene& flat)
+{
+    std::map<int, unsigned int> groupOfSceneIndex;
+    auto spread = [&](auto&& self, const Material* m, unsigned int g, int depth) -> void {
+        const MaterialTwoSided* two = dynamic_cast<const MaterialTwoSided*>(m);
+        if (two && depth < 4) {
+            self(self, two->frontSideMaterial(), g, depth + 1);
+            self(self, two->backSideMaterial(), g, depth + 1);
+        }
+        const int index = scene.materialIndex(m);
+        if (index >= 0)
+            groupOfSceneIndex[index] = g;
+    };
+    for (const auto& entry : sensor.assignments())
+        if (dynamic_cast<const MaterialTwoSided*>(entry.first))
+            spread(spread, entry.first, entry.second, 0);
+    for (const auto& entry : sensor.assignments())
+        if (!dynamic_cast<const MaterialTwoSided*>(entry.first))
+            spread(spread, entry.first, entry.second, 0);
+    std::vector<uint8_t> table(flat.materials.size(), 0);
+    for (size_t i = 0; i < table.size(); i++) {
+        auto it = groupOfSceneIndex.find(flat.materialSceneIndex[i]);
+        if (it != groupOfSceneIndex.end())
+            table[i] = uint8_t(it->second);
+    }
+    return table;
+}
+
+/* mcpt() for a SensorRGBLightGroups: the frame and every group's frame in one pass per block (wurblpt_hip.h:
+ * wpt_render_light_groups_block), the blocks handed out by the coordinator as for the transient film. */
+inline void mcptLightGroups(MPICoordinator& mpiCoordinator, SensorRGBLightGroups& sensor, const Camera& camera, const Scene& scene,
+        unsigned int samplesSqrt, float t0, float t1, const Parameters& params)
+{
+    wpt_camera cam;
+    if (!camera.describe(cam, t0))
+        mcptFatal("this camera cannot be described to the device path");
+    FlatScene flat;
+    std::string error;
+    if (!scene.flatten(flat, &error))
+        mcptFatal(error);
+    if (camera.animation) {
+        cam.animation = flat.addAnimation(camera.animation.get());
+        if (cam.animation < 0)
+            mcptFatal("only key frame animations (AnimationKeyframes) can go to the device");
+    }
+    const wpt_scene_desc desc = flat.desc();
+    SensorRGB gates(1, 1, sensor.minDistToLight, sensor.maxDistToLight, sensor.minPathLen, sensor.maxPathLen);
+    wpt_params p = makeParams(params, gates);
+    p.t0 = t0;
+    p.t1 = t1;
+    const unsigned int width = sensor.width();
+    const unsigned int height = sensor.height();
+    const unsigned int groupCount = sensor.groupCount();
+    const std::vector<uint8_t> table = lightGroupsTable(sensor, scene, flat);
+    ArrayContainer* pixelArray = sensor.pixelArray();
+
+    fprintf(stderr, "Number of hitables that are hot spots: %zu\n", scene.hotSpots().size());
+    fprintf(stderr, "Rendering %ux%u pixels with %u samples into the frame and %u light groups.\n", width, height,
+            samplesSqrt * samplesSqrt, groupCount);
+    if (wpt_device_count() <= 0)
+        mcptFatal(std::string("no HIP device: ") + wpt_last_error());
+
+    mpiCoordinator.init(width, height, static_cast<float*>(pixelArray->data()), pixelArray->componentCount());
+    std::vector<std::string> workerErrors(mpiCoordinator.devices().size());
+    const auto renderStart = std::chrono::steady_clock::now();
+    auto worker = [&](size_t w) {
+        int device = mpiCoordinator.devices()[w];
+        if (device >= 0 && wpt_select_device(device) != WPT_OK) {
+            workerErrors[w] = wpt_last_error();
+            return;
+        }
+        wpt_scene* dscene = nullptr;
+        if (wpt_scene_upload(&desc, &dscene) != WPT_OK) {
+            workerErrors[w] = wpt_last_error();
+            return;
+        }
+        std::vector<float> blockPlanes;
+        for (;;) {
+            unsigned int blockStart, blockSize;
+            mpiCoordinator.getBlock(&blockStart, &blockSize);
+            if (blockSize == 0)
+                break;
+            fprintf(stderr, "%s: device %d renders block of size %u starting at %u\n", mpiCoordinator.processId(), device, blockSize, blockStart);
+            blockPlanes.resize(size_t(groupCount) * blockSize * 3);
+            if (wpt_render_light_groups_block(dscene, &cam, &p, table.data(), uint32_t(table.size()), groupCount, sensor.environmentGroup(),
+                        width, height, samplesSqrt, blockStart, blockSize, mpiCoordinator.blockData(blockStart), blockPlanes.data()) != WPT_OK) {
+                workerErrors[w] = wpt_last_error();
+                break;
+            }
+            for (unsigned int g = 0; g < groupCount; g++)
+                std::copy(blockPlanes.begin() + size_t(g) * blockSize * 3, blockPlanes.begin() + size_t(g + 1) * blockSize * 3,
+                        static_cast<float*>(sensor.group(g).data()) + size_t(blockStart) * 3);
+            mpiCoordinator.submitBlock(blockStart, blockSize);
+        }
+        wpt_scene_free(dscene);
+    };
+    if (mpiCoordinator.devices().size() == 1) {
+        worker(0);
+    } else {
+        std::vector<std::thread> threads;
+        for (size_t w = 0; w < mpiCoordinator.devices().size(); w++)
+            threads.emplace_back(worker, w);
+        for (auto& t : threads)
+            t.join();
+    }
+    mpiCoordinator.finish();
+    for (const std::string& e : workerErrors)
+        if (!e.empty())
+            mcptFatal(e);
+
+    std::string deviceModel;
+    for (int device : mpiCoordinator.devices()) {
+        int current = device;
+        if (current < 0 && wpt_current_device(&current) != WPT_OK)
+            current = 0;
+        deviceModel += (deviceModel.empty() ? "" : "; ") + std::string(wpt_device_name(current));
+    }
+    const std::string seconds = std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count());
+    auto runTags = [&](ArrayContainer& a) {
+        a.globalTagList().set("WURBLPT/SAMPLES_PER_PIXEL", std::to_string(samplesSqrt * samplesSqrt));
+        a.globalTagList().set("WURBLPT/MAX_PATH_COMPONENTS", std::to_string(params.maxPathComponents));
+        a.globalTagList().set("WURBLPT/RUSSIAN_ROULETTE_THRESHOLD", std::to_string(params.rrThreshold));
+        a.globalTagList().set("WURBLPT/DEVICE_KERNEL", wpt_kernel_name());
+        a.globalTagList().set("WURBLPT/COMPILER", wpt_build_info());
+        a.globalTagList().set("WURBLPT/DEVICE_MODEL", deviceModel);
+        a.globalTagList().set("WURBLPT/DEVICE_COUNT", std::to_string(mpiCoordinator.devices().size()));
+        a.globalTagList().set("WURBLPT/DEVICE_SECONDS", seconds);
+    };
+    runTags(*pixelArray);
+    for (unsigned int g = 0; g < groupCount; g++) {
+        runTags(sensor.group(g));
+        sensor.group(g).globalTagList().set("WURBLPT/LIGHT_GROUP", std::to_string(g));
     }
 }
 

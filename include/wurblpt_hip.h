@@ -389,6 +389,47 @@ wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         float* block_rgb, float* block_bins);
 
+/* ---- light groups: a frame per group of emitters from one render pass ----
+ * One launch renders the frame and group_count planes: plane g holds every contribution whose emitter is in group g.  The
+ * emitter of a contribution is the resolved material of the hit whose emission is evaluated (inside a two-sided material: the
+ * child), for the path's own hits and for the light ray's hit alike; for the environment's contributions it is `env_group`.
+ * Nothing that steers a path reads an emitted radiance, so plane g is bit-identical to the frame of a plain render of the same
+ * description with the emission of every material outside group g set to 0 (v[0] of LIGHT_DIFFUSE / LIGHT_SPOT; v[3] of
+ * MODPHONG with tex[4] = -1, since an emission texture stands in that factor's place), wherever the full frame is finite.  Both gates of `params` apply to the planes as they do to the frame, and the
+ * frame of the launch is the frame of wpt_render_block_device.  The launch is a launch of the transient film's kernels
+ * (wpt_kernel_name() reports them) that chooses a contribution's plane by its emitter instead of by its path length.
+ * `group_of_material`: one byte per material record of the scene, in host memory, each a group below group_count or
+ * WPT_LIGHT_GROUP_NONE (the emitter's light reaches the frame only); `material_count` must be the scene's; `env_group`: a group or
+ * WPT_LIGHT_GROUP_NONE; 1 <= group_count <= WPT_LIGHT_GROUPS_MAX.  A bad table is refused with WPT_ERR_INVALID_ARGUMENT before
+ * anything else is looked at.  The planes cost group_count * width * height * 12 bytes. */
+#define WPT_LIGHT_GROUPS_MAX 255u
+#define WPT_LIGHT_GROUP_NONE 0xffu
+
+/* Asynchronous on `hip_stream`.  `frame_device` (may be NULL): the FULL frame as for wpt_render_block_device;
+ * `planes_device`: float[group_count][height][width][3] in device memory, full frames, row 0 = bottom.  Only the block's
+ * pixels are written, in the frame and in every plane. */
+wpt_status wpt_render_light_groups_block_device(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const uint8_t* group_of_material, uint32_t material_count, uint32_t group_count,
+        uint32_t env_group, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* frame_device, float* planes_device, void* hip_stream);
+
+/* Synchronous form with MPICoordinator::submitBlock semantics: `block_rgb` (may be NULL) receives block_size*3 floats,
+ * `block_planes` group_count*block_size*3 floats (plane g's block_size*3 floats after plane g-1's), both in host memory. */
+wpt_status wpt_render_light_groups_block(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const uint8_t* group_of_material, uint32_t material_count, uint32_t group_count,
+        uint32_t env_group, uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* block_rgb, float* block_planes);
+
+/* Planes mixed into one frame with an RGB weight per plane (a group's intensity and colour, chosen after the render):
+ *   out[p][c] = (((0 + w[0][c] * P0[p][c]) + w[1][c] * P1[p][c]) + ...)   in float, every operation rounded on its own.
+ * `planes_device`: plane k's `pixels` RGB triples start `stride` floats after plane k-1's (light-group planes or the transient
+ * film's bins); `weights_host`: plane_count * 3 floats in host memory; 1 <= plane_count <= WPT_TRANSIENT_MAX_BINS.
+ * Asynchronous on `hip_stream`.  The host form computes the same bits on the CPU and needs no device. */
+wpt_status wpt_postproc_mix_planes(const float* planes_device, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        const float* weights_host, float* out_device, void* hip_stream);
+wpt_status wpt_postproc_mix_planes_host(const float* planes_host, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        const float* weights_host, float* out_host);
+
 /* ---- time-of-flight sensor (amplitude-modulated continuous wave; sensor_tof_amcw.hpp) ----
  * One launch renders phase_count phase images of one exposure interval.  Plane j holds, per pixel, the energies (a_j, b_j, total)
  * that the sensor's two taps and their sum collect with the phase offset tau[j]: every contribution adds

@@ -11,6 +11,7 @@ WPT_OK = 0
 NODE_INNER, NODE_TRIANGLE, NODE_SPHERE, NODE_EMPTY = 0, 1, 2, 3
 MATF_TOF_LIGHT = 16
 TOF_MAX_PHASES = 8
+LIGHT_GROUPS_MAX, LIGHT_GROUP_NONE = 255, 0xff
 MAT_NONE, MAT_LAMBERTIAN, MAT_LIGHT_DIFFUSE, MAT_MIRROR, MAT_GGX, MAT_GLASS, MAT_MODPHONG, MAT_TWOSIDED, MAT_RGL, MAT_LIGHT_SPOT = range(10)
 
 

@@ -408,14 +408,22 @@ template<class PS> WPT_D void accumulateRadiance(const wpt_params& par, f3 opl, 
  * path length lies in [edges[k], edges[k + 1]).  A lane owns its pixel for all its samples (pool and two passes included),
  * so a plain read - add - write of the pixel's values in HBM keeps the order of its contributions and needs no atomics.
  * Plane k, pixel `at`, channel c is bins[k * stride + 3 * at + c]; the launch zeroes the planes before and scales them by
- * 1 / samples after (wpt_capi.hip), as finishPixel does with the frame's accumulator. */
+ * 1 / samples after (wpt_capi.hip), as finishPixel does with the frame's accumulator.
+ * Light groups are the same film under a second rule for the plane (`rule` != 0): plane g takes the light whose emitter is in
+ * group g.  `edges` then is the launch's table of one byte per material record, a group below binCount or BINS_GROUP_NONE, and
+ * the rule's low byte the environment's group. */
 struct BinsView {
-    const float* edges;  /* binCount + 1 increasing floats in device memory; only the last may be +inf */
+    const float* edges;  /* binCount + 1 increasing floats in device memory; only the last may be +inf (light groups: bytes) */
     float* bins;
     size_t stride;       /* floats from one plane to the next */
     uint32_t binCount;
     uint32_t width;      /* of the frame: a pixel's index is y * width + x */
     float guessScale;    /* bins per unit of path length between the first and the last finite edge (0: no guess) */
+    uint32_t rule;       /* 0: plane by path length; BINS_BY_EMITTER | the environment's group: plane by emitter */
+};
+enum : uint32_t {
+    BINS_BY_EMITTER = 0x100u,
+    BINS_GROUP_NONE = 0xffu            /* an emitter of no group: its light reaches the frame only */
 };
 
 /* the k with edges[k] <= x < edges[k + 1], or -1.  The guess from the uniform spacing is taken when the edges confirm it,
@@ -468,9 +476,23 @@ template<uint32_t F> WPT_D bool isTofLight(const wpt_material& m)
         return false;
 }
 
+/* the resolved material that emitted, for the kernels whose film asks who did (the others pass nothing); its record's index
+ * is taken where the film needs it, under the light-groups rule only */
+template<uint32_t F> WPT_D const wpt_material* emitterOf(const wpt_material& m)
+{
+    if constexpr ((F & FEAT_TRANSIENT) != 0)
+        return &m;
+    else
+        return nullptr;
+}
+
 /* Sensor::accumulateRadiance of the launch: the frame's accumulator as above and, in FEAT_TRANSIENT kernels, the bins --
  * behind the same distance gate, by each channel's own path length (the path-length gate of `par` is the frame's only).
  * Where the three channels' lengths are equal (everything but dispersive glass) the bin is looked up once.
+ * Under the light-groups rule (bv.rule, the same word in every lane) the plane is the group of `emitter`'s record and both gates of `par`
+ * apply, channel by channel, as in accumulateRadiance: the plane's additions are those of the frame of a scene in which only that
+ * group emits.  A contribution of three zeros is left out (every hit that is no light makes one): it would add 0 to a sum that
+ * started at +0 and so is never -0, and the plane keeps its bits, as in the time-of-flight branch below.
  *
  * FEAT_TOF kernels: SensorTofAmcw::accumulateRadiance (wpt_tof.h).  `opl.x` is the fourth channel of the optical path length,
  * `tofLight` says whether the hit that emitted is a ToF light's (Material::isTofLight of the resolved material); no gate.  The
@@ -479,7 +501,7 @@ template<uint32_t F> WPT_D bool isTofLight(const wpt_material& m)
  * live in `bins` like the transient film's planes, [phase][pixel][a, b, total], each plane fed by the very operations of the
  * one-phase launch with its tau (the cosine is evaluated per phase; `total` is the same sequence of additions in every plane). */
 template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, const BinsView& bv, f3 opl, float distanceToLight, f4 radiance, PS& ps,
-        bool tofLight = false)
+        bool tofLight = false, const wpt_material* emitter = nullptr, const wpt_material* materials = nullptr)
 {
     if constexpr ((F & FEAT_TOF) != 0) {
         const float* const c = bv.edges;
@@ -533,6 +555,22 @@ template<uint32_t F, class PS> WPT_D void accumulate(const wpt_params& par, cons
             return;
         const uint32_t pxy = ps.getW(SLOT_SRDIR);
         float* const px = bv.bins + 3 * ((size_t)(pxy >> 16) * bv.width + (pxy & 0xffffu));
+        if (__builtin_expect(bv.rule != 0, 0)) {
+            if (radiance.x == 0.0f && radiance.y == 0.0f && radiance.z == 0.0f)
+                return;
+            /* no emitter: the environment's light */
+            const uint32_t g = emitter ? reinterpret_cast<const uint8_t*>(bv.edges)[emitter - materials] : (bv.rule & 0xffu);
+            if (g == BINS_GROUP_NONE)
+                return;
+            float* const p = px + (size_t)g * bv.stride;
+            if (opl.x >= par.min_path_len && opl.x <= par.max_path_len)
+                p[0] += radiance.x;
+            if (opl.y >= par.min_path_len && opl.y <= par.max_path_len)
+                p[1] += radiance.y;
+            if (opl.z >= par.min_path_len && opl.z <= par.max_path_len)
+                p[2] += radiance.z;
+            return;
+        }
         const int kx = binOf(bv, opl.x);
         if (opl.y == opl.x && opl.z == opl.x) {
             if (kx >= 0) {
@@ -777,7 +815,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
     const f4 att = ps.get4(SLOT_ATT);
     {
         f4 rad = mul(att, materialEmitted<F>(sv, m, h, ray.d));
-        accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps, isTofLight<F>(m));
+        accumulate<F>(par, bins, opl, (pathComponent == 0 ? 0.0f : h.a), rad, ps, isTofLight<F>(m), emitterOf<F>(m), sv.materials);
     }
     section(2);
     if (sr.type == SCATTER_NONE) {
@@ -910,7 +948,7 @@ WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS&
             f4 rad = mul(neeFactorOf<F>(nee), materialEmitted<F>(sv, lm, lh, ps.d));
             const f4 ri = ps.get4(SLOT_RI);
             f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, sensorChannels<F>(ri)));
-            accumulate<F>(par, bins, oplLight, lh.a, rad, ps, isTofLight<F>(lm));
+            accumulate<F>(par, bins, oplLight, lh.a, rad, ps, isTofLight<F>(lm), emitterOf<F>(lm), sv.materials);
         }
     } else if (F & FEAT_ENVMAP) {
         if (best.prim == NO_HIT) {

@@ -24,6 +24,7 @@
 #include "wpt_scene_layout.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
+#include "wpt_lightmix.h"
 #include "wpt_progress.h"
 #include "wpt_progress_state.h"
 
@@ -1452,6 +1453,78 @@ wpt_status transientLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt
     return planesLaunch(rq, edges, size_t(binCount) + 1, true, "transient film");
 }
 
+/* refuses a bad light-groups table; fills what the kernels need of a good one but the device copy of the table */
+wpt_status lightGroupsTable(const uint8_t* groupOfMaterial, uint32_t materialCount, uint32_t groupCount, uint32_t envGroup, wptk::BinsView& bv)
+{
+    uint32_t at = 0;
+    switch (wptmix::checkTable(groupOfMaterial, materialCount, groupCount, envGroup, &at)) {
+    case wptmix::TABLE_OK:
+        break;
+    case wptmix::TABLE_NULL:
+        return fail(WPT_ERR_INVALID_ARGUMENT, "light groups: the table of the materials' groups is NULL");
+    case wptmix::TABLE_GROUP_COUNT:
+        return fail(WPT_ERR_INVALID_ARGUMENT, "light groups: group count must lie in 1 .. " + std::to_string(WPT_LIGHT_GROUPS_MAX));
+    case wptmix::TABLE_ENTRY:
+        return fail(WPT_ERR_INVALID_ARGUMENT, "light groups: material " + std::to_string(at) + " has group " + std::to_string(groupOfMaterial[at])
+                + ", which is neither below the group count " + std::to_string(groupCount) + " nor WPT_LIGHT_GROUP_NONE");
+    case wptmix::TABLE_ENV_GROUP:
+        return fail(WPT_ERR_INVALID_ARGUMENT, "light groups: the environment's group " + std::to_string(envGroup)
+                + " is neither below the group count " + std::to_string(groupCount) + " nor WPT_LIGHT_GROUP_NONE");
+    }
+    bv = wptk::BinsView{};
+    bv.binCount = groupCount;
+    bv.rule = wptk::BINS_BY_EMITTER | envGroup;
+    return WPT_OK;
+}
+
+/* one light-groups launch: a launch of the transient film's kernels whose BinsView says "plane by emitter"; `planes` and
+ * `stride` as planesLaunch takes them.  The table travels as the sensor's words, padded to whole floats with NONE. */
+wpt_status lightGroupsLaunch(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const uint8_t* groupOfMaterial,
+        uint32_t materialCount, uint32_t groupCount, uint32_t envGroup, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        uint32_t block_start, uint32_t block_size, float* frame, float* planes, size_t stride, hipStream_t stream)
+{
+    LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, block_start, block_size, frame, stream };
+    WPT_TRY(lightGroupsTable(groupOfMaterial, materialCount, groupCount, envGroup, rq.bins));
+    if (!scene || !camera || !params || !planes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (materialCount != uint32_t(scene->view.materialCount))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "light groups: the table has " + std::to_string(materialCount) + " materials, the scene "
+                + std::to_string(uint32_t(scene->view.materialCount)));
+    const wpt_status inFrame = checkFrameBlock(width, height, &samples_sqrt, block_start, block_size);
+    if (inFrame != WPT_OK || block_size == 0)
+        return inFrame;
+    rq.sensor = wptk::SENSOR_TRANSIENT;
+    rq.bins.bins = planes;
+    rq.bins.stride = stride;
+    rq.bins.width = width;
+    std::vector<float> words((size_t(materialCount) + 3) / 4 + 1);
+    memset(words.data(), 0xff, words.size() * sizeof(float));
+    memcpy(words.data(), groupOfMaterial, materialCount);
+    return planesLaunch(rq, words.data(), words.size(), true, "light groups");
+}
+
+/* the mix of planes (wpt_lightmix.h): one thread per value */
+__global__ void wpt_lightmix_kernel(const float* planes, uint32_t planeCount, size_t stride, uint64_t values, const float* weights, float* out)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < values)
+        out[i] = wptmix::mixValue(planes, planeCount, stride, weights, size_t(i));
+}
+
+/* what a mix is refused for, on the device or on the host */
+wpt_status mixCheck(const void* planes, uint32_t planeCount, uint64_t stride, uint64_t pixels, const void* weights, const void* out)
+{
+    if (!planes || !weights || !out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mix of planes: NULL argument");
+    if (planeCount == 0 || planeCount > wptmix::PLANES_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mix of planes: plane count must lie in 1 .. " + std::to_string(uint32_t(wptmix::PLANES_MAX)));
+    if (pixels == 0 || pixels > 0x7fffffffull * 256ull / 3)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mix of planes: bad pixel count");
+    if (planeCount > 1 && stride < pixels * 3)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mix of planes: the planes overlap (stride below pixels * 3)");
+    return WPT_OK;
+}
+
 /* what a batch of views is refused for before anything needs the scene or a device */
 wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void* frames, uint32_t width, uint32_t height)
 {
@@ -1558,6 +1631,63 @@ wpt_status wpt_render_transient_block(wpt_scene* scene, const wpt_camera* camera
         return fail(WPT_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
     return finishStaged(transientLaunch(scene, camera, params, edges_host, bin_count, width, height, samples_sqrt, block_start, block_size,
             block.biased(block_start), bins.biased(block_start), size_t(block_size) * 3, nullptr), scene, block, block_rgb, &bins, block_bins);
+}
+
+wpt_status wpt_render_light_groups_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const uint8_t* group_of_material, uint32_t material_count, uint32_t group_count, uint32_t env_group, uint32_t width, uint32_t height,
+        uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* frame_device, float* planes_device, void* hip_stream)
+{
+    return lightGroupsLaunch(scene, camera, params, group_of_material, material_count, group_count, env_group, width, height, samples_sqrt,
+            block_start, block_size, frame_device, planes_device, size_t(width) * height * 3, static_cast<hipStream_t>(hip_stream));
+}
+
+wpt_status wpt_render_light_groups_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        const uint8_t* group_of_material, uint32_t material_count, uint32_t group_count, uint32_t env_group, uint32_t width, uint32_t height,
+        uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_rgb, float* block_planes)
+{
+    wptk::BinsView bv;
+    WPT_TRY(lightGroupsTable(group_of_material, material_count, group_count, env_group, bv));
+    if (!block_planes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "block_planes is NULL");
+    if (block_size == 0)
+        return WPT_OK;
+    StagedBlock block, planes;
+    if (block_rgb)
+        HIP_TRY(block.allocatePixels(block_size));
+    const hipError_t e = planes.allocatePixels(block_size, group_count);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return finishStaged(lightGroupsLaunch(scene, camera, params, group_of_material, material_count, group_count, env_group, width, height,
+            samples_sqrt, block_start, block_size, block.biased(block_start), planes.biased(block_start), size_t(block_size) * 3, nullptr),
+            scene, block, block_rgb, &planes, block_planes);
+}
+
+wpt_status wpt_postproc_mix_planes(const float* planes_device, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        const float* weights_host, float* out_device, void* hip_stream)
+{
+    WPT_TRY(mixCheck(planes_device, plane_count, stride, pixels, weights_host, out_device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const size_t weightBytes = size_t(plane_count) * 3 * sizeof(float);
+    float* dWeights = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dWeights), weightBytes, stream));
+    hipError_t e = hipMemcpyAsync(dWeights, weights_host, weightBytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(wpt_lightmix_kernel, dim3(uint32_t((pixels * 3 + 255) / 256)), dim3(256), 0, stream, planes_device, plane_count,
+                size_t(stride), pixels * 3, dWeights, out_device);
+        e = hipGetLastError();
+    }
+    (void)hipFreeAsync(dWeights, stream);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("mix of planes: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_mix_planes_host(const float* planes_host, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        const float* weights_host, float* out_host)
+{
+    WPT_TRY(mixCheck(planes_host, plane_count, stride, pixels, weights_host, out_host));
+    wptmix::mixHost(planes_host, plane_count, size_t(stride), pixels, weights_host, out_host);
+    return WPT_OK;
 }
 
 wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,

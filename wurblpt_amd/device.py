@@ -24,6 +24,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
+           "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
            "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
@@ -65,6 +66,15 @@ def lib():
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_transient_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(L, "wpt_render_light_groups_block"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_render_light_groups_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p,
+                                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_render_light_groups_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p,
+                                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_mix_planes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_mix_planes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
         L.wpt_render_views_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
@@ -132,6 +142,62 @@ def _edges_array(edges):
     e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32))
     assert e.ndim == 1 and e.size >= 2, "bin edges: at least two values"
     return e
+
+
+def _groups_table(groups, material_count):
+    """uint8 copy of a light-groups table (one group per material record, or _abi.LIGHT_GROUP_NONE) for the C ABI"""
+    import numpy as np
+    a = np.asarray(groups)
+    if a.dtype.kind not in "iub" or a.ndim != 1:
+        raise TypeError("light groups: one integer per material")
+    if a.size != material_count:
+        raise ValueError("light groups: the table has %d entries, the scene %d materials" % (a.size, material_count))
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 255):
+        raise ValueError("light groups: a group is a byte (0 .. 254, or %d for none)" % _abi.LIGHT_GROUP_NONE)
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def _mix_weights(weights, plane_count):
+    """float32 [K, 3] of a mix's weights: an RGB triple per plane, or one number per plane for all three channels"""
+    import numpy as np
+    w = np.asarray(weights, dtype=np.float32)
+    if w.ndim == 1:
+        w = np.repeat(w[:, None], 3, axis=1)
+    if w.shape != (plane_count, 3):
+        raise ValueError("mix_planes: %d planes need weights [%d, 3] or [%d]" % (plane_count, plane_count, plane_count))
+    return np.ascontiguousarray(w)
+
+
+def mix_planes(planes, weights, out=None, stream=None):
+    """wpt_postproc_mix_planes: CUDA float32 planes [K, ..., 3] (a light-groups launch's or the transient film's) mixed into one
+    frame [..., 3], out[p][c] = (((0 + w[0][c] * P0[p][c]) + w[1][c] * P1[p][c]) + ...) in float32, each operation rounded on
+    its own.  `weights`: [K, 3] or [K].  Asynchronous on `stream` (default: torch's current stream); returns `out`."""
+    import torch
+    assert planes.is_cuda and planes.is_contiguous() and planes.dtype == torch.float32 and planes.dim() >= 3 and planes.shape[-1] == 3
+    K = planes.shape[0]
+    w = _mix_weights(weights, K)
+    if out is None:
+        out = torch.empty(tuple(planes.shape[1:]), dtype=torch.float32, device=planes.device)
+    pixels = planes[0].numel() // 3
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == pixels * 3
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _check(lib().wpt_postproc_mix_planes(C.c_void_p(planes.data_ptr()), K, pixels * 3, pixels, C.c_void_p(w.ctypes.data),
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def mix_planes_host(planes, weights):
+    """wpt_postproc_mix_planes_host: the same mix of numpy planes [K, ..., 3] on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    p = np.ascontiguousarray(planes, dtype=np.float32)
+    assert p.ndim >= 3 and p.shape[-1] == 3
+    K = p.shape[0]
+    w = _mix_weights(weights, K)
+    out = np.zeros(p.shape[1:], np.float32)
+    pixels = out.size // 3
+    _check(lib().wpt_postproc_mix_planes_host(C.c_void_p(p.ctypes.data), K, pixels * 3, pixels, C.c_void_p(w.ctypes.data),
+                                              C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def _map_int(samples_sqrt):
@@ -597,6 +663,62 @@ class DeviceScene:
         _check(lib().wpt_render_transient_block(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K, w, h,
                                                 samples_sqrt, start, size, C.c_void_p(rgb.ctypes.data), C.c_void_p(bins.ctypes.data)))
         return rgb, bins
+
+    def render_light_groups_into(self, frame, planes, samples_sqrt, groups, group_count, env_group=_abi.LIGHT_GROUP_NONE, block=None,
+                                 params=None, stream=None, width=None, height=None):
+        """Asynchronously renders pixels [start, start+size) of the frame and of a plane per group of emitters in one launch.
+        `frame`: CUDA float32 tensor [h, w, 3] or None; `planes`: CUDA float32 tensor [K, h, w, 3] (full frames), K = group_count;
+        `groups`: one integer per material record of the scene (host.emitters lists those that emit), a group below K or
+        _abi.LIGHT_GROUP_NONE; `env_group`: the environment's.  Plane g is bit for bit the plain render of the scene in which
+        only group g emits (host.mute_emitters); both gates of `params` apply to the planes as to the frame."""
+        from . import host
+        w = width or self.host.width
+        h = height or self.host.height
+        t = _groups_table(groups, self.host.d.material_count)
+        K = int(group_count)
+        assert planes.is_cuda and planes.is_contiguous() and planes.dtype.is_floating_point and planes.element_size() == 4 \
+            and planes.numel() == K * w * h * 3
+        if frame is not None:
+            assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
+        p = params if params is not None else host.default_params()
+        start, size = block if block is not None else (0, w * h)
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
+        _check(lib().wpt_render_light_groups_block_device(self._handle, self.host.camera, C.byref(p), C.c_void_p(t.ctypes.data), t.size, K,
+                                                           int(env_group), w, h, samples_sqrt, start, size, fptr,
+                                                           C.c_void_p(planes.data_ptr()), sptr))
+
+    def render_light_groups(self, samples_sqrt, groups, group_count, env_group=_abi.LIGHT_GROUP_NONE, block=None, params=None,
+                            width=None, height=None):
+        """Synchronous convenience: returns (frame [h, w, 3], planes [K, h, w, 3]) as numpy arrays."""
+        import torch
+        w = width or self.host.width
+        h = height or self.host.height
+        frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        planes = torch.zeros((int(group_count), h, w, 3), dtype=torch.float32, device="cuda")
+        self.render_light_groups_into(frame, planes, samples_sqrt, groups, group_count, env_group, block, params,
+                                      torch.cuda.current_stream(), w, h)
+        torch.cuda.synchronize()
+        self.check()
+        return frame.cpu().numpy(), planes.cpu().numpy()
+
+    def render_light_groups_host(self, samples_sqrt, groups, group_count, block, env_group=_abi.LIGHT_GROUP_NONE, params=None,
+                                 width=None, height=None):
+        """wpt_render_light_groups_block: submitBlock semantics; returns (block rgb [size, 3], block planes [K, size, 3])."""
+        import numpy as np
+        from . import host
+        w = width or self.host.width
+        h = height or self.host.height
+        t = _groups_table(groups, self.host.d.material_count)
+        K = int(group_count)
+        p = params if params is not None else host.default_params()
+        start, size = block
+        rgb = np.zeros((size, 3), dtype=np.float32)
+        planes = np.zeros((K, size, 3), dtype=np.float32)
+        _check(lib().wpt_render_light_groups_block(self._handle, self.host.camera, C.byref(p), C.c_void_p(t.ctypes.data), t.size, K,
+                                                    int(env_group), w, h, samples_sqrt, start, size, C.c_void_p(rgb.ctypes.data),
+                                                    C.c_void_p(planes.ctypes.data)))
+        return rgb, planes
 
     def render_tof_into(self, planes, samples_sqrt, sensor, phases=None, block=None, params=None, stream=None):
         """Asynchronously renders pixels [start, start+size) of the time-of-flight sensor's phase images in one launch.

@@ -284,6 +284,82 @@ def spot_scene(width, height, variant=0):
     return HostScene(L.wpt_host_spot_scene(variant, width, height), width, height, "spot_scene(variant=%d)" % variant)
 
 
+def light_groups_scene(width, height, variant=0, t0=0.0, t1=0.0, dispersive=False):
+    """Scenes with several emitters for the light-groups launch (DeviceScene.render_light_groups).  0 = a closed box of
+    Lambertian walls with a GGX and a glass cube under two diffuse ceiling lamps of different colour, both hot spots (small
+    enough for the kernels that keep the scene in LDS); 1 = variant 0's room and lamps plus a two-sided spot lamp, a ModPhong
+    panel whose emission has a checker texture, a sphere lamp that is a hot spot, and an equirect environment without
+    importance tables (N = 0) seen through the open front; 2 = two lamps, one of them moving on key frames, over a swinging
+    panel, bounded for the exposure interval [t0, t1] (pass the same t0, t1 in the render parameters); 3 = two lamps over two
+    plates with the measured BRDFs of the committed fixtures (rgl_fixture).  dispersive (variant 0 only): the glass cube has a
+    refractive index per channel, so the channels' optical path lengths differ."""
+    L = lib()
+    L.wpt_host_light_groups_scene.restype = C.c_void_p
+    L.wpt_host_light_groups_scene.argtypes = [C.c_int, C.c_float, C.c_float, C.c_char_p, C.c_char_p, C.c_uint, C.c_uint]
+    h = L.wpt_host_light_groups_scene(variant | (16 if dispersive else 0), t0, t1, rgl_fixture("iso").encode(),
+                                      rgl_fixture("aniso").encode(), width, height)
+    return HostScene(h, width, height, "light_groups_scene(variant=%d)" % variant)
+
+
+def _emission(m):
+    """the four floats of a material record that scale its emission, or None for a record that never emits"""
+    if m.type in (_abi.MAT_LIGHT_DIFFUSE, _abi.MAT_LIGHT_SPOT):
+        return m.v[0]
+    if m.type == _abi.MAT_MODPHONG:
+        return m.v[3]
+    return None
+
+
+def emitters(scene):
+    """The indices of the scene's material records that emit: LIGHT_DIFFUSE, LIGHT_SPOT and MODPHONG records whose emission
+    factor (v[0], v[3]) is not all zero, and MODPHONG records with an emission texture (tex[4], which stands in the factor's
+    place).  A two-sided material's record is not one; its children are."""
+    d = scene.d
+    out = []
+    for i in range(d.material_count):
+        m = d.materials[i]
+        e = _emission(m)
+        if e is not None and (any(float(x) != 0.0 for x in e) or (m.type == _abi.MAT_MODPHONG and m.tex[4] >= 0)):
+            out.append(i)
+    return out
+
+
+def mute_emitters(scene, keep):
+    """Zeroes IN PLACE the emission factor of every emitting material record whose index is not in `keep`: the muted twin of the
+    scene for the group `keep`.  A MODPHONG record's emission texture stands in its factor's place, so the record lets go of it
+    (tex[4] = -1) and emits the zeroed factor.  Texture records stay as they are.  The environment is not a material; it stays
+    too (mute_environment)."""
+    keep = set(int(k) for k in keep)
+    d = scene.d
+    for i in emitters(scene):
+        if i not in keep:
+            m = d.materials[i]
+            e = _emission(m)
+            for c in range(4):
+                e[c] = 0.0
+            if m.type == _abi.MAT_MODPHONG:
+                m.tex[4] = -1
+    return scene
+
+
+def mute_environment(scene):
+    """Zeroes IN PLACE the value factor and offset of the environment map's textures (a constant's or a checker's colours): the
+    environment of a muted twin.  Only where that changes no table: a scene with hot spots never samples the environment by
+    importance, and one with N = 0 has no tables; anything else raises ValueError."""
+    d = scene.d
+    e = d.envmap
+    if e.type == 0:
+        return scene
+    if e.N > 0 and d.hotspot_count == 0:
+        raise ValueError("mute_environment: the environment's importance tables would change")
+    for t in ([e.tex] if e.type == 1 else list(e.cube_tex)):
+        tex = d.textures[t]  # (a transformer's own factor and offset: its child may belong to a material as well)
+        for c in range(4):
+            tex.a[c] = 0.0
+            tex.b[c] = 0.0
+    return scene
+
+
 def rgl_fixture(name):
     """path of a synthetic measured-BRDF file committed under tests/golden (iso / aniso)"""
     return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "synthetic_%s.bsdf" % name)

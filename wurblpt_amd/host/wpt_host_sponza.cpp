@@ -719,3 +719,94 @@ extern "C" wpt_host_scene* wpt_host_rgl_scene(int variant, const char* file0, co
     scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(0.0f, 4.0f, 1.0f), toQuat(radians(90.0f), vec3(1.0f, 0.0f, 0.0f)), vec3(0.7f, 0.7f, 1.0f)), 1)), light), HotSpot);
     return wptHostFinish(scenePtr, width, height, radians(45.0f), vec3(0.0f, 2.0f, 6.0f), vec3(0.0f, 0.7f, 0.0f), 0.0f, 1.0f);
 }
+
+/* Scenes with several emitters for the light-groups launch (wpt_render_light_groups_block).  The room of all four: floor, ceiling,
+ * back and side walls of a 2 x 2 x 2 box open towards the camera, meshes with their transformation applied.
+ *   0  a GGX and a glass cube under two diffuse ceiling lamps of different colour, both hot spots: Lambertian, GGX, glass and
+ *      diffuse lights only, and small enough for the kernels that keep the scene in LDS.  | 16: the glass has a refractive index
+ *      per channel (chromatic dispersion, as the Cornell box's third short-box material): the channels' path lengths differ
+ *   1  variant 0 plus a two-sided spot lamp on the back wall, a ModPhong panel whose emission has a checker texture, a sphere lamp
+ *      that is a hot spot, and an equirect environment of float texels without importance tables (N = 0)
+ *   2  two ceiling lamps, one sliding on key frames, over a swinging two-sided panel and a GGX cube, for the exposure interval
+ *      [t0, t1]; the camera stands still
+ *   3  two ceiling lamps over two plates with the measured BRDFs of `rgl0` and `rgl1` */
+extern "C" wpt_host_scene* wpt_host_light_groups_scene(int variant, float t0, float t1, const char* rgl0, const char* rgl1,
+        unsigned int width, unsigned int height)
+{
+    const bool dispersive = (variant & 16) != 0;
+    variant &= ~16;
+    if (variant < 0 || variant > 3 || (dispersive && variant != 0)) {
+        fprintf(stderr, "wpt_host: light groups scene variant %d is not known\n", variant);
+        return nullptr;
+    }
+    Scene* scenePtr = new Scene;
+    Scene& scene = *scenePtr;
+    const vec3 xAxis(1.0f, 0.0f, 0.0f), yAxis(0.0f, 1.0f, 0.0f);
+    Material* white = scene.take(new MaterialLambertian(vec3(0.73f, 0.72f, 0.69f)));
+    Material* red = scene.take(new MaterialLambertian(vec3(0.6f, 0.1f, 0.08f)));
+    Material* blue = scene.take(new MaterialLambertian(vec3(0.12f, 0.2f, 0.55f)));
+    auto wall = [&](Material* m, const vec3& where, float degrees, const vec3& axis) {
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(where, toQuat(radians(degrees), axis), vec3(1.0f)))), m));
+    };
+    wall(white, vec3(0.0f, 0.0f, 0.0f), -90.0f, xAxis);
+    wall(white, vec3(0.0f, 2.0f, 0.0f), +90.0f, xAxis);
+    wall(white, vec3(0.0f, 1.0f, -1.0f), 0.0f, yAxis);
+    wall(red, vec3(-1.0f, 1.0f, 0.0f), +90.0f, yAxis);
+    wall(blue, vec3(+1.0f, 1.0f, 0.0f), -90.0f, yAxis);
+    /* the two ceiling lamps of every variant: warm on the left, cool on the right, facing down */
+    Material* warm = scene.take(new LightDiffuse(vec3(9.0f, 6.0f, 3.0f)));
+    Material* cool = scene.take(new LightDiffuse(vec3(2.5f, 4.0f, 8.0f)));
+    const quat down = toQuat(radians(90.0f), xAxis);
+    scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(-0.5f, 1.98f, -0.1f), down, vec3(0.22f)))), warm), HotSpot);
+    if (variant != 2)
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(+0.5f, 1.98f, 0.2f), down, vec3(0.25f, 0.18f, 1.0f)))), cool), HotSpot);
+    if (variant == 0 || variant == 1) {
+        Material* metal = scene.take(new MaterialGGX(vec3(0.95f, 0.85f, 0.6f), vec2(0.12f)));
+        Material* glass = dispersive ? scene.take(new MaterialGlass(vec4(0.2f), vec4(1.46f, 1.5f, 1.54f, 1.5f)))
+                                     : scene.take(new MaterialGlass(vec3(0.15f), 1.5f));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(-0.4f, 0.35f, -0.3f), toQuat(radians(20.0f), yAxis), vec3(0.3f, 0.35f, 0.3f)))), metal));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(0.45f, 0.3f, 0.25f), toQuat(radians(-15.0f), yAxis), vec3(0.28f, 0.3f, 0.28f)))), glass));
+    }
+    if (variant == 1) {
+        Material* spot = scene.take(new MaterialTwoSided(scene.take(new LightSpot(radians(50.0f), vec3(6.0f, 6.0f, 4.5f))),
+                    scene.take(new MaterialLambertian(vec3(0.0f)))));
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(0.0f, 1.5f, -0.98f), quat::null(), vec3(0.2f)))), spot), HotSpot);
+        MaterialModPhong* panel = new MaterialModPhong(vec3(0.4f, 0.4f, 0.35f), vec3(0.2f), 40.0f);
+        panel->emissive = vec4(1.5f, 0.6f, 2.0f, 0.0f);
+        panel->emissiveTex = scene.take(new TextureChecker(vec3(1.0f, 0.9f, 0.8f), vec3(0.15f, 0.3f, 0.1f), 4, 3));
+        scene.take(panel);
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(-0.98f, 0.9f, 0.2f), toQuat(radians(90.0f), yAxis), vec3(0.35f, 0.3f, 1.0f)))), panel));
+        Material* bulb = scene.take(new LightDiffuse(vec3(3.0f, 7.0f, 3.5f)));
+        scene.take(new Sphere(vec3(0.05f, 1.15f, 0.45f), 0.1f, bulb), HotSpot);
+        unsigned int state = 97531u;
+        auto next = [&state]() { state = state * 1664525u + 1013904223u; return state >> 8; };
+        Array<float> sky(16, 8, 3);
+        for (size_t i = 0; i < sky.elementCount(); i++)
+            for (int c = 0; c < 3; c++)
+                sky[i][c] = 0.1f + float(next() & 0xffffu) * (1.0f / 65536.0f) * (0.4f + 0.3f * c);
+        scene.take(new EnvironmentMapEquiRect(scene.take(createTextureImage(sky, LinearizeSRGB_Off)))); /* no importance sampling: N = 0 */
+    }
+    if (variant == 2) {
+        AnimationKeyframes* lampMotion = new AnimationKeyframes(0.0f, Transformation(vec3(0.2f, 1.95f, 0.3f), down, vec3(0.25f, 0.18f, 1.0f)),
+                1.0f, Transformation(vec3(0.75f, 1.9f, -0.2f), toQuat(radians(75.0f), vec3(1.0f, 0.1f, 0.0f)), vec3(0.25f, 0.18f, 1.0f)));
+        AnimationKeyframes* panelMotion = new AnimationKeyframes(0.0f, Transformation(vec3(0.3f, 0.8f, -0.4f), toQuat(radians(-25.0f), vec3(0.0f, 0.0f, 1.0f)), vec3(0.4f)),
+                1.0f, Transformation(vec3(0.3f, 0.8f, -0.4f), toQuat(radians(35.0f), vec3(0.0f, 0.0f, 1.0f)), vec3(0.4f)));
+        const int lampAnim = scene.take(lampMotion);
+        const int panelAnim = scene.take(panelMotion);
+        Material* metal = scene.take(new MaterialGGX(vec3(0.95f, 0.85f, 0.6f), vec2(0.15f)));
+        Material* panel = scene.take(new MaterialTwoSided(scene.take(new MaterialLambertian(vec3(0.7f, 0.65f, 0.3f))), blue));
+        scene.take(new MeshInstance(scene.take(generateCube(Transformation(vec3(-0.45f, 0.3f, 0.0f), toQuat(radians(25.0f), yAxis), vec3(0.3f)))), metal));
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(), 2)), panel, panelAnim));
+        scene.take(new MeshInstance(scene.take(generateQuad()), cool, lampAnim), HotSpot);
+        AnimationKeyframes* cameraStill = new AnimationKeyframes;
+        cameraStill->addKeyframe(0.0f, Transformation::fromLookAt(vec3(0.0f, 1.0f, 3.6f), vec3(0.0f, 0.9f, 0.0f), yAxis));
+        return wptHostFinishAnimated(scenePtr, width, height, radians(45.0f), cameraStill, t0, t1, 0.0f, 3.0f);
+    }
+    if (variant == 3) {
+        Material* plate0 = scene.take(new MaterialRGL(rgl0), "measured-plate-0");
+        Material* plate1 = scene.take(new MaterialRGL(rgl1), "measured-plate-1");
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(-0.45f, 0.35f, 0.0f), toQuat(radians(-60.0f), xAxis), vec3(0.4f, 0.5f, 1.0f)))), plate0));
+        scene.take(new MeshInstance(scene.take(generateQuad(Transformation(vec3(+0.45f, 0.35f, 0.1f), toQuat(radians(-70.0f), xAxis), vec3(0.4f, 0.5f, 1.0f)))), plate1));
+    }
+    return wptHostFinish(scenePtr, width, height, radians(45.0f), vec3(0.0f, 1.0f, 3.6f), vec3(0.0f, 0.9f, 0.0f), 0.0f, 1.0f);
+}
