@@ -693,13 +693,17 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
  *                           compute unit, and a test reads them in its ray's order: wpt_kernel_form)
  *   WPT_WALK_NO_FOLD        the kernels with the scene in LDS keep every node's own first child in their copy of the tree (A/B
  *                           runs and tests; by default a first child whose box is its parent's bit for bit is folded into the
- *                           parent's link, because its box test repeats the parent's on the same inputs: wpt_fold.h) */
+ *                           parent's link, because its box test repeats the parent's on the same inputs: wpt_fold.h); the
+ *                           links that go round nodes are built on the fold, so this flag keeps those away too
+ *   WPT_WALK_NO_BYPASS      the kernels with the scene in LDS test every node of the folded tree (A/B runs and tests; by default
+ *                           links that lead to an inner node of the scene's plan, wpt_bypass_plan below, lead to its first child) */
 #define WPT_WALK_WIDE 1u
 #define WPT_WALK_FULL_SHADOW 2u
 #define WPT_WALK_COUNT_PRODUCT 4u
 #define WPT_WALK_TRIANGLES_AS_GIVEN 8u
 #define WPT_WALK_SELECT_CORNERS 16u
 #define WPT_WALK_NO_FOLD 32u
+#define WPT_WALK_NO_BYPASS 64u
 wpt_status wpt_set_walk(uint32_t flags);
 /* Nodes whose link the kernels with the scene in LDS fold in their copy of the tree: inner nodes that go past one or more inner
  * first children with their own box.
@@ -710,6 +714,19 @@ wpt_status wpt_set_walk(uint32_t flags);
  *                           the words are those of the description's own depth-first order with its own triangle indices */
 wpt_status wpt_scene_folded_links(const wpt_scene* scene, uint32_t* folded);
 wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t* lds_words);
+/* Inner nodes that the walk of a scene in LDS leaves out (wpt_bypass.h): a node whose children's boxes lie within its own almost
+ * always passes its test, and a ray that fails it fails its children as well, so every link that led to it leads to its first
+ * child instead -- for rays whose slab distances are numbers; the others, and trees with a NaN bound, walk the fold's links.
+ * Which of the eligible nodes go is chosen at the upload by a cost model over a fixed sample of rays made from the scene.
+ *   wpt_scene_bypassed_nodes  nodes left out of an uploaded scene's walk (0 for a scene that does not fit LDS)
+ *   wpt_bypass_plan           the same count from a description, a pure function that needs no device (0 for a scene that does
+ *                             not fit LDS); words (or NULL): 2 * node_count + 1 words -- per node its skip link and word 7 of its
+ *                             copy in LDS as wpt_fold_plan gives it, both led past the nodes left out, then the node a ray starts at
+ *   wpt_set_bypass            tests: 0 = the cost model chooses (default), 1 = every eligible node is left out; read at the upload
+ *                             and by wpt_bypass_plan (process-global like the hooks above) */
+wpt_status wpt_scene_bypassed_nodes(const wpt_scene* scene, uint32_t* count);
+wpt_status wpt_bypass_plan(const wpt_scene_desc* desc, uint32_t* count, uint32_t* words);
+wpt_status wpt_set_bypass(uint32_t mode);
 /* Pixels in slices (results do not depend on it; process-global like the hooks above).  A pooled, plain product launch of the
  * kernels with the scene in LDS cuts every pixel into `units` units of `rows` rows of strata and hands out all first units,
  * then all second units, and so on, each time in the frame's own order, in one launch: the work that is left when the pool

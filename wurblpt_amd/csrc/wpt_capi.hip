@@ -22,6 +22,7 @@
 #include "wpt_kernel_table.h"
 #include "wpt_launch_plan.h"
 #include "wpt_scene_layout.h"
+#include "wpt_bypass.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
@@ -280,6 +281,10 @@ struct wpt_scene {
     uint32_t features;
     uint32_t nodeCount, triCount;
     uint32_t foldedLinks; /* wpt_scene_folded_links */
+    /* a scene that fits LDS: the link words of its tree's copy there (wpt_bypass.h, Plan), three arrays of 2 * nodeCount + 4
+     * words one behind the other -- plain, folded, bypass -- and the inner nodes the last one leaves out; else NULL */
+    uint32_t* ldsLinks = nullptr;
+    uint32_t bypassedNodes = 0; /* wpt_scene_bypassed_nodes */
     uint32_t animationCount;
     std::vector<void*> allocations;
     int cuCount;
@@ -307,6 +312,8 @@ uint32_t g_wfMode = 0;
 wptk::WfConfig g_wfConfig = { 0, 0, 0, 1, 0, 0, 0, 0, 0 };
 /* wpt_set_walk: WPT_WALK_* bits */
 uint32_t g_walk = 0;
+/* wpt_set_bypass: how scenes uploaded from now on choose the nodes their walk leaves out (wpt_bypass.h) */
+uint32_t g_bypassMode = wptb::MODE_MODEL;
 /* wpt_set_slices: 0 = wpt_slices_plan, 1 = never, 2 .. 15 = that many units; WPT_SLICES_DECLINE_ODD beside it */
 uint32_t g_slices = 0;
 /* the two counters of the sliced kernels (wpt_last_slice_stats), one pair per device, allocated at a device's first sliced
@@ -572,6 +579,8 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
     s->triCount = desc->tri_count;
     memset(&view, 0, sizeof(view));
     const std::vector<uint32_t> triNew = wptl::triangleOrder(desc, (walk & WPT_WALK_TRIANGLES_AS_GIVEN) != 0);
+    const bool fitsLds = size_t(desc->node_count) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES;
+    std::vector<uint32_t> ldsNodes; /* the device nodes of a tree that fits LDS, kept for its link words below */
     {
         wptl::DeviceNodes nodes;
         WPT_TRY(layoutStatus(wptl::deviceNodes(desc, triNew, topNodes, &nodes)));
@@ -579,8 +588,11 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
         view.boxesMayBeNan = nodes.boxesMayBeNan;
         WPT_TRY(uploadQuads(s, nodes.quads, &view.nodes));
         s->foldedLinks = 0;
-        if (size_t(desc->node_count) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES) /* the trees that are walked from LDS */
+        if (fitsLds) { /* the trees that are walked from LDS */
             s->foldedLinks = wptl::countFoldedLinks(reinterpret_cast<const uint32_t*>(nodes.quads.data()), desc->node_count, nullptr);
+            ldsNodes.resize(size_t(desc->node_count) * 8);
+            memcpy(ldsNodes.data(), nodes.quads.data(), ldsNodes.size() * 4);
+        }
     }
     if (walk & WPT_WALK_WIDE) {
         const std::vector<wptl::Quad> wide = wptl::wideNodes(desc, triNew);
@@ -590,6 +602,18 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
     {
         const std::vector<wpt_tri_geom> g = wptl::permuted(desc->tri_geom, triNew);
         WPT_TRY(uploadArray(s, reinterpret_cast<const float4*>(g.data()), size_t(desc->tri_count) * 3, &view.triGeom));
+        if (fitsLds) {
+            /* the link words of the tree's copy in LDS, computed once per scene: the exact ones, plain and folded, and the
+             * ones that go round the nodes the plan leaves out (wpt_bypass.h) */
+            const wptb::Plan plan = wptb::plan(ldsNodes.data(), desc->node_count, g.data(), desc->tri_count, g_bypassMode);
+            std::vector<uint32_t> words(plan.plain);
+            words.insert(words.end(), plan.folded.begin(), plan.folded.end());
+            words.insert(words.end(), plan.bypass.begin(), plan.bypass.end());
+            const uint32_t* onDevice = nullptr;
+            WPT_TRY(uploadArray(s, words.data(), words.size(), &onDevice));
+            s->ldsLinks = const_cast<uint32_t*>(onDevice);
+            s->bypassedNodes = plan.outCount;
+        }
     }
     {
         const std::vector<wpt_tri_attr> a = wptl::permuted(desc->tri_attr, triNew);
@@ -896,12 +920,24 @@ unsigned long long* runSliced(const wptk::KernelArgs& args, const SingleKernel& 
 
 /* The single kernel by the plan's strategy, and the pool's counter where the plan has one.  Where the memory a strategy needs
  * cannot be had (the counter first of all), one plain pass renders the launch.  Returns the launch's error. */
-hipError_t runSingleKernel(wptk::KernelArgs& args, const wptk::KernelChoice& choice, const wptk::KernelEntry* kernel,
+hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const wptk::KernelChoice& choice, const wptk::KernelEntry* kernel,
         const wptk::KernelEntry* slicedTwin, const wptk::LaunchPlan& plan, hipStream_t stream)
 {
     StreamScratch scratch(stream);
     args.pool = plan.pooled ? scratch.get<uint32_t>(1) : nullptr;
     args.materialsInLds = choice.materialsInLds;
+    if (choice.ldsScene) {
+        /* The link words of the tree's copy in LDS.  Exact: the fold's, or every node's own under WPT_WALK_NO_FOLD; the launch's:
+         * the ones that go round the nodes the scene's plan leaves out -- they are built on the fold, so not under NO_FOLD, not
+         * under WPT_WALK_NO_BYPASS, and not for a tree with a NaN bound, whose rays all keep the exact links. */
+        if (!scene->ldsLinks)
+            return hipErrorInvalidValue; /* (every scene that fits LDS has them) */
+        const size_t words = 2 * size_t(scene->nodeCount) + 4;
+        const bool fold = (choice.materialsInLds & wptk::LDS_FOLD) != 0;
+        const bool bypass = fold && !(g_walk & WPT_WALK_NO_BYPASS) && !args.sv.boxesMayBeNan;
+        args.sv.spheres = reinterpret_cast<const wpt_sphere*>(scene->ldsLinks + (fold ? words : 0));
+        args.sv.wideNodes = reinterpret_cast<const float4*>(scene->ldsLinks + (bypass ? 2 * words : fold ? words : 0));
+    }
     const SingleKernel run = { kernel, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
     bool done = false;
     unsigned long long* sliceStats = nullptr;
@@ -968,7 +1004,7 @@ wpt_status renderLaunch(const LaunchRequest& rq)
             return fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
         (void)hipGetLastError();
     }
-    HIP_TRY(runSingleKernel(args, choice, kernel, slicedTwin, plan, stream));
+    HIP_TRY(runSingleKernel(rq.scene, args, choice, kernel, slicedTwin, plan, stream));
     return WPT_OK;
 }
 
@@ -1224,7 +1260,7 @@ wpt_status wpt_progress_advance_device(wpt_progress* p, uint32_t rows, float* fr
      * one pass, in the order set up above */
     const bool pooled = wptk::planLaunch({ wptk::SENSOR_FRAME, false, false, false, p->choice.sceneInLds, stage.blockSize, total, stage.cuCount,
             g_variant, 2u, 1u }).pooled;
-    HIP_TRY(runSingleKernel(stage, p->choice, p->kernel, nullptr, { false, false, pooled, wptk::ONE_PASS, 1, total, 1 }, stream));
+    HIP_TRY(runSingleKernel(p->scene, stage, p->choice, p->kernel, nullptr, { false, false, pooled, wptk::ONE_PASS, 1, total, 1 }, stream));
     /* The launch that renders the last row writes the frame and stores no carry.  A finished session keeps the block's pixels
      * of its frame in the carry's place instead, so that its preview and its saved state still yield the frame. */
     if (rowStop == total) {
@@ -1921,7 +1957,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes)
 
 wpt_status wpt_set_walk(uint32_t flags)
 {
-    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD))
+    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD | WPT_WALK_NO_BYPASS))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     g_walk = flags;
     return WPT_OK;
@@ -2034,6 +2070,47 @@ wpt_status wpt_fold_plan(const wpt_scene_desc* desc, uint32_t* folded, uint32_t*
     wptl::DeviceNodes nodes;
     WPT_TRY(layoutStatus(wptl::deviceNodes(desc, wptl::triangleOrder(desc, true), 0, &nodes)));
     *folded = wptl::countFoldedLinks(reinterpret_cast<const uint32_t*>(nodes.quads.data()), desc->node_count, lds_words);
+    return WPT_OK;
+}
+
+wpt_status wpt_set_bypass(uint32_t mode)
+{
+    if (mode > wptb::MODE_ALL_ELIGIBLE)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "bypass mode: 0 (the cost model's choice) or 1 (every eligible inner node)");
+    g_bypassMode = mode;
+    return WPT_OK;
+}
+
+wpt_status wpt_scene_bypassed_nodes(const wpt_scene* scene, uint32_t* count)
+{
+    if (!scene || !count)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *count = scene->bypassedNodes;
+    return WPT_OK;
+}
+
+wpt_status wpt_bypass_plan(const wpt_scene_desc* desc, uint32_t* count, uint32_t* words)
+{
+    if (!count)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    WPT_TRY(validate(desc));
+    /* as wpt_fold_plan: the description's own depth-first order and triangle indices */
+    wptl::DeviceNodes nodes;
+    WPT_TRY(layoutStatus(wptl::deviceNodes(desc, wptl::triangleOrder(desc, true), 0, &nodes)));
+    const uint32_t* n = reinterpret_cast<const uint32_t*>(nodes.quads.data());
+    *count = 0;
+    std::vector<uint32_t> links;
+    if (size_t(desc->node_count) * 32 + size_t(desc->tri_count) * 48 <= LDS_SCENE_MAX_BYTES) {
+        const wptb::Plan plan = wptb::plan(n, desc->node_count, desc->tri_geom, desc->tri_count, g_bypassMode);
+        *count = plan.outCount;
+        links = plan.bypass;
+    } else { /* a tree that is not walked from LDS has no plan: the fold's links */
+        links = wptb::linkWords(n, desc->node_count, true, nullptr);
+    }
+    if (words) {
+        memcpy(words, links.data(), 2 * size_t(desc->node_count) * 4);
+        words[2 * size_t(desc->node_count)] = links[2 * size_t(desc->node_count) + 2]; /* the node a ray starts at */
+    }
     return WPT_OK;
 }
 

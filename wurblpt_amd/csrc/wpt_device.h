@@ -347,7 +347,12 @@ struct SceneView {
     const wpt_hotspot* hotspots;
     float invHotspotCount;     /* 1.0f / (float)hotspotCount, divided once on the host (IEEE, the same bits) */
     const float4* hotspotFace; /* per triangle hot spot: unit face normal, face area (wpt_hotspot_face_kernel, at upload) */
-    const wpt_sphere* spheres;
+    /* The kernels with the scene in LDS know no spheres and no wide form; their launches carry the link words of the tree's copy
+     * in LDS in the two pointers' places (wpt_bypass.h, Plan: per node skip link and word 7, the null node's pair, the start
+     * node): in wideNodes' place the set the launch walks, in spheres' place the one its rays with RAY_MAY_NAN keep to
+     * (ldsLinks and ldsExactLinks of wpt_pathtrace.inc.h; plain members, not unions, so that every other kernel's code stays
+     * what it was). */
+    const wpt_sphere* spheres; /* (launches of the kernels with the scene in LDS: the exact link words, see above) */
     const wpt_rgl_brdf* rglBrdfs; /* measured BRDFs and the pool their tables live in */
     const float* rglData;
     const uint32_t* rglRgbl; /* per measured BRDF: offset of its interleaved colour + luminance table in rglData, or WPT_RGL_NONE (wpt_rgl.h) */
@@ -370,7 +375,7 @@ struct SceneView {
      * walks it).  8 quadwords per wide node: lo.x, lo.y, lo.z, hi.x, hi.y, hi.z of up to four entries (the node's grandchildren, a
      * child that is a leaf standing for itself, in the reference's order), their references (NODE_CHILD | wide node, a triangle
      * index, PRIM_SPHERE | sphere index, 0xffffffff = no entry), one spare.  Wide node 0 is the root's. */
-    const float4* wideNodes;
+    const float4* wideNodes; /* (launches of the kernels with the scene in LDS: the link words the launch walks, see `spheres`) */
 };
 
 /* ---- animations at a ray's time (wpt_anim.h) ---- */

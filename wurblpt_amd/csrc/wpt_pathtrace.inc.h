@@ -43,7 +43,6 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_blocks.h"
-#include "wpt_fold.h"
 
 namespace wptk {
 
@@ -207,6 +206,12 @@ constexpr uint32_t WIDE_STACK = 96;          /* pending children per lane (8 byt
 constexpr uint32_t WIDE_NONE = 0xffffffffu;  /* no child (also: an empty entry of a wide node) */
 constexpr int RAY_WALK_BINARY = 0x80;        /* in RayAux::k: this ray walks the binary tree although its slab distances are numbers (its bound has grown) */
 
+/* LDSSCENE: node n's pair of exact link words (a 32-bit byte offset from the uniform base: one register of address per lane) */
+WPT_D uint2 exactLinks(const SceneView& sv, uint32_t n)
+{
+    return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(sv.spheres) + (n << 3));
+}
+
 template<uint32_t F, bool COUNT, bool LDSSCENE, int OCC, bool WIDE = false>
 __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 {
@@ -217,6 +222,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     static_assert(!((F & FEAT_ADAPTIVE) && COUNT), "adaptive sampling has no counting build");
     static_assert(!((F & FEAT_TOF) && ((F & (FEAT_VIEWS | FEAT_TRANSIENT | FEAT_ADAPTIVE)) || COUNT)), "the time-of-flight sensor: one view, no other film, no counting build");
     static_assert(!((F & FEAT_SLICED) && ((F & (FEAT_VIEWS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_TOF)) || COUNT)), "pixels in slices: plain product launches (they share KernelArgs' union)");
+    static_assert(!LDSSCENE || (!WIDE && !(F & FEAT_SPHERES)), "the kernels with the scene in LDS carry their link words in SceneView::wideNodes and ::spheres (wpt_device.h): they may read neither as what it is named");
     constexpr bool VIEWS = (F & FEAT_VIEWS) != 0;
     constexpr bool ADAPTIVE = (F & FEAT_ADAPTIVE) != 0;
     constexpr bool SLICED = (F & FEAT_SLICED) != 0;
@@ -256,19 +262,19 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 
     if (LDSSCENE) {
         /* nodes (2 x float4 each), the null node, then the triangle positions (3 x float4 each).  The LDS copy of a node has
-         * the walk's own word 7 (ldsStep below, wpt_fold.h): the node a ray that passes an inner node's box goes to as a plain
-         * index -- its first child, or with LDS_FOLD what lies behind the first children that repeat its box -- a leaf's word
-         * complemented (>= 2^31), links clamped to nodeCount.  The null node (index nodeCount: skip and child both nodeCount) is where
-         * every lane that does not walk stands, so that a step leaves it where it is whatever its box test says. */
+         * the walk's own two link words, made on the host once per scene (the words in sv.wideNodes' place, wpt_device.h; wpt_fold.h, wpt_bypass.h): the skip link,
+         * and in word 7 the node a ray that passes an inner node's box goes to as a plain index -- its first child, with
+         * LDS_FOLD what lies behind the first children that repeat its box, and either led on past the nodes the scene's plan
+         * leaves out of the walk -- or a leaf's word complemented (>= 2^31); links clamped to nodeCount.  The null node (index
+         * nodeCount: skip and child both nodeCount) is where every lane that does not walk stands, so that a step leaves it
+         * where it is whatever its box test says. */
         const uint32_t n4 = 2 * nodeCount, t4 = 3 * sv.triCount;
         for (uint32_t i = threadIdx.x; i < n4; i += WG) {
             float4 q = sv.nodes[i];
             if (i & 1) {
-                const uint32_t skip = __float_as_uint(q.z);
-                uint32_t links;
-                q.z = __uint_as_float(skip < nodeCount ? skip : nodeCount);
-                q.w = __uint_as_float(wptf::foldLdsWord(reinterpret_cast<const uint32_t*>(sv.nodes), nodeCount, i >> 1,
-                        (args.materialsInLds & LDS_FOLD) != 0, &links));
+                const uint2 links = reinterpret_cast<const uint2*>(sv.wideNodes)[i >> 1];
+                q.z = __uint_as_float(links.x);
+                q.w = __uint_as_float(links.y);
             }
             ldsScene[i] = q;
         }
@@ -309,6 +315,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
         else
             return sv.triGeom[i];
     };
+
+    /* LDSSCENE: the node a ray's walk starts at under the launch's links (the root, or what the plan's links make of it), the
+     * entry behind the null node's; rays with RAY_MAY_NAN start at the root and keep to the exact words (in sv.spheres' place) at every step */
+    uint32_t walkStart = 0;
+    if constexpr (LDSSCENE)
+        walkStart = reinterpret_cast<const uint2*>(sv.wideNodes)[nodeCount + 1].x;
 
     auto pixelOf = [&](uint32_t gid, uint32_t& pixel) -> bool { return lanePixel(args, gid, pixel); };
     const bool firstPass = !ADAPTIVE && args.rowStop < args.samplesSqrt; /* (an adaptive launch is one pass) */
@@ -442,6 +454,10 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
          * and in WIDE kernels they walk the binary tree */
         if (rayMayNan(ps.o, aux.inv))
             aux.k |= RAY_MAY_NAN;
+        if constexpr (LDSSCENE) {
+            if (!(aux.k & RAY_MAY_NAN))
+                node = walkStart;
+        }
         if (WIDE) {
             /* the root's wide node, admitted under any bound (the root's own box decides nothing its children do not) */
             curRef = NODE_CHILD | 0u;
@@ -571,8 +587,15 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
              * link again.  Each walking lane performs the box test and the decisions of binaryStep on the same values. */
             auto ldsStep = [&](auto nanCheck) {
                 const float4 n0 = node4(2 * node), n1 = node4(2 * node + 1);
-                const uint32_t skip = __float_as_uint(n1.z);
-                const uint32_t word = __float_as_uint(n1.w); /* the LDS copy's word: child index, or ~leaf word (>= 2^31) */
+                uint32_t skip = __float_as_uint(n1.z);
+                uint32_t word = __float_as_uint(n1.w); /* the LDS copy's word: child index, or ~leaf word (>= 2^31) */
+                if constexpr (decltype(nanCheck)::value) {
+                    /* a group in which a ray's slab distances may be NaN walks the exact links, every lane of it (node is at
+                     * most nodeCount, the null node, which has its pair there too) */
+                    const uint2 exact = exactLinks(sv, node);
+                    skip = exact.x;
+                    word = exact.y;
+                }
                 const bool hit = boxTest<decltype(nanCheck)::value>(nodeLo(n0, n1), nodeHi(n0, n1), ps.o, aux.inv, par.min_hit_distance, amax);
                 const bool toLeaf = hit && (int32_t)word < 0;
                 leafNode = toLeaf ? node : leafNode;
@@ -629,6 +652,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                             const float4 n1 = node4(2 * leafNode + 1);
                             leafPrim = ~__float_as_uint(n1.w);
                             node = __float_as_uint(n1.z);
+                            if (nanPossible) /* wave-uniform: the exact skip link, as in ldsStep (leafNode is a leaf's index) */
+                                node = exactLinks(sv, leafNode).x;
                         }
                         Candidate c;
                         bool accepted;

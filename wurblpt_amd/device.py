@@ -16,7 +16,7 @@ def lib_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get("WPT_LIB_DIR", "lib"), "libwurblpt_hip.so")
 
 
-WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD = 1, 2, 4, 8, 16, 32  # wpt_set_walk (include/wurblpt_hip.h)
+WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD, WALK_NO_BYPASS = 1, 2, 4, 8, 16, 32, 64  # wpt_set_walk (include/wurblpt_hip.h)
 SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
 EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_scene_upload", "wpt_scene_free", "wpt_scene_check",
@@ -26,7 +26,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
+           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_scene_bypassed_nodes", "wpt_bypass_plan", "wpt_set_bypass", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
            "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
            "wpt_progress_save", "wpt_progress_restore", "wpt_progress_state_info",
@@ -394,6 +394,30 @@ def fold_plan(host_scene, with_words=False):
     return (int(folded.value), words) if with_words else int(folded.value)
 
 
+BYPASS_MODEL, BYPASS_ALL_ELIGIBLE = 0, 1  # wpt_set_bypass
+
+
+def set_bypass(mode):
+    """wpt_set_bypass (tests): which eligible inner nodes the walk of a scene in LDS leaves out -- BYPASS_MODEL: the cost model's
+    choice, BYPASS_ALL_ELIGIBLE: all of them; read when a scene is uploaded and by bypass_plan"""
+    L = lib()
+    L.wpt_set_bypass.argtypes = [C.c_uint32]
+    _check(L.wpt_set_bypass(mode))
+
+
+def bypass_plan(host_scene, with_words=False):
+    """wpt_bypass_plan: the inner nodes that the walk of the scene's tree in LDS leaves out; with with_words (count, links, start):
+    links[i] = (skip link, word 7) of node i's LDS copy as numpy uint32, start = the node a ray starts at.  Needs no device"""
+    import numpy as np
+    L = lib()
+    L.wpt_bypass_plan.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    count = C.c_uint32()
+    n = int(host_scene.d.node_count)
+    words = np.zeros(2 * n + 1, np.uint32)
+    _check(L.wpt_bypass_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(count), C.c_void_p(words.ctypes.data) if with_words else None))
+    return (int(count.value), words[:2 * n].reshape(n, 2), int(words[2 * n])) if with_words else int(count.value)
+
+
 def progress_covers(sensor=SENSOR_FRAME, counting=False, bands=False):
     """wpt_progress_covers: raises RuntimeError with the library's reason if progressive sessions do not cover such a launch;
     needs no device"""
@@ -481,6 +505,14 @@ class DeviceScene:
         self._handle = C.c_void_p()
         _check(lib().wpt_scene_upload(host_scene.desc, C.byref(self._handle)))
         self.host = host_scene
+
+    def bypassed_nodes(self):
+        """wpt_scene_bypassed_nodes: the inner nodes the walk leaves out, chosen at the upload"""
+        L = lib()
+        L.wpt_scene_bypassed_nodes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        count = C.c_uint32()
+        _check(L.wpt_scene_bypassed_nodes(self._handle, C.byref(count)))
+        return int(count.value)
 
     def folded_links(self):
         """wpt_scene_folded_links: the folded nodes, counted at the upload"""
