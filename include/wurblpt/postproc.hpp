@@ -108,4 +108,59 @@ inline Array<float> mixLightGroups(const SensorRGBLightGroups& sensor, const std
     return r;
 }
 
+/* The denoiser's parameters (wpt_denoise_params in wurblpt_hip.h, which has the formula and what the defaults were measured to do) */
+class DenoiseParameters
+{
+public:
+    float sigmaL = 1.0f;          // standard deviations of luminance a tap may differ by
+    float sigmaZ = 0.1f;          // sine of the angle by which a tap may leave the pixel's tangent plane
+    unsigned int normalLog2 = 7;  // the normal weight is the cosine to the power 2^normalLog2
+    unsigned int iterations = 5;  // a-trous iterations with steps 1, 2, 4, ...; 0 copies
+};
+
+/* A rendered frame filtered with the edge-avoiding a-trous wavelet filter under variance guidance: `frame` and `moments` are an
+ * adaptive render's result and moment film (mcpt() with a sample-count map), `samplesSqrtMap` that map, and the three arrays a
+ * GroundTruth's cameraSpacePositions, cameraSpaceMaterialNormals and materials at the frame's size.  Returns the filtered frame
+ * with the frame's tags; `variance` (optional) receives the variance of its luminance, one component.  Runs on the CPU
+ * (wpt_postproc_denoise_host, the same bits as the device's wpt_postproc_denoise). */
+inline Array<float> denoise(const Array<float>& frame, const Array<float>& moments, const std::vector<uint16_t>& samplesSqrtMap,
+        const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+        const DenoiseParameters& params = DenoiseParameters(), Array<float>* variance = nullptr)
+{
+    const size_t width = frame.dimension(0), height = frame.dimension(1), pixels = frame.elementCount();
+    const Array<float>* three[3] = { &moments, &cameraSpacePositions, &cameraSpaceMaterialNormals };
+    for (const Array<float>* a : three)
+        if (a->elementCount() != pixels || a->dimension(0) != width || a->componentCount() != 3)
+            throw std::invalid_argument("denoise: moments, positions and normals must have the frame's size and three components");
+    if (materials.elementCount() != pixels || materials.dimension(0) != width || materials.componentCount() != 1 || samplesSqrtMap.size() != pixels)
+        throw std::invalid_argument("denoise: the materials and the sample-count map must have the frame's size");
+    const std::vector<float> rgb = postprocdetail::packRgb(frame);
+    std::vector<float> out(rgb.size());
+    if (variance)
+        *variance = Array<float>(width, height, 1);
+    const wpt_denoise_params p = { params.sigmaL, params.sigmaZ, params.normalLog2, params.iterations };
+    if (wpt_postproc_denoise_host(rgb.data(), static_cast<const float*>(moments.data()), samplesSqrtMap.data(),
+                static_cast<const float*>(cameraSpacePositions.data()), static_cast<const float*>(cameraSpaceMaterialNormals.data()),
+                static_cast<const int32_t*>(materials.data()), uint32_t(width), uint32_t(height), &p, out.data(),
+                variance ? static_cast<float*>(variance->data()) : nullptr) != WPT_OK)
+        throw std::runtime_error(std::string("denoise failed: ") + wpt_last_error());
+    Array<float> r(width, height, frame.componentCount());   /* further components stay 0 */
+    r.globalTagList() = frame.globalTagList();
+    for (size_t i = 0; i < pixels; i++)
+        for (size_t c = 0; c < 3; c++)
+            r[i][c] = out[3 * i + c];
+    return r;
+}
+
+/* The same for a frame rendered with samplesSqrt^2 samples in every pixel */
+inline Array<float> denoise(const Array<float>& frame, const Array<float>& moments, unsigned int samplesSqrt,
+        const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+        const DenoiseParameters& params = DenoiseParameters(), Array<float>* variance = nullptr)
+{
+    if (samplesSqrt > 65535)
+        throw std::invalid_argument("denoise: samplesSqrt must not exceed 65535");
+    return denoise(frame, moments, std::vector<uint16_t>(frame.elementCount(), uint16_t(samplesSqrt)), cameraSpacePositions,
+            cameraSpaceMaterialNormals, materials, params, variance);
+}
+
 }

@@ -661,6 +661,51 @@ wpt_status wpt_postproc_scale_luminance(const float* rgb_device, float* out_devi
  * float), 3 = max luminance (out: one float). */
 wpt_status wpt_postproc_host(int op, const float* rgb_host, void* out_host, uint64_t pixels, float a, float b);
 
+/* ---- denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with the variance guidance of SVGF (Schied et
+ * al. 2017), spatial only ----
+ * Filters a rendered frame with what the library already produces beside it: the moment film and the sample-count map of an
+ * adaptive render (wpt_render_adaptive_block*) and three arrays of the first-hit pass (wpt_ground_truth*) at the frame's size.
+ * All arrays are [height][width][c], row 0 = bottom:
+ *   frame, moments    3 floats per pixel                       samples_sqrt   n_p, one uint16 per pixel
+ *   positions         WPT_GT_CAMERA_SPACE_POSITIONS (P)        normals        WPT_GT_CAMERA_SPACE_MATERIAL_NORMALS (n)
+ *   materials         WPT_GT_MATERIALS (m; -1 where the ray hit nothing)
+ * Preparation: per channel v = max(moment - frame * frame, 0) / (float)(n_p * n_p - 1) where n_p >= 2, else frame * frame;
+ * Y(c) = (kr * r + kg * g) + kb * b with the Y row of the RGB -> XYZ matrix; V_0 = Y(sqrt(v))^2, the variance of the luminance.
+ * Iteration i = 0 .. iterations - 1 with step s = 2^i reads the 5 x 5 taps q = p + s * (dx, dy) with the B3 weights
+ * h = (1, 4, 6, 4, 1) / 16, dy outer, dx inner; taps outside the frame and taps with m(q) != m(p) are skipped:
+ *   L   = sigma_l * sqrt(g) + 1e-10f,  g the (1,2,1) x (1,2,1) mean of V_i over the in-frame neighbours at unit offsets
+ *   w_n = max(0, n(p) . n(q)) squared normal_log2 times;  D = P(q) - P(p), t = n(p) . D, dd = D . D,
+ *   e_z = dd == 0 ? 0 : (t * t) / ((sigma_z * sigma_z) * dd)      (w_n = 1 and e_z = 0 where m(p) < 0)
+ *   e_l = |Y(c_i(q)) - Y(c_i(p))| / L,   w = (h[dy] * h[dx]) * w_n * expf(-(e_z + e_l)),  the centre tap's w = 9/64
+ *   c_{i+1}(p) = sum(w * c_i(q)) / sum(w),   V_{i+1}(p) = sum((w * w) * V_i(q)) / (sum(w) * sum(w))
+ * in float, in tap order, every operation rounded on its own.  `out`: the filtered frame; `variance` (may be NULL): V after the
+ * last iteration, one float per pixel.  iterations = 0 copies the frame.  The inputs must be finite and are never written.
+ * Refused with WPT_ERR_INVALID_ARGUMENT before a device is needed: a NULL input or `out`, a width or height of 0 or above
+ * 65535, iterations > WPT_DENOISE_MAX_ITERATIONS, normal_log2 > WPT_DENOISE_MAX_NORMAL_LOG2, a sigma that is not finite and
+ * positive, an output that overlaps an input or the other output.
+ * The device form is asynchronous on `hip_stream`; its scratch (64 bytes per pixel) is allocated and freed in stream order.
+ * The host form computes the same bits on the CPU and needs no device. */
+#define WPT_DENOISE_MAX_ITERATIONS 8u
+#define WPT_DENOISE_MAX_NORMAL_LOG2 16u
+typedef struct wpt_denoise_params {
+    float sigma_l;        /* default 1: how many standard deviations of luminance a tap may differ by.  Schied et al. publish 4; on the
+                           * Cornell box at 16 spp that doubles the error against a converged render, 1 lowers it by 3.5 % at
+                           * 64 x 64 and by 20 % at 256 x 256 (profiles/denoise_quality.txt) */
+    float sigma_z;        /* default 0.1: the sine of the angle by which a tap may leave the pixel's tangent plane */
+    uint32_t normal_log2; /* default 7: the normal weight is the cosine to the power 2^7 = 128 (Schied et al.) */
+    uint32_t iterations;  /* default 5, 0 .. WPT_DENOISE_MAX_ITERATIONS */
+} wpt_denoise_params;
+/* `params` NULL: the defaults */
+wpt_status wpt_postproc_denoise(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device, uint32_t width, uint32_t height,
+        const wpt_denoise_params* params, float* out_device, float* variance_device, void* hip_stream);
+wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, uint32_t width, uint32_t height,
+        const wpt_denoise_params* params, float* out_host, float* variance_host);
+/* "tile" (a workgroup's pixels and their halo in LDS) or "gather" (taps from device memory): the form the device's iteration
+ * with this step takes, decided from the step alone; both give the same bits */
+const char* wpt_postproc_denoise_form(uint32_t step);
+
 /* Kernel launch geometry knobs (0 = default); for benchmarking only, results do not change.  wpt_set_launch_config,
  * wpt_set_top_nodes and wpt_set_wavefront are PROCESS-GLOBAL hooks for tests and measurements: set them before rendering
  * starts, not while other threads render (MPICoordinator's worker threads read them).

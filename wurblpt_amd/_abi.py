@@ -130,6 +130,17 @@ class ProgressInfo(C.Structure):
         + [("tag", C.c_uint64), ("state_bytes", C.c_uint64)]
 
 
+class DenoiseParams(C.Structure):
+    """wpt_denoise_params; the defaults are the header's"""
+    _fields_ = [("sigma_l", C.c_float), ("sigma_z", C.c_float), ("normal_log2", C.c_uint32), ("iterations", C.c_uint32)]
+
+    def __init__(self, sigma_l=1.0, sigma_z=0.1, normal_log2=7, iterations=5):
+        super().__init__(sigma_l, sigma_z, normal_log2, iterations)
+
+
+DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_LOG2 = 8, 16
+
+
 # the saved state of a progressive session (include/wurblpt_hip.h has the layout)
 PROGRESS_MAGIC, PROGRESS_STATE_VERSION, PROGRESS_HEADER_BYTES, PROGRESS_CARRY_BYTES = 0x50545057, 1, 224, 32
 
@@ -140,5 +151,5 @@ STRUCT_SIZES = {
     "wpt_texture": (Texture, 88), "wpt_rgl_warp": (RglWarp, 76), "wpt_rgl_brdf": (RglBrdf, 388), "wpt_camera": (Camera, 140), "wpt_params": (Params, 40),
     "wpt_keyframe": (Keyframe, 44), "wpt_animation": (Animation, 8),
     "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
-    "wpt_progress_info": (ProgressInfo, 48),
+    "wpt_progress_info": (ProgressInfo, 48), "wpt_denoise_params": (DenoiseParams, 16),
 }

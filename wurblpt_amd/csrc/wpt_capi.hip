@@ -26,6 +26,7 @@
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
+#include "wpt_denoise_launch.h"
 #include "wpt_progress.h"
 #include "wpt_progress_state.h"
 
@@ -1561,6 +1562,46 @@ wpt_status mixCheck(const void* planes, uint32_t planeCount, uint64_t stride, ui
     return WPT_OK;
 }
 
+/* what a denoiser call is refused for, on the device or on the host; fills in the defaults and the filter's own parameters */
+wpt_status denoiseCheck(const void* frame, const void* moments, const void* samplesSqrt, const void* positions, const void* normals,
+        const void* materials, uint32_t width, uint32_t height, const wpt_denoise_params* params, const void* out, const void* variance,
+        wptdn::Params& filter, uint32_t& iterations)
+{
+    if (!frame || !moments || !samplesSqrt || !positions || !normals || !materials)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: an input is NULL");
+    if (!out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame is NULL");
+    if (width == 0 || height == 0 || width > wptdn::SIDE_MAX || height > wptdn::SIDE_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: width and height must lie in 1 .. " + std::to_string(uint32_t(wptdn::SIDE_MAX)));
+    const wpt_denoise_params defaults = { 1.0f, 0.1f, 7u, 5u };
+    const wpt_denoise_params& p = params ? *params : defaults;
+    if (p.iterations > WPT_DENOISE_MAX_ITERATIONS)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: iterations must lie in 0 .. " + std::to_string(WPT_DENOISE_MAX_ITERATIONS));
+    if (p.normal_log2 > WPT_DENOISE_MAX_NORMAL_LOG2)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: normal_log2 must lie in 0 .. " + std::to_string(WPT_DENOISE_MAX_NORMAL_LOG2));
+    if (!(std::isfinite(p.sigma_l) && p.sigma_l > 0.0f) || !(std::isfinite(p.sigma_z) && p.sigma_z > 0.0f))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: sigma_l and sigma_z must be finite and positive");
+    /* the byte ranges of the arrays: an output may overlap neither an input nor the other output */
+    const size_t pixels = size_t(width) * height;
+    const struct { const void* at; size_t bytes; } in[] = { { frame, pixels * 12 }, { moments, pixels * 12 }, { samplesSqrt, pixels * 2 },
+        { positions, pixels * 12 }, { normals, pixels * 12 }, { materials, pixels * 4 }, { variance, pixels * 4 } };
+    const auto overlap = [](const void* a, size_t an, const void* b, size_t bn) {
+        const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+        return x < y + bn && y < x + an;
+    };
+    for (size_t k = 0; k < sizeof(in) / sizeof(in[0]); k++) {
+        if (in[k].at && overlap(out, pixels * 12, in[k].at, in[k].bytes))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame aliases another array of the call");
+        if (variance && k < 6 && overlap(variance, pixels * 4, in[k].at, in[k].bytes))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the variance plane aliases another array of the call");
+    }
+    filter.sigmaL = p.sigma_l;
+    filter.sigmaZ2 = p.sigma_z * p.sigma_z;
+    filter.normalLog2 = p.normal_log2;
+    iterations = p.iterations;
+    return WPT_OK;
+}
+
 /* what a batch of views is refused for before anything needs the scene or a device */
 wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void* frames, uint32_t width, uint32_t height)
 {
@@ -1724,6 +1765,44 @@ wpt_status wpt_postproc_mix_planes_host(const float* planes_host, uint32_t plane
     WPT_TRY(mixCheck(planes_host, plane_count, stride, pixels, weights_host, out_host));
     wptmix::mixHost(planes_host, plane_count, size_t(stride), pixels, weights_host, out_host);
     return WPT_OK;
+}
+
+wpt_status wpt_postproc_denoise(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device, uint32_t width, uint32_t height,
+        const wpt_denoise_params* params, float* out_device, float* variance_device, void* hip_stream)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseCheck(frame_device, moments_device, samples_sqrt_device, positions_device, normals_device, materials_device, width, height,
+            params, out_device, variance_device, filter, iterations));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    wptdn::Rec* scratch = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), size_t(width) * height * 4 * sizeof(wptdn::Rec), stream));
+    const hipError_t e = wptk::launchDenoise(frame_device, moments_device, samples_sqrt_device, positions_device, normals_device,
+            materials_device, width, height, filter, iterations, scratch, out_device, variance_device, stream);
+    (void)hipFreeAsync(scratch, stream);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("denoise: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, uint32_t width, uint32_t height,
+        const wpt_denoise_params* params, float* out_host, float* variance_host)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseCheck(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, width, height, params,
+            out_host, variance_host, filter, iterations));
+    std::vector<wptdn::Rec> scratch(size_t(width) * height * 4);
+    wptdn::denoiseHost(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, width, height, filter,
+            iterations, scratch.data(), out_host, variance_host);
+    return WPT_OK;
+}
+
+const char* wpt_postproc_denoise_form(uint32_t step)
+{
+    return wptk::denoiseFormOfStep(step);
 }
 
 wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,

@@ -26,6 +26,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
            "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
+           "wpt_postproc_denoise", "wpt_postproc_denoise_host", "wpt_postproc_denoise_form",
            "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_scene_bypassed_nodes", "wpt_bypass_plan", "wpt_set_bypass", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
            "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
@@ -75,6 +76,13 @@ def lib():
                                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
             L.wpt_postproc_mix_planes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
             L.wpt_postproc_mix_planes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "wpt_postproc_denoise"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_postproc_denoise.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p]
+            L.wpt_postproc_denoise_host.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_void_p,
+                                                                       C.c_void_p]
+            L.wpt_postproc_denoise_form.argtypes = [C.c_uint32]
+            L.wpt_postproc_denoise_form.restype = C.c_char_p
         L.wpt_render_views_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
@@ -198,6 +206,87 @@ def mix_planes_host(planes, weights):
     _check(lib().wpt_postproc_mix_planes_host(C.c_void_p(p.ctypes.data), K, pixels * 3, pixels, C.c_void_p(w.ctypes.data),
                                               C.c_void_p(out.ctypes.data)))
     return out
+
+
+GUIDE_NAMES = ("camera_space_positions", "camera_space_material_normals", "materials")  # the ground truth arrays a denoiser call reads
+
+
+def _denoise_guide(guide):
+    """(P, n, m) of a denoiser call: a dict as ground_truth / ground_truth_device return it, or the three arrays"""
+    if isinstance(guide, dict):
+        return tuple(guide[name] for name in GUIDE_NAMES)
+    P, n, m = guide
+    return P, n, m
+
+
+def denoise_form(step):
+    """wpt_postproc_denoise_form: "tile" or "gather", the form the device's iteration with this step takes"""
+    return lib().wpt_postproc_denoise_form(int(step)).decode()
+
+
+def denoise(frame, moments, samples_sqrt, guide, params=None, variance_out=False, stream=None):
+    """wpt_postproc_denoise: the edge-avoiding a-trous filter with variance guidance (include/wurblpt_hip.h has the formula) on
+    CUDA tensors.  `frame`, `moments`: float32 [h, w, 3] (an adaptive render's frame and moment film); `samples_sqrt`: the map the
+    frame was rendered with (any integer tensor or array [h, w]) or one integer for all pixels; `guide`: the dict of
+    DeviceScene.ground_truth_device (GUIDE_NAMES) or the tuple (positions, normals, materials); `params`: _abi.DenoiseParams
+    (None: the defaults).  Asynchronous on `stream` (None: torch's current stream), ordered behind the work on the current
+    stream.  Returns the filtered frame, and with variance_out the variance of its luminance [h, w] as well."""
+    import numpy as np
+    import torch
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    P, n, m = _denoise_guide(guide)
+    for t, comps, what in ((frame, 3, "frame"), (moments, 3, "moments"), (P, 3, "positions"), (n, 3, "normals")):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, comps), "denoise: %s must be CUDA float32 [h, w, %d]" % (what, comps)
+    assert m.is_cuda and m.is_contiguous() and m.dtype == torch.int32 and m.numel() == w * h, "denoise: materials must be CUDA int32 [h, w]"
+    if isinstance(samples_sqrt, (int, np.integer)):
+        if not 0 <= int(samples_sqrt) <= 65535:
+            raise ValueError("the sample count's square root must lie in [0, 65535]")
+        samples_sqrt = np.full((h, w), int(samples_sqrt), np.uint16)
+    elif not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
+        _map_int(samples_sqrt)
+    assert tuple(samples_sqrt.shape) == (h, w), "samples_sqrt: [h, w]"
+    current = torch.cuda.current_stream()
+    launch = stream if stream is not None else current
+    m16 = _map_u16_device(samples_sqrt)
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
+    variance = torch.empty((h, w), dtype=torch.float32, device=frame.device) if variance_out else None
+    if launch != current:
+        launch.wait_stream(current)
+        for t in (m16, out, variance):
+            if t is not None:
+                t.record_stream(launch)
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise(C.c_void_p(frame.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(m16.data_ptr()),
+                                      C.c_void_p(P.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(m.data_ptr()), w, h, C.byref(p),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(variance.data_ptr()) if variance_out else None,
+                                      C.c_void_p(launch.cuda_stream)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_host(frame, moments, samples_sqrt, guide, params=None, variance_out=False):
+    """wpt_postproc_denoise_host: the same filter of numpy arrays on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    assert f.ndim == 3 and f.shape[2] == 3, "denoise: the frame must be [h, w, 3]"
+    h, w = f.shape[:2]
+    P, n, m = _denoise_guide(guide)
+    mo = np.ascontiguousarray(moments, dtype=np.float32)
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.float32)
+    m = np.ascontiguousarray(m, dtype=np.int32)
+    assert mo.shape == f.shape and P.shape == f.shape and n.shape == f.shape and m.size == w * h, "denoise: arrays of the frame's size"
+    if isinstance(samples_sqrt, (int, np.integer)):
+        samples_sqrt = np.full((h, w), int(samples_sqrt), np.int64)
+    a = _map_int(samples_sqrt)
+    assert a.shape == (h, w), "samples_sqrt: [h, w]"
+    m16 = np.ascontiguousarray(a.astype(np.uint16))
+    out = np.zeros((h, w, 3), np.float32)
+    variance = np.zeros((h, w), np.float32) if variance_out else None
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise_host(C.c_void_p(f.ctypes.data), C.c_void_p(mo.ctypes.data), C.c_void_p(m16.ctypes.data),
+                                           C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data), w, h, C.byref(p),
+                                           C.c_void_p(out.ctypes.data), C.c_void_p(variance.ctypes.data) if variance_out else None))
+    return (out, variance) if variance_out else out
 
 
 def _map_int(samples_sqrt):
@@ -896,6 +985,32 @@ class DeviceScene:
         _check(lib().wpt_render_block(self._handle, self.host.camera, C.byref(p), w, h, samples_sqrt, start, size,
                                        C.c_void_p(out.ctypes.data)))
         return out
+
+    def ground_truth_device(self, bits=None, camera_prev=None, camera_next=None, params=None, width=None, height=None, times=None,
+                            stream=None):
+        """wpt_ground_truth_device: dict name -> CUDA tensor [h, w, comps] (float32; "materials": int32) of the requested
+        GroundTruth bits (None: the three arrays a denoiser call reads, GUIDE_NAMES), left in device memory.  Asynchronous on
+        `stream` (None: torch's current stream).  times = (t0, tPrev, tNext) for animated instances."""
+        import torch
+        from . import host
+        if bits is None:
+            bits = sum(1 << GT_NAMES.index(name) for name in GUIDE_NAMES)
+        w = width or self.host.width
+        h = height or self.host.height
+        p = params if params is not None else host.default_params()
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            arrays = [torch.zeros((h, w, GT_COMPONENTS[k]), dtype=torch.int32 if k == 19 else torch.float32, device="cuda")
+                      if bits & (1 << k) else None for k in range(20)]
+        ptrs = (C.c_void_p * 20)(*[a.data_ptr() if a is not None else None for a in arrays])
+        L = lib()
+        L.wpt_ground_truth_device.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        tm = (C.c_float * 3)(*times) if times is not None else None
+        _check(L.wpt_ground_truth_device(self._handle, C.cast(self.host.camera, C.c_void_p),
+                                         C.addressof(camera_prev) if camera_prev is not None else None,
+                                         C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs,
+                                         C.c_void_p(s.cuda_stream)))
+        return {GT_NAMES[k]: a for k, a in enumerate(arrays) if a is not None}
 
 
 GT_NAMES = ("world_space_positions", "world_space_geometry_normals", "world_space_geometry_tangents",
