@@ -827,7 +827,9 @@ wpt_status wpt_set_scheduler_stats(unsigned long long* stats_device);
 const char* wpt_kernel_name(void);
 /* The form of that family's kernel the most recent render call launched, where a family has more than one: "rotated corners" for
  * the kernel with the scene in LDS that holds the corners in all three rotations (WPT_WALK_SELECT_CORNERS above), otherwise ""; ", sliced xU" behind it where the launch handed its pixels out in U units each
- * (wpt_set_slices). */
+ * (wpt_set_slices).  "rotated corners, leaf links from the nodes": that kernel for a scene whose tree does not have exactly one
+ * leaf per triangle (the description admits it); its leaf tests read the leaf's node for the skip link, as every other kernel
+ * with the scene in LDS does, where otherwise they find it in the triangle's corner records. */
 const char* wpt_kernel_form(void);
 /* Which instantiation of the single kernel renders a launch, from the facts the library decides by: a pure function that needs
  * no device (tests).  need: the feature bits of the scene and the launch's cameras (wpt_device.h, FEAT_*; FEAT_ANIM for a moving

@@ -23,6 +23,7 @@
 #include "wpt_launch_plan.h"
 #include "wpt_scene_layout.h"
 #include "wpt_bypass.h"
+#include "wpt_leaf_words.h"
 #include "wpt_wavefront.inc.h"
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
@@ -285,6 +286,10 @@ struct wpt_scene {
     /* a scene that fits LDS: the link words of its tree's copy there (wpt_bypass.h, Plan), three arrays of 2 * nodeCount + 4
      * words one behind the other -- plain, folded, bypass -- and the inner nodes the last one leaves out; else NULL */
     uint32_t* ldsLinks = nullptr;
+    /* ... and behind them the same three sets for the kernels with rotated corner copies (wpt_leaf_words.h: leaf words that say
+     * where the corners lie, and per triangle its leaf's skip link), wptw::leafWordsSize words each.  leafOneToOne: every
+     * triangle has exactly one leaf, so the leaf pass of those kernels takes its links from the corner records */
+    bool leafOneToOne = false;
     uint32_t bypassedNodes = 0; /* wpt_scene_bypassed_nodes */
     uint32_t animationCount;
     std::vector<void*> allocations;
@@ -328,6 +333,10 @@ static_assert(wptk::PLAN_WG == uint32_t(WG) && wptk::PLAN_SLICE_SLOT_MAX == wptk
 static_assert(wptl::NODE_CHILD == NODE_CHILD && wptl::NODE_INDEX_MASK == NODE_INDEX_MASK && wptl::PRIM_SPHERE == PRIM_SPHERE && wptl::WIDE_STACK == WIDE_STACK
         && wptl::WIDE_NONE == WIDE_NONE && wptl::LDS_SCENE_MAX_BYTES == LDS_SCENE_MAX_BYTES, "wpt_scene_layout.h restates the kernels' node words and limits");
 
+static_assert(wptw::LEAF_NODE_SHIFT == wptk::LEAF_NODE_SHIFT && wptw::LEAF_NODE_MAX == wptk::LEAF_NODE_MAX && wptw::LEAF_CORNER_MASK == wptk::LEAF_CORNER_MASK
+        && LDS_SCENE_MAX_BYTES / 32 <= wptw::LEAF_NODE_MAX && LDS_SCENE_MAX_BYTES / 16 <= wptw::LEAF_CORNER_MASK,
+        "wpt_leaf_words.h restates the rotated kernels' leaf word, which has room for every tree that fits LDS");
+
 /* What the process's most recent render call ran, all of it at once: every path that renders stores it here and nowhere else
  * (the wavefront form and the stages of a session too).  sliceStats: the counters a sliced launch adds to, else NULL. */
 void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned long long* sliceStats)
@@ -338,18 +347,20 @@ void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned 
     g_lastSliceStats.store(sliceStats, std::memory_order_relaxed);
 }
 
-/* wpt_kernel_form of a launch: "rotated corners" for that form of the kernel with the scene in LDS, ", sliced xU" behind it for
- * a launch that hands its pixels out in U > 1 units */
-const char* kernelForm(bool rotated, uint32_t units = 0)
+/* wpt_kernel_form of a launch: "rotated corners" for that form of the kernel with the scene in LDS -- with ", leaf links from
+ * the nodes" where the scene's tree is not one leaf per triangle and the leaf pass reads the leaf's node (wpt_leaf_words.h) --
+ * and ", sliced xU" behind it for a launch that hands its pixels out in U > 1 units */
+const char* kernelForm(bool rotated, uint32_t units = 0, bool leafLinksFromNodes = false)
 {
     static const std::vector<std::string> forms = [] {
         std::vector<std::string> f;
-        for (int r = 0; r < 2; r++)
+        for (int r = 0; r < 3; r++)
             for (uint32_t u = 0; u <= wptk::SLICE_UNITS_MAX; u++)
-                f.push_back(std::string(r ? "rotated corners" : "") + (u > 1 ? ", sliced x" + std::to_string(u) : std::string()));
+                f.push_back(std::string(r ? "rotated corners" : "") + (r == 2 ? ", leaf links from the nodes" : "")
+                        + (u > 1 ? ", sliced x" + std::to_string(u) : std::string()));
         return f;
     }();
-    return forms[(rotated ? wptk::SLICE_UNITS_MAX + 1 : 0) + (units <= wptk::SLICE_UNITS_MAX ? units : 0)].c_str();
+    return forms[(rotated ? (leafLinksFromNodes ? 2 : 1) * (wptk::SLICE_UNITS_MAX + 1) : 0) + (units <= wptk::SLICE_UNITS_MAX ? units : 0)].c_str();
 }
 
 /* the kernel table's row for an instantiation; there is no launch without one */
@@ -610,6 +621,14 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
             std::vector<uint32_t> words(plan.plain);
             words.insert(words.end(), plan.folded.begin(), plan.folded.end());
             words.insert(words.end(), plan.bypass.begin(), plan.bypass.end());
+            s->leafOneToOne = true;
+            for (const std::vector<uint32_t>* links : { &plan.plain, &plan.folded, &plan.bypass }) {
+                const wptw::LeafWords leaf = wptw::leafWords(links->data(), desc->node_count, desc->tri_count);
+                if (leaf.verdict == wptw::TOO_LARGE)
+                    return fail(WPT_ERR_UNSUPPORTED, "a tree that fits LDS has indices beyond its leaf words");
+                s->leafOneToOne = s->leafOneToOne && leaf.verdict == wptw::ONE_TO_ONE;
+                words.insert(words.end(), leaf.words.begin(), leaf.words.end());
+            }
             const uint32_t* onDevice = nullptr;
             WPT_TRY(uploadArray(s, words.data(), words.size(), &onDevice));
             s->ldsLinks = const_cast<uint32_t*>(onDevice);
@@ -938,6 +957,15 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
         const bool bypass = fold && !(g_walk & WPT_WALK_NO_BYPASS) && !args.sv.boxesMayBeNan;
         args.sv.spheres = reinterpret_cast<const wpt_sphere*>(scene->ldsLinks + (fold ? words : 0));
         args.sv.wideNodes = reinterpret_cast<const float4*>(scene->ldsLinks + (bypass ? 2 * words : fold ? words : 0));
+        if (choice.rotated) {
+            /* the same sets with the leaf words of the rotated kernels (wpt_leaf_words.h) */
+            const size_t leafWords = wptw::leafWordsSize(scene->nodeCount, scene->triCount);
+            const uint32_t* sets = scene->ldsLinks + 3 * words;
+            args.sv.spheres = reinterpret_cast<const wpt_sphere*>(sets + (fold ? leafWords : 0));
+            args.sv.wideNodes = reinterpret_cast<const float4*>(sets + (bypass ? 2 * leafWords : fold ? leafWords : 0));
+            if (scene->leafOneToOne)
+                args.materialsInLds |= wptk::LDS_LEAF_LINKS;
+        }
     }
     const SingleKernel run = { kernel, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
     bool done = false;
@@ -950,7 +978,8 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
         done = (sliceStats = runSliced(args, SingleKernel{ slicedTwin, run.grid, run.sceneLdsBytes, stream }, plan, scratch)) != nullptr;
     if (!done)
         run(args);
-    recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0), done ? plan.passes : 1u, sliceStats);
+    recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0, choice.rotated && !scene->leafOneToOne), done ? plan.passes : 1u,
+            sliceStats);
     return hipGetLastError();
 }
 

@@ -351,7 +351,9 @@ struct SceneView {
      * in LDS in the two pointers' places (wpt_bypass.h, Plan: per node skip link and word 7, the null node's pair, the start
      * node): in wideNodes' place the set the launch walks, in spheres' place the one its rays with RAY_MAY_NAN keep to
      * (ldsLinks and ldsExactLinks of wpt_pathtrace.inc.h; plain members, not unions, so that every other kernel's code stays
-     * what it was). */
+     * what it was).  The FEAT_ROTATED kernels are given sets of their own (wpt_leaf_words.h): the same pairs, but a leaf's word
+     * is sign bit | its node's index << 16 | 3 * its triangle, and behind the pairs follows one word per triangle, the skip link
+     * of the triangle's leaf under that set; the prologue writes those words into the corner records' fourth words. */
     const wpt_sphere* spheres; /* (launches of the kernels with the scene in LDS: the exact link words, see above) */
     const wpt_rgl_brdf* rglBrdfs; /* measured BRDFs and the pool their tables live in */
     const float* rglData;
@@ -542,12 +544,23 @@ WPT_D Hit finishHit(const SceneView& sv, const Candidate& c, f3 org, f3 dir, flo
     Hit h;
     h.a = c.a;
     h.prim = c.prim;
-    const float4 g0 = tri4(3 * c.prim + 0);
-    const float4 g1 = tri4(3 * c.prim + 1);
-    const float4 g2 = tri4(3 * c.prim + 2);
-    const uint32_t instance = __float_as_uint(g0.w);
-    h.material = __float_as_uint(g1.w);
-    const uint32_t flags = __float_as_uint(g2.w);
+    uint32_t instance, flags;
+    if constexpr ((F & FEAT_ROTATED) != 0) {
+        /* the corner records in LDS carry the leaf pass's words in these places (wpt_leaf_words.h): the three words come from
+         * the records in HBM, beside the attributes below */
+        (void)tri4;
+        const uint32_t* words = reinterpret_cast<const uint32_t*>(sv.triGeom + 3 * (size_t)c.prim);
+        instance = words[3];
+        h.material = words[7];
+        flags = words[11];
+    } else {
+        const float4 g0 = tri4(3 * c.prim + 0);
+        const float4 g1 = tri4(3 * c.prim + 1);
+        const float4 g2 = tri4(3 * c.prim + 2);
+        instance = __float_as_uint(g0.w);
+        h.material = __float_as_uint(g1.w);
+        flags = __float_as_uint(g2.w);
+    }
     const bool backfacing = c.invDet < 0.0f; /* det < 0 (hitable_triangle.hpp:274) */
     const float bx = c.invDet * c.U, by = c.invDet * c.V, bz = c.invDet * c.W;
     h.p = add(org, scl(c.a, dir));

@@ -65,6 +65,10 @@ constexpr uint32_t LDS_BYTES_PER_WORKGROUP_AT_FOUR = 160 * 1024 / 4;
 /* KernelArgs::materialsInLds is a word of bits for the kernels with the scene in LDS */
 constexpr uint32_t LDS_MATERIALS = 1u; /* the material records are in LDS too */
 constexpr uint32_t LDS_FOLD = 2u;      /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h) */
+constexpr uint32_t LDS_LEAF_LINKS = 4u; /* ROTATED kernels: a leaf's skip links are those in its triangle's corner records (every triangle has one leaf) */
+/* ROTATED kernels, the leaf word of the tree's copy in LDS (wpt_leaf_words.h; wpt_capi.hip asserts that they agree):
+ * sign bit | the leaf's node index << LEAF_NODE_SHIFT | quadword offset of the triangle's first corner within a copy */
+constexpr uint32_t LEAF_NODE_SHIFT = 16, LEAF_NODE_MAX = 0x7fffu, LEAF_CORNER_MASK = 0xffffu;
 /* the material records are copied to LDS quadword by quadword and read there through a generic pointer */
 static_assert(sizeof(wpt_material) % 16 == 0 && alignof(wpt_material) <= 16, "wpt_material must be a whole number of quadwords");
 /* A batch of views (FEAT_VIEWS kernels): the launch's lane indices g in [0, viewCount * viewPixels) are view g / viewPixels,
@@ -244,6 +248,13 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
      * the single kernel 106.1 -> 112.5; 10 M triangles 67.97 -> 68.09).  With the scene in LDS the frame is bound by the
      * instructions its waves issue and the same costs (Cornell 1055.6 against 1038.7 / 1049.1 / 1036.0 with 8 / 16 / 24). */
     constexpr int NEE_IN_WALK = LDSSCENE ? 0 : 4;
+    /* ROTATED: a wave's issue priority by phase, set at the two wave-uniform points where the scheduler has picked (s_setprio is a
+     * scalar instruction and does not look at the exec mask).  A wave in the walk issues short bursts between LDS round trips
+     * and is ready for a few cycles at a time; a wave in the long round has long runs of independent arithmetic and loses
+     * little when it yields.  Walk above long round: Cornell 1493.9 - 1497.2 against 1484.5 - 1486.7 Msamples/s; the reverse
+     * 1465.1 - 1466.4; priority 1 for two of a workgroup's four waves throughout 1479.4 - 1480.5
+     * (profiles/leaf_words_cornell.txt). */
+    constexpr int PRIORITY_WALK = 2, PRIORITY_LONG = 0;
     /* [ math tables ][ cold path words: SLOT_COUNT x WG float4 ][ LDSSCENE: nodes, triangle positions (ROTATED: and their two
      * rotated copies), material records where they fit ] */
     extern __shared__ float4 lds[];
@@ -265,7 +276,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
          * the walk's own two link words, made on the host once per scene (the words in sv.wideNodes' place, wpt_device.h; wpt_fold.h, wpt_bypass.h): the skip link,
          * and in word 7 the node a ray that passes an inner node's box goes to as a plain index -- its first child, with
          * LDS_FOLD what lies behind the first children that repeat its box, and either led on past the nodes the scene's plan
-         * leaves out of the walk -- or a leaf's word complemented (>= 2^31); links clamped to nodeCount.  The null node (index
+         * leaves out of the walk -- or a leaf's word complemented (>= 2^31; ROTATED: the leaf word of wpt_leaf_words.h, >= 2^31
+         * as well, in the sets these kernels are given); links clamped to nodeCount.  The null node (index
          * nodeCount: skip and child both nodeCount) is where every lane that does not walk stands, so that a step leaves it
          * where it is whatever its box test says. */
         const uint32_t n4 = 2 * nodeCount, t4 = 3 * sv.triCount;
@@ -281,16 +293,25 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
         if (threadIdx.x < 2)
             ldsScene[n4 + threadIdx.x] = threadIdx.x == 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f)
                     : make_float4(0.0f, 0.0f, __uint_as_float(nodeCount), __uint_as_float(nodeCount));
-        for (uint32_t i = threadIdx.x; i < t4; i += WG)
-            ldsScene[n4 + 2 + i] = sv.triGeom[i];
         if (ROTATED) {
-            /* the copies for rays whose largest direction component is x (kz = 0: y, z, x) and y (kz = 1: z, x, y), records of the
-             * same shape behind the stored ones (rotatedCopyOffset); the stored order is that of kz = 2 */
+            /* the stored order (that of kz = 2) and the copies for rays whose largest direction component is x (kz = 0: y, z, x)
+             * and y (kz = 1: z, x, y), records of the same shape behind the stored ones (rotatedCopyOffset).  The fourth words
+             * of a triangle's three records are what a leaf pass needs beside the corners, made once per scene on the host
+             * (wpt_leaf_words.h, behind the link words): its leaf's skip link under the launch's links, the exact one, and the
+             * triangle's index.  (What finishHit reads in their place comes from the records in HBM.) */
+            const uint32_t* const triSkip = reinterpret_cast<const uint32_t*>(sv.wideNodes) + n4 + 4;
+            const uint32_t* const triExact = reinterpret_cast<const uint32_t*>(sv.spheres) + n4 + 4;
             for (uint32_t i = threadIdx.x; i < t4; i += WG) {
                 const float4 g = sv.triGeom[i];
-                ldsScene[n4 + 2 + t4 + i] = make_float4(g.y, g.z, g.x, g.w);
-                ldsScene[n4 + 2 + 2 * t4 + i] = make_float4(g.z, g.x, g.y, g.w);
+                const uint32_t tri = i / 3u, corner = i - 3u * tri;
+                const float w = __uint_as_float(corner == 0 ? triSkip[tri] : corner == 1 ? triExact[tri] : tri);
+                ldsScene[n4 + 2 + i] = make_float4(g.x, g.y, g.z, w);
+                ldsScene[n4 + 2 + t4 + i] = make_float4(g.y, g.z, g.x, w);
+                ldsScene[n4 + 2 + 2 * t4 + i] = make_float4(g.z, g.x, g.y, w);
             }
+        } else {
+            for (uint32_t i = threadIdx.x; i < t4; i += WG)
+                ldsScene[n4 + 2 + i] = sv.triGeom[i];
         }
         const uint32_t c4 = ROTATED ? 3 * t4 : t4; /* quadwords of triangle positions in LDS */
         if (args.materialsInLds & LDS_MATERIALS) {
@@ -419,7 +440,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
     bool poolDry = false; /* wave-uniform */
     RayAux aux = rayAux(ps.d);
     /* LDSSCENE: a lane that does not walk stands on the null node (index nodeCount), and a lane that waits for its leaf test
-     * keeps the leaf's index in leafNode (ldsStep below) */
+     * keeps the leaf's index in leafNode (ldsStep below; ROTATED: the leaf's word, which says where its corners lie) */
     uint32_t node = LDSSCENE ? nodeCount : 0u, leafPrim = 0, leafNode = 0;
     float amax = k_maxval;
     /* ROTATED: the ray's origin in the order of its kz and inv[kz], beside aux, whose Sx and Sy then are the unswapped shear
@@ -544,6 +565,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
         long long tBlock = 0;
         if (COUNT)
             tBlock = clock64();
+        if constexpr (ROTATED) {
+            if (pick == S_NODE) /* (the instruction takes a literal) */
+                __builtin_amdgcn_s_setprio(PRIORITY_WALK);
+            else
+                __builtin_amdgcn_s_setprio(PRIORITY_LONG);
+        }
         if (pick == S_NODE) {
             /* Leave when fewer than leaveEighths/8 of the entering lanes are still traversing
              * (never below 1: the loop must end when no lane is left in it). */
@@ -584,7 +611,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
              * A lane that does not walk stands on the null node, whose child and skip link are itself, and stays there; a lane
              * whose walk leaves the tree by a skip link arrives there too and keeps state NODE until the next look (below).  A lane
              * that reaches a leaf goes to the null node as well and remembers the leaf; its test reads the leaf's word and skip
-             * link again.  Each walking lane performs the box test and the decisions of binaryStep on the same values. */
+             * link again -- ROTATED: it remembers the leaf's word, and the test finds the rest in the corner records.  Each
+             * walking lane performs the box test and the decisions of binaryStep on the same values. */
             auto ldsStep = [&](auto nanCheck) {
                 const float4 n0 = node4(2 * node), n1 = node4(2 * node + 1);
                 uint32_t skip = __float_as_uint(n1.z);
@@ -598,7 +626,7 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                 }
                 const bool hit = boxTest<decltype(nanCheck)::value>(nodeLo(n0, n1), nodeHi(n0, n1), ps.o, aux.inv, par.min_hit_distance, amax);
                 const bool toLeaf = hit && (int32_t)word < 0;
-                leafNode = toLeaf ? node : leafNode;
+                leafNode = toLeaf ? (ROTATED ? word : node) : leafNode;
                 state = toLeaf ? (int)S_LEAF : state;
                 node = hit ? (toLeaf ? nodeCount : word) : skip;
             };
@@ -647,7 +675,26 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                          * it goes on (a leaf's subtree is the leaf itself) */
                         if (COUNT)
                             lc.leaves++;
-                        if constexpr (LDSSCENE) {
+                        float4 r0, r1, r2; /* ROTATED: the corners from the copy in the ray's order */
+                        if constexpr (ROTATED) {
+                            /* one round trip: the leaf's word says where the corners lie, and their records say the rest -- the
+                             * skip link under the launch's links, the exact one (nanPossible is wave-uniform), the triangle */
+                            const uint32_t at = (((uint32_t)aux.k >> 8) & 0x7fffffu) + (leafNode & LEAF_CORNER_MASK);
+                            /* lgkmcnt(0) before the three reads and not between them: nothing of the walk is in flight here, but
+                             * the compiler's bookkeeping across the loop's edges otherwise puts that wait behind the first read
+                             * (the sliced twin), which makes the pass two round trips again */
+                            __builtin_amdgcn_s_waitcnt(0xc07f);
+                            r0 = tri4(at);
+                            r1 = tri4(at + 1);
+                            r2 = tri4(at + 2);
+                            leafPrim = __float_as_uint(r2.w);
+                            node = __float_as_uint(nanPossible ? r1.w : r0.w);
+                            if (!(args.materialsInLds & LDS_LEAF_LINKS)) {
+                                /* (a tree in which a triangle has two leaves, or none: the links of the leaf's own node) */
+                                const uint32_t leaf = (leafNode >> LEAF_NODE_SHIFT) & LEAF_NODE_MAX;
+                                node = nanPossible ? exactLinks(sv, leaf).x : __float_as_uint(node4(2 * leaf + 1).z);
+                            }
+                        } else if constexpr (LDSSCENE) {
                             /* the leaf ldsStep stopped at: its word (complemented in the LDS copy) and its skip link */
                             const float4 n1 = node4(2 * leafNode + 1);
                             leafPrim = ~__float_as_uint(n1.w);
@@ -662,10 +709,8 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
                             c.invDet = c.U = c.V = c.W = 0.0f;
                             accepted = sphereTest(sphereNow<F>(sv, ps, sv.spheres[leafPrim & ~PRIM_SPHERE]), ps.o, ps.d, par.min_hit_distance, amax, c.a);
                         } else if constexpr (ROTATED) {
-                            /* the corners from the copy in the ray's order: the same three reads, no select by axis */
-                            const uint32_t at = (((uint32_t)aux.k >> 8) & 0x7fffffu) + 3 * leafPrim;
-                            const float4 g0 = tri4(at), g1 = tri4(at + 1), g2 = tri4(at + 2);
-                            accepted = triangleTestRotated(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), orgRotated, aux.Sx, aux.Sy,
+                            /* no select by axis */
+                            accepted = triangleTestRotated(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), mk3(r2.x, r2.y, r2.z), orgRotated, aux.Sx, aux.Sy,
                                     auxSz, (uint32_t)aux.k & (uint32_t)RAY_FLIP, par.min_hit_distance, amax, c);
                         } else {
                             const float4 g0 = tri4(3 * leafPrim), g1 = tri4(3 * leafPrim + 1), g2 = tri4(3 * leafPrim + 2);
