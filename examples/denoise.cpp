@@ -9,7 +9,8 @@
  *   g++ -std=c++20 -O2 -fopenmp -Iinclude examples/denoise.cpp -Lwurblpt_amd/lib -lwurblpt_hip -Wl,-rpath,$PWD/wurblpt_amd/lib -o denoise
  *   ./denoise [width height samplesSqrt iterations outdir]
  *
- * Writes noisy.png and denoised.png (sRGB, one tone mapping for both).
+ * Writes noisy.png, denoised.png and despeckled.png (sRGB, one tone mapping for all): the last is the noisy frame after
+ * despeckle(), the 3 x 3 firefly filter, which takes single outliers out and leaves the noise.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -70,11 +71,12 @@ int main(int argc, char* argv[])
     const float maxLum = maxLuminance(denoised) / 800.0f;
     std::string error;
     if (!saveImage(toSRGB(uniformRationalQuantization(noisy, maxLum, 4.0f)), outdir + "/noisy.png", &error)
+            || !saveImage(toSRGB(uniformRationalQuantization(despeckle(noisy), maxLum, 4.0f)), outdir + "/despeckled.png", &error)
             || !saveImage(toSRGB(uniformRationalQuantization(denoised, maxLum, 4.0f)), outdir + "/denoised.png", &error)) {
         fprintf(stderr, "%s\n", error.c_str());
         return 1;
     }
-    printf("rendered %ux%u at %u spp on kernel %s and filtered it with %u iterations: noisy.png, denoised.png\n", width, height,
+    printf("rendered %ux%u at %u spp on kernel %s and filtered it with %u iterations: noisy.png, denoised.png, despeckled.png\n", width, height,
             samplesSqrt * samplesSqrt, noisy.globalTagList().value("WURBLPT/DEVICE_KERNEL").c_str(), params.iterations);
     return 0;
 }

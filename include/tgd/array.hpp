@@ -4,7 +4,8 @@
  * wurblpt-cornellbox.cpp:26,271-273), so that they compile against include/ unchanged where libtgd itself is not
  * installed.  It is NOT libtgd: only what libwurblpt's public interface and those applications touch is here -- a
  * 2D array of interleaved components with libtgd's accessor names (texture_image.hpp:45, sensor_rgb.hpp:37), x
- * fastest, then y; copies share the pixel storage.  With libtgd installed and in front of this directory in the
+ * fastest, then y; copies share the pixel storage.  Dimensions and a pixel's index may also be given as libtgd gives them,
+ * as a list: Array<float>({ width, height }, comps), a[{ x, y }], dimensions().  With libtgd installed and in front of this directory in the
  * include path the real container is taken instead (untested here: the library is not in this image).
  */
 #pragma once
@@ -55,9 +56,15 @@ public:
         _globalTags(new TagList)
     {
     }
+    /* libtgd's spelling: the dimensions as a list, { width, height } */
+    ArrayContainer(const std::vector<size_t>& dims, size_t comps, ComponentType type) :
+        ArrayContainer(dims.size() > 0 ? dims[0] : 0, dims.size() > 1 ? dims[1] : 1, comps, type)
+    {
+    }
 
     size_t dimensionCount() const { return 2; }
     size_t dimension(size_t i) const { return _dims[i]; }
+    std::vector<size_t> dimensions() const { return { _dims[0], _dims[1] }; }
     size_t componentCount() const { return _comps; }
     ComponentType componentType() const { return _type; }
     size_t componentSize() const { return componentTypeSize(_type); }
@@ -79,6 +86,8 @@ public:
     }
     template<typename T> T* get(size_t x, size_t y) { return get<T>(y * _dims[0] + x); }
     template<typename T> const T* get(size_t x, size_t y) const { return get<T>(y * _dims[0] + x); }
+    template<typename T> T* get(const std::vector<size_t>& index) { return get<T>(index[1] * _dims[0] + index[0]); }
+    template<typename T> const T* get(const std::vector<size_t>& index) const { return get<T>(index[1] * _dims[0] + index[0]); }
 };
 
 template<typename T> struct ComponentTypeOf;
@@ -92,10 +101,13 @@ template<typename T> class Array : public ArrayContainer
 public:
     Array() {}
     Array(size_t width, size_t height, size_t comps) : ArrayContainer(width, height, comps, ComponentTypeOf<T>::value) {}
+    Array(const std::vector<size_t>& dims, size_t comps) : ArrayContainer(dims, comps, ComponentTypeOf<T>::value) {}
     /* a container whose components already have this type (shares its storage); anything else is an empty array */
     Array(const ArrayContainer& container) : ArrayContainer(container.componentType() == ComponentTypeOf<T>::value ? container : ArrayContainer()) {}
     T* operator[](size_t elementIndex) { return this->template get<T>(elementIndex); }
     const T* operator[](size_t elementIndex) const { return this->template get<T>(elementIndex); }
+    T* operator[](const std::vector<size_t>& index) { return this->template get<T>(index); }
+    const T* operator[](const std::vector<size_t>& index) const { return this->template get<T>(index); }
     T* at(size_t x, size_t y) { return this->template get<T>(x, y); }
     const T* at(size_t x, size_t y) const { return this->template get<T>(x, y); }
 };

@@ -1,20 +1,25 @@
 /*
- * postproc.hpp -- the output side of a rendering: sRGB conversion and dynamic range reduction
- * (reference interface: libwurblpt/postproc.hpp:44-108, same function names and arguments).
+ * postproc.hpp -- the output side of a rendering: sRGB conversion and dynamic range reduction, and the image operations behind
+ * them (reference interface: libwurblpt/postproc.hpp:44-337, same function names and arguments).
  *
- * Each function hands the frame to the HIP library (wpt_postproc_host in wurblpt_hip.h), which
- * runs one thread per pixel on the device; results equal the reference's loops value for value
- * (tests/test_gpu_parity.py).  Like everything else here there is no CPU fallback: without a
- * device the functions throw.
+ * toSRGB, maxLuminance, uniformRationalQuantization and scaleLuminance hand the frame to the HIP library (wpt_postproc_host in
+ * wurblpt_hip.h), which runs one thread per pixel on the device; results equal the reference's loops value for value
+ * (tests/test_gpu_parity.py).  There is no CPU fallback for them: without a device they throw.
+ * scale, despeckle, applyLensDistortion / distort / undistort, cameraSpaceDistanceToCoords and cameraSpaceToPMDSpace call the
+ * host forms of the image operations (wpt_postproc_*_host), which need no device and give the bits of the device forms and of
+ * the reference's functions (tests/golden/image_ops/ holds the reference's outputs).  extractComponent(s) copy.
  */
 #pragma once
 
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../wurblpt_hip.h"
 #include "array.hpp"
+#include "camera.hpp"
+#include "optics.hpp"
 #include "sensor.hpp"
 
 namespace WurblPT {
@@ -161,6 +166,129 @@ inline Array<float> denoise(const Array<float>& frame, const Array<float>& momen
         throw std::invalid_argument("denoise: samplesSqrt must not exceed 65535");
     return denoise(frame, moments, std::vector<uint16_t>(frame.elementCount(), uint16_t(samplesSqrt)), cameraSpacePositions,
             cameraSpaceMaterialNormals, materials, params, variance);
+}
+
+/* ---- image operations (postproc.hpp:112-337) ---- */
+
+namespace postprocdetail {
+
+/* a float image of at most four components, or an exception */
+inline void checkImage(const Array<float>& img, const char* what)
+{
+    if (img.elementCount() == 0 || img.componentCount() < 1 || img.componentCount() > 4)
+        throw std::invalid_argument(std::string(what) + ": the image must be a float array with 1 to 4 components");
+}
+
+inline void check(wpt_status status, const char* what)
+{
+    if (status != WPT_OK)
+        throw std::runtime_error(std::string(what) + " failed: " + wpt_last_error());
+}
+
+/* the camera record of a lens on a projection: the image operations read its distortion part only */
+inline wpt_camera lensRecord(const LensDistortion& distortion, const Projection& projection)
+{
+    wpt_camera record = {};
+    Camera(Optics(projection, distortion)).describe(record);
+    return record;
+}
+
+}
+
+/* Bilinear resampling to newWidth x newHeight; postproc.hpp:112-136 */
+inline Array<float> scale(const Array<float>& img, unsigned int newWidth, unsigned int newHeight)
+{
+    postprocdetail::checkImage(img, "scale");
+    Array<float> scaledImg({ newWidth, newHeight }, img.componentCount());
+    scaledImg.globalTagList() = img.globalTagList();
+    postprocdetail::check(wpt_postproc_resample_host(static_cast<const float*>(img.data()), uint32_t(img.dimension(0)), uint32_t(img.dimension(1)),
+                uint32_t(img.componentCount()), newWidth, newHeight, static_cast<float*>(scaledImg.data())), "scale");
+    return scaledImg;
+}
+
+/* Selective despeckling: every pixel whose luminance is the greatest of its 3x3 neighbourhood and at least minFactor times the
+ * second greatest is replaced by the neighbourhood's median pixel.  Input and output are RGB images; postproc.hpp:143-193 */
+inline Array<float> despeckle(const Array<float>& img, float minFactor = 1.25f)
+{
+    postprocdetail::checkImage(img, "despeckle");
+    Array<float> out({ img.dimension(0), img.dimension(1) }, img.componentCount());
+    out.globalTagList() = img.globalTagList();
+    postprocdetail::check(wpt_postproc_despeckle_host(static_cast<const float*>(img.data()), uint32_t(img.dimension(0)), uint32_t(img.dimension(1)),
+                uint32_t(img.componentCount()), minFactor, static_cast<float*>(out.data())), "despeckle");
+    return out;
+}
+
+/* Lens distortion; postproc.hpp:197-248.  forward: true distorts the input, false undistorts it */
+inline Array<float> applyLensDistortion(const Array<float>& input, const LensDistortion& distortion, const Projection& projection, bool forward)
+{
+    postprocdetail::checkImage(input, "applyLensDistortion");
+    Array<float> output(input.dimensions(), input.componentCount());
+    output.globalTagList() = input.globalTagList();
+    const wpt_camera record = postprocdetail::lensRecord(distortion, projection);
+    postprocdetail::check(wpt_postproc_lens_warp_host(static_cast<const float*>(input.data()), uint32_t(input.dimension(0)),
+                uint32_t(input.dimension(1)), uint32_t(input.componentCount()), &record, forward ? 1 : 0, static_cast<float*>(output.data())),
+            "applyLensDistortion");
+    return output;
+}
+
+inline Array<float> distort(const Array<float>& undistorted, const LensDistortion& distortion, const Projection& projection)
+{
+    return applyLensDistortion(undistorted, distortion, projection, true);
+}
+
+inline Array<float> undistort(const Array<float>& distorted, const LensDistortion& distortion, const Projection& projection)
+{
+    return applyLensDistortion(distorted, distortion, projection, false);
+}
+
+/* Distance measurements (typically ToF; the first component holds the distance) to camera space coordinates; postproc.hpp:252-287 */
+inline Array<float> cameraSpaceDistanceToCoords(const Array<float>& distances, const Projection& projection, const LensDistortion& distortion)
+{
+    postprocdetail::checkImage(distances, "cameraSpaceDistanceToCoords");
+    Array<float> coords(distances.dimensions(), 3);
+    coords.globalTagList() = distances.globalTagList();
+    const wpt_camera record = postprocdetail::lensRecord(distortion, projection);
+    postprocdetail::check(wpt_postproc_distance_to_coords_host(static_cast<const float*>(distances.data()), uint32_t(distances.dimension(0)),
+                uint32_t(distances.dimension(1)), uint32_t(distances.componentCount()), &record, 0, static_cast<float*>(coords.data())),
+            "cameraSpaceDistanceToCoords");
+    return coords;
+}
+
+/* Camera space coordinates (the first three components are x, y, z) in the PMD camera's system; postproc.hpp:289-309 */
+inline Array<float> cameraSpaceToPMDSpace(const Array<float>& coords)
+{
+    if (coords.componentCount() < 3)
+        throw std::invalid_argument("cameraSpaceToPMDSpace: the first three components must be x, y, z");
+    Array<float> pmdspace(coords.dimensions(), 3);
+    pmdspace.globalTagList() = coords.globalTagList();
+    for (size_t e = 0; e < pmdspace.elementCount(); e++) {
+        pmdspace[e][0] = coords[e][0];
+        pmdspace[e][1] = -coords[e][1];
+        pmdspace[e][2] = -coords[e][2];
+    }
+    return pmdspace;
+}
+
+/* Components of an array, in the order of the list; postproc.hpp:313-337 */
+inline ArrayContainer extractComponents(const ArrayContainer& a, const std::vector<size_t>& componentList)
+{
+    for (size_t component : componentList)
+        if (component >= a.componentCount())
+            throw std::invalid_argument("extractComponents: the array has no component " + std::to_string(component));
+    ArrayContainer r(a.dimensions(), componentList.size(), a.componentType());
+    r.globalTagList() = a.globalTagList();
+    unsigned char* dst = static_cast<unsigned char*>(r.data());
+    const unsigned char* src = static_cast<const unsigned char*>(a.data());
+    for (size_t e = 0; e < a.elementCount(); e++)
+        for (size_t c = 0; c < componentList.size(); c++)
+            std::memcpy(dst + e * r.elementSize() + c * r.componentSize(), src + e * a.elementSize() + componentList[c] * a.componentSize(),
+                    a.componentSize());
+    return r;
+}
+
+inline ArrayContainer extractComponent(const ArrayContainer& a, size_t component)
+{
+    return extractComponents(a, { component });
 }
 
 }

@@ -706,6 +706,57 @@ wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* momen
  * with this step takes, decided from the step alone; both give the same bits */
 const char* wpt_postproc_denoise_form(uint32_t step);
 
+/* ---- image operations (postproc.hpp:112-309): scale(), applyLensDistortion() / distort() / undistort(), despeckle(),
+ * cameraSpaceDistanceToCoords() and cameraSpaceToPMDSpace() ----
+ * Images are [height][width][components] floats, row 0 = bottom; every product and sum is rounded on its own; the device form,
+ * the host form and the reference's function give the same bits.
+ * Sampling rule of resample, lens_warp and distance_to_coords (texture_image.hpp:182-212, float data, no sRGB): uv = tc - floor(tc)
+ * (coordinates outside [0, 1) wrap); uvs = max(0, uv.s * width - 0.5f), x0 = (size_t)uvs, x1 = x0 + 1, both clamped to width - 1,
+ * alpha = uvs - x0, the same for t; value = mix(mix(v00, v10, alpha), mix(v01, v11, alpha), beta), mix(x, y, a) = x + a * (y - x).
+ * A texel is expanded by the component count first (texture_image.hpp:152-177): 3 -> (r, g, b, 1), 4 -> unchanged, 1 -> (v, v, v, 1),
+ * 2 -> (v0, v0, v0, v1), and output component c is component c of the expansion.  OUTPUT COMPONENT 1 OF A TWO-COMPONENT IMAGE IS
+ * THEREFORE COMPONENT 0's VALUE: the reference's functions return that, and it is kept.
+ * A sampling coordinate that is not finite (undefined in the reference) makes every component of that output pixel +0.
+ *   resample             pixel (x, y) of the new_width x new_height output samples at ((x + 0.5f) / new_width, (y + 0.5f) / new_height)
+ *   lens_warp            p = (x + 0.5f) * (1.0f / width), q likewise; forward != 0 (an undistorted render becomes what the lens
+ *                        shows): LensDistortion::undistort with the image's width and height, else LensDistortion::distort; then
+ *                        sampled there.  WPT_DISTORTION_NONE resamples at the pixel centres like every other type.
+ *   despeckle            RGB only.  The 3 x 3 neighbourhood with coordinates clamped to the frame, sorted by luminance (the Y of
+ *                        max_luminance), equal luminances in the neighbourhood's row-major order; the pixel is replaced by sorted
+ *                        element 4 where its luminance is >= element 8's and >= min_factor * element 7's.  Inputs must be finite.
+ *   distance_to_coords   distance = component 0 of the image at LensDistortion::distort(p, q); uv = ((p, q) - dist_center) *
+ *                        dist_inverse_focal_length; xyz = (vec3(uv, 1) / length(vec3(uv, 1))) * distance; the output is three
+ *                        floats (x, y, -z), and with pmd_space != 0 (x, -y, z): the PMD camera's coordinate system.
+ * Of `camera` only distortion_type, k1 .. p2, b1 .. b4 and the three dist_* pairs are read.
+ * All forms refuse with WPT_ERR_INVALID_ARGUMENT before a device is needed: a NULL pointer, a width or height (of the image or of
+ * the output) of 0 or above 65535, a component count outside 1 .. 4 (despeckle: other than 3), an unknown distortion type, a
+ * min_factor that is not finite, an output that overlaps the image.
+ * The device forms are asynchronous on `hip_stream`, one launch each, and take no scratch; the host forms need no device. */
+wpt_status wpt_postproc_resample(const float* image_device, uint32_t width, uint32_t height, uint32_t components, uint32_t new_width,
+        uint32_t new_height, float* out_device, void* hip_stream);
+wpt_status wpt_postproc_resample_host(const float* image_host, uint32_t width, uint32_t height, uint32_t components, uint32_t new_width,
+        uint32_t new_height, float* out_host);
+wpt_status wpt_postproc_lens_warp(const float* image_device, uint32_t width, uint32_t height, uint32_t components, const wpt_camera* camera,
+        int forward, float* out_device, void* hip_stream);
+wpt_status wpt_postproc_lens_warp_host(const float* image_host, uint32_t width, uint32_t height, uint32_t components, const wpt_camera* camera,
+        int forward, float* out_host);
+wpt_status wpt_postproc_despeckle(const float* rgb_device, uint32_t width, uint32_t height, uint32_t components, float min_factor,
+        float* out_device, void* hip_stream);
+wpt_status wpt_postproc_despeckle_host(const float* rgb_host, uint32_t width, uint32_t height, uint32_t components, float min_factor,
+        float* out_host);
+wpt_status wpt_postproc_distance_to_coords(const float* distances_device, uint32_t width, uint32_t height, uint32_t components,
+        const wpt_camera* camera, int pmd_space, float* coords_device, void* hip_stream);
+wpt_status wpt_postproc_distance_to_coords_host(const float* distances_host, uint32_t width, uint32_t height, uint32_t components,
+        const wpt_camera* camera, int pmd_space, float* coords_host);
+/* "tile" (a workgroup's pixels and the ring around them in LDS) or "gather" (nine loads per lane): the form the device's
+ * despeckle takes; both give the same bits */
+const char* wpt_postproc_despeckle_form(void);
+/* A PROCESS-GLOBAL hook for tests and measurements like wpt_set_launch_config: -1 = the form the library was built with, 0 =
+ * gather, 1 = tile.  Results do not depend on it. */
+wpt_status wpt_set_despeckle_form(int form);
+/* the output pixels of one workgroup of the device forms (for tests of sizes around it) */
+void wpt_postproc_image_ops_tile(uint32_t* width, uint32_t* height);
+
 /* Kernel launch geometry knobs (0 = default); for benchmarking only, results do not change.  wpt_set_launch_config,
  * wpt_set_top_nodes and wpt_set_wavefront are PROCESS-GLOBAL hooks for tests and measurements: set them before rendering
  * starts, not while other threads render (MPICoordinator's worker threads read them).

@@ -28,6 +28,7 @@
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
 #include "wpt_denoise_launch.h"
+#include "wpt_image_ops_launch.h"
 #include "wpt_progress.h"
 #include "wpt_progress_state.h"
 
@@ -1631,6 +1632,55 @@ wpt_status denoiseCheck(const void* frame, const void* moments, const void* samp
     return WPT_OK;
 }
 
+/* what a call of the image operations (wpt_image_ops.h) is refused for, on the device or on the host: `what` names the call,
+ * the output holds outWidth x outHeight x outComps floats */
+wpt_status imageOpCheck(const char* what, const void* image, uint32_t width, uint32_t height, uint32_t comps, const void* out,
+        uint32_t outWidth, uint32_t outHeight, uint32_t outComps)
+{
+    const std::string name(what);
+    if (!image || !out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, name + ": the image or the output is NULL");
+    if (width == 0 || height == 0 || width > wptio::SIDE_MAX || height > wptio::SIDE_MAX || outWidth == 0 || outHeight == 0
+            || outWidth > wptio::SIDE_MAX || outHeight > wptio::SIDE_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, name + ": width and height must lie in 1 .. " + std::to_string(uint32_t(wptio::SIDE_MAX)));
+    if (comps < 1 || comps > wptio::COMPONENTS_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, name + ": the image must have 1 .. 4 components");
+    const size_t inBytes = size_t(width) * height * comps * sizeof(float), outBytes = size_t(outWidth) * outHeight * outComps * sizeof(float);
+    const uintptr_t x = reinterpret_cast<uintptr_t>(image), y = reinterpret_cast<uintptr_t>(out);
+    if (x < y + outBytes && y < x + inBytes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, name + ": the output overlaps the image");
+    return WPT_OK;
+}
+
+/* the lens of a warp or of a distance image: only the distortion part of the camera record is read */
+wpt_status imageOpLens(const char* what, const wpt_camera* camera, wptlens::Coeffs& lens)
+{
+    if (!camera)
+        return fail(WPT_ERR_INVALID_ARGUMENT, std::string(what) + ": the camera is NULL");
+    if (camera->distortion_type > WPT_DISTORTION_OPENCV)
+        return fail(WPT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown distortion type " + std::to_string(camera->distortion_type));
+    lens = wptlens::coeffs(*camera);
+    return WPT_OK;
+}
+
+wpt_status despeckleCheck(const void* rgb, uint32_t width, uint32_t height, uint32_t comps, float minFactor, const void* out)
+{
+    if (rgb && out && comps != 3)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "despeckle: the image must have 3 components");
+    WPT_TRY(imageOpCheck("despeckle", rgb, width, height, 3, out, width, height, 3));
+    if (!std::isfinite(minFactor))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "despeckle: min_factor must be finite");
+    return WPT_OK;
+}
+
+/* -1: as built (WPT_DESPECKLE_TILE), 0: gather, 1: tile; wpt_set_despeckle_form */
+int g_despeckleForm = -1;
+
+bool despeckleTile()
+{
+    return g_despeckleForm < 0 ? wptk::despeckleTileByDefault() : g_despeckleForm != 0;
+}
+
 /* what a batch of views is refused for before anything needs the scene or a device */
 wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void* frames, uint32_t width, uint32_t height)
 {
@@ -1832,6 +1882,113 @@ wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* momen
 const char* wpt_postproc_denoise_form(uint32_t step)
 {
     return wptk::denoiseFormOfStep(step);
+}
+
+wpt_status wpt_postproc_resample(const float* image_device, uint32_t width, uint32_t height, uint32_t components, uint32_t new_width,
+        uint32_t new_height, float* out_device, void* hip_stream)
+{
+    WPT_TRY(imageOpCheck("resample", image_device, width, height, components, out_device, new_width, new_height, components));
+    const wptio::Image img = { image_device, width, height, components };
+    const hipError_t e = wptk::launchResample(img, new_width, new_height, out_device, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("resample: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_resample_host(const float* image_host, uint32_t width, uint32_t height, uint32_t components, uint32_t new_width,
+        uint32_t new_height, float* out_host)
+{
+    WPT_TRY(imageOpCheck("resample", image_host, width, height, components, out_host, new_width, new_height, components));
+    const wptio::Image img = { image_host, width, height, components };
+    wptio::resampleHost(img, new_width, new_height, out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_lens_warp(const float* image_device, uint32_t width, uint32_t height, uint32_t components, const wpt_camera* camera,
+        int forward, float* out_device, void* hip_stream)
+{
+    wptlens::Coeffs lens;
+    WPT_TRY(imageOpCheck("lens warp", image_device, width, height, components, out_device, width, height, components));
+    WPT_TRY(imageOpLens("lens warp", camera, lens));
+    const wptio::Image img = { image_device, width, height, components };
+    const hipError_t e = wptk::launchLensWarp(img, lens, forward != 0, out_device, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("lens warp: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_lens_warp_host(const float* image_host, uint32_t width, uint32_t height, uint32_t components, const wpt_camera* camera,
+        int forward, float* out_host)
+{
+    wptlens::Coeffs lens;
+    WPT_TRY(imageOpCheck("lens warp", image_host, width, height, components, out_host, width, height, components));
+    WPT_TRY(imageOpLens("lens warp", camera, lens));
+    const wptio::Image img = { image_host, width, height, components };
+    wptio::warpHost(img, lens, forward != 0, out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_despeckle(const float* rgb_device, uint32_t width, uint32_t height, uint32_t components, float min_factor,
+        float* out_device, void* hip_stream)
+{
+    WPT_TRY(despeckleCheck(rgb_device, width, height, components, min_factor, out_device));
+    const hipError_t e = wptk::launchDespeckle(rgb_device, width, height, min_factor, despeckleTile(), out_device, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("despeckle: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_despeckle_host(const float* rgb_host, uint32_t width, uint32_t height, uint32_t components, float min_factor,
+        float* out_host)
+{
+    WPT_TRY(despeckleCheck(rgb_host, width, height, components, min_factor, out_host));
+    wptio::despeckleHost(rgb_host, width, height, min_factor, out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_distance_to_coords(const float* distances_device, uint32_t width, uint32_t height, uint32_t components,
+        const wpt_camera* camera, int pmd_space, float* coords_device, void* hip_stream)
+{
+    wptlens::Coeffs lens;
+    WPT_TRY(imageOpCheck("distance to coordinates", distances_device, width, height, components, coords_device, width, height, 3));
+    WPT_TRY(imageOpLens("distance to coordinates", camera, lens));
+    const wptio::Image img = { distances_device, width, height, components };
+    const hipError_t e = wptk::launchDistanceToCoords(img, lens, pmd_space != 0, coords_device, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("distance to coordinates: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_distance_to_coords_host(const float* distances_host, uint32_t width, uint32_t height, uint32_t components,
+        const wpt_camera* camera, int pmd_space, float* coords_host)
+{
+    wptlens::Coeffs lens;
+    WPT_TRY(imageOpCheck("distance to coordinates", distances_host, width, height, components, coords_host, width, height, 3));
+    WPT_TRY(imageOpLens("distance to coordinates", camera, lens));
+    const wptio::Image img = { distances_host, width, height, components };
+    wptio::coordsHost(img, lens, pmd_space != 0, coords_host);
+    return WPT_OK;
+}
+
+const char* wpt_postproc_despeckle_form(void)
+{
+    return despeckleTile() ? "tile" : "gather";
+}
+
+wpt_status wpt_set_despeckle_form(int form)
+{
+    if (form < -1 || form > 1)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "despeckle form: -1 (as built), 0 (gather) or 1 (tile)");
+    g_despeckleForm = form;
+    return WPT_OK;
+}
+
+void wpt_postproc_image_ops_tile(uint32_t* width, uint32_t* height)
+{
+    if (width)
+        *width = wptk::IMAGE_OPS_TILE_W;
+    if (height)
+        *height = wptk::IMAGE_OPS_TILE_H;
 }
 
 wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,

@@ -27,6 +27,9 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
            "wpt_postproc_denoise", "wpt_postproc_denoise_host", "wpt_postproc_denoise_form",
+           "wpt_postproc_resample", "wpt_postproc_resample_host", "wpt_postproc_lens_warp", "wpt_postproc_lens_warp_host",
+           "wpt_postproc_despeckle", "wpt_postproc_despeckle_host", "wpt_postproc_distance_to_coords", "wpt_postproc_distance_to_coords_host",
+           "wpt_postproc_despeckle_form", "wpt_set_despeckle_form", "wpt_postproc_image_ops_tile",
            "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_scene_bypassed_nodes", "wpt_bypass_plan", "wpt_set_bypass", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
            "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
            "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
@@ -83,6 +86,19 @@ def lib():
                                                                        C.c_void_p]
             L.wpt_postproc_denoise_form.argtypes = [C.c_uint32]
             L.wpt_postproc_denoise_form.restype = C.c_char_p
+        if hasattr(L, "wpt_postproc_resample"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_postproc_resample.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
+            L.wpt_postproc_resample_host.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p]
+            L.wpt_postproc_lens_warp.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(_abi.Camera), C.c_int, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_lens_warp_host.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(_abi.Camera), C.c_int, C.c_void_p]
+            L.wpt_postproc_despeckle.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_float, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_despeckle_host.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_float, C.c_void_p]
+            L.wpt_postproc_distance_to_coords.argtypes = L.wpt_postproc_lens_warp.argtypes
+            L.wpt_postproc_distance_to_coords_host.argtypes = L.wpt_postproc_lens_warp_host.argtypes
+            L.wpt_postproc_despeckle_form.restype = C.c_char_p
+            L.wpt_set_despeckle_form.argtypes = [C.c_int]
+            L.wpt_postproc_image_ops_tile.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.wpt_postproc_image_ops_tile.restype = None
         L.wpt_render_views_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
@@ -287,6 +303,134 @@ def denoise_host(frame, moments, samples_sqrt, guide, params=None, variance_out=
                                            C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data), w, h, C.byref(p),
                                            C.c_void_p(out.ctypes.data), C.c_void_p(variance.ctypes.data) if variance_out else None))
     return (out, variance) if variance_out else out
+
+
+def _image_tensor(image, what):
+    """(h, w, c) of a CUDA float32 image [h, w, c] or [h, w]"""
+    import torch
+    assert image.is_cuda and image.is_contiguous() and image.dtype == torch.float32 and image.dim() in (2, 3), "%s: a CUDA float32 image [h, w, c]" % what
+    return int(image.shape[0]), int(image.shape[1]), int(image.shape[2]) if image.dim() == 3 else 1
+
+
+def _image_array(image, what):
+    """a float32 numpy image [h, w, c] (from [h, w, c] or [h, w]) and its (h, w, c)"""
+    import numpy as np
+    a = np.ascontiguousarray(image, dtype=np.float32)
+    assert a.ndim in (2, 3), "%s: an image [h, w, c]" % what
+    if a.ndim == 2:
+        a = a[:, :, None]
+    return a, a.shape
+
+
+def _image_launch(image, out_shape, stream):
+    """the output tensor of an image operation and the stream it is launched on, ordered behind the current stream's work"""
+    import torch
+    out = torch.empty(out_shape, dtype=torch.float32, device=image.device)
+    current = torch.cuda.current_stream()
+    launch = stream if stream is not None else current
+    if launch != current:
+        launch.wait_stream(current)
+        out.record_stream(launch)
+        image.record_stream(launch)
+    return out, launch
+
+
+def image_ops_tile():
+    """wpt_postproc_image_ops_tile: (width, height) of the output pixels of one workgroup of the device forms below"""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    lib().wpt_postproc_image_ops_tile(C.byref(w), C.byref(h))
+    return int(w.value), int(h.value)
+
+
+def despeckle_form():
+    """wpt_postproc_despeckle_form: "tile" or "gather", the form the device's despeckle takes"""
+    return lib().wpt_postproc_despeckle_form().decode()
+
+
+def set_despeckle_form(form):
+    """wpt_set_despeckle_form: -1 the form the library was built with, 0 gather, 1 tile (process-global; for tests and measurements)"""
+    _check(lib().wpt_set_despeckle_form(int(form)))
+
+
+def resample(image, new_width, new_height, stream=None):
+    """wpt_postproc_resample (scale() of the reference): a CUDA float32 image [h, w, c], c in 1 .. 4, row 0 at the bottom,
+    resampled bilinearly to [new_height, new_width, c].  Asynchronous on `stream` (None: torch's current stream)."""
+    h, w, c = _image_tensor(image, "resample")
+    out, launch = _image_launch(image, (int(new_height), int(new_width), c) if image.dim() == 3 else (int(new_height), int(new_width)), stream)
+    _check(lib().wpt_postproc_resample(C.c_void_p(image.data_ptr()), w, h, c, int(new_width), int(new_height), C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(launch.cuda_stream)))
+    return out
+
+
+def resample_host(image, new_width, new_height):
+    """wpt_postproc_resample_host: the same on a numpy image on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    a, (h, w, c) = _image_array(image, "resample")
+    out = np.zeros((int(new_height), int(new_width), c), np.float32)
+    _check(lib().wpt_postproc_resample_host(C.c_void_p(a.ctypes.data), w, h, c, int(new_width), int(new_height), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def lens_warp(image, camera, forward, stream=None):
+    """wpt_postproc_lens_warp (applyLensDistortion() of the reference): a CUDA float32 image [h, w, c] through the lens of `camera`
+    (an _abi.Camera, e.g. host.lens_camera(...) or a scene's; only its distortion part is read).  forward: an undistorted render
+    becomes what the lens shows (distort()); otherwise a distorted image is rectified (undistort())."""
+    h, w, c = _image_tensor(image, "lens_warp")
+    out, launch = _image_launch(image, tuple(image.shape), stream)
+    _check(lib().wpt_postproc_lens_warp(C.c_void_p(image.data_ptr()), w, h, c, C.byref(camera), 1 if forward else 0, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(launch.cuda_stream)))
+    return out
+
+
+def lens_warp_host(image, camera, forward):
+    """wpt_postproc_lens_warp_host: the same on a numpy image on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    a, (h, w, c) = _image_array(image, "lens_warp")
+    out = np.zeros((h, w, c), np.float32)
+    _check(lib().wpt_postproc_lens_warp_host(C.c_void_p(a.ctypes.data), w, h, c, C.byref(camera), 1 if forward else 0, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def despeckle(image, min_factor=1.25, stream=None):
+    """wpt_postproc_despeckle (despeckle() of the reference, the firefly filter): a CUDA float32 RGB image [h, w, 3]; a pixel whose
+    luminance is the greatest of its 3 x 3 neighbourhood and at least min_factor times the second greatest becomes the
+    neighbourhood's median pixel.  The values must be finite."""
+    h, w, c = _image_tensor(image, "despeckle")
+    out, launch = _image_launch(image, tuple(image.shape), stream)
+    _check(lib().wpt_postproc_despeckle(C.c_void_p(image.data_ptr()), w, h, c, float(min_factor), C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(launch.cuda_stream)))
+    return out
+
+
+def despeckle_host(image, min_factor=1.25):
+    """wpt_postproc_despeckle_host: the same on a numpy image on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    a, (h, w, c) = _image_array(image, "despeckle")
+    out = np.zeros((h, w, c), np.float32)
+    _check(lib().wpt_postproc_despeckle_host(C.c_void_p(a.ctypes.data), w, h, c, float(min_factor), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def distance_to_coords(distances, camera, pmd_space=False, stream=None):
+    """wpt_postproc_distance_to_coords (cameraSpaceDistanceToCoords() of the reference, and with pmd_space cameraSpaceToPMDSpace()
+    behind it): CUDA float32 distances [h, w] or [h, w, c] (component 0 is the distance from the camera, as the ToF sensor's result
+    and the ground truth's camera_space_distances hold it) to coordinates [h, w, 3]: (x, y, -z) in camera space, or (x, -y, z) in
+    the PMD camera's space.  `camera`: an _abi.Camera; its dist_center, dist_inverse_focal_length and lens are read."""
+    h, w, c = _image_tensor(distances, "distance_to_coords")
+    out, launch = _image_launch(distances, (h, w, 3), stream)
+    _check(lib().wpt_postproc_distance_to_coords(C.c_void_p(distances.data_ptr()), w, h, c, C.byref(camera), 1 if pmd_space else 0,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(launch.cuda_stream)))
+    return out
+
+
+def distance_to_coords_host(distances, camera, pmd_space=False):
+    """wpt_postproc_distance_to_coords_host: the same on a numpy image on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    a, (h, w, c) = _image_array(distances, "distance_to_coords")
+    out = np.zeros((h, w, 3), np.float32)
+    _check(lib().wpt_postproc_distance_to_coords_host(C.c_void_p(a.ctypes.data), w, h, c, C.byref(camera), 1 if pmd_space else 0,
+                                                      C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def _map_int(samples_sqrt):

@@ -146,6 +146,42 @@ def camera_looking_at(scene, eye, target, up=(0.0, 1.0, 0.0)):
     return cam
 
 
+def lens_camera(frustum, model=0, k1=0.0, k2=0.0, k3=0.0, p1=0.0, p2=0.0):
+    """The camera record (_abi.Camera) of a lens on a projection, for the image operations of device.py (lens_warp,
+    distance_to_coords), which read nothing else of it: `frustum` = (l, r, b, t) of Projection at distance 1, `model` and the
+    coefficients as in set_distortion.  dist_center, dist_focal_length and dist_inverse_focal_length are Projection::center(),
+    focalLength() and inverseFocalLength() and b1 .. b4 the RadialOnly model's inverse series, in float32 with the reference's
+    order of operations (optics.hpp:86-99, 170-173).  All-zero coefficients mean no distortion, as there."""
+    f = np.float32
+    l, r, b, t = (f(x) for x in frustum)
+    k1, k2, k3, p1, p2 = (f(x) for x in (k1, k2, k3, p1, p2))
+    if model not in (0, 1, 2, 3):
+        raise ValueError("lens_camera: model 0 (none), 1 (RadialAndPlanar), 2 (RadialOnly) or 3 (OpenCV)")
+    if model == 1:
+        k3 = f(0)
+    elif model == 2:
+        p1 = p2 = f(0)
+    elif model == 0:
+        k1 = k2 = k3 = p1 = p2 = f(0)
+    cam = _abi.Camera()
+    cam.l, cam.r, cam.b, cam.t = l, r, b, t
+    cam.rotation[3] = 1.0
+    cam.scaling[:] = [1.0, 1.0, 1.0]
+    cam.focus_dist = 1.0
+    cam.animation = -1
+    cam.distortion_type = model if any(float(x) != 0.0 for x in (k1, k2, k3, p1, p2)) else 0
+    cam.k1, cam.k2, cam.k3, cam.p1, cam.p2 = k1, k2, k3, p1, p2
+    if model == 2:
+        cam.b1 = -k1
+        cam.b2 = f(3) * k1 * k1 - k2
+        cam.b3 = f(-12) * k1 * k1 * k1 + f(8) * k1 * k2 - k3
+        cam.b4 = f(55) * k1 * k1 * k1 * k1 - f(55) * k1 * k1 * k2 + f(5) * k2 * k2 + f(10) * k1 * k3
+    cam.dist_center[:] = [l / (l - r), b / (b - t)]
+    cam.dist_focal_length[:] = [f(1) / (r - l), f(1) / (t - b)]
+    cam.dist_inverse_focal_length[:] = [r - l, t - b]
+    return cam
+
+
 def cornell(width, height, tall_box_material=0, short_object_material=0):
     """Cornell box of wurblpt-cornellbox.cpp: tall box 0 = white / 1 = GGX metal,
     short box 0 = white / 2 = glass / 3 = glass with a refractive index per channel (chromatic dispersion: the channels'
