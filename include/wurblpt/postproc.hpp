@@ -168,6 +168,53 @@ inline Array<float> denoise(const Array<float>& frame, const Array<float>& momen
             cameraSpaceMaterialNormals, materials, params, variance);
 }
 
+/* The denoiser on the demodulated frame: `albedo` and `emission` (a FirstHitColours' arrays, wurblpt.hpp) are taken out of the
+ * frame before the filter and put back after it, so that a texture is not filtered with the noise (wpt_postproc_denoise_
+ * demodulated_host; wurblpt_hip.h has the rule).  albedoFloor <= 0: the default 1 / 64.  `variance` (optional) receives the
+ * variance of the DEMODULATED luminance.  Everything else as for denoise() above. */
+inline Array<float> denoise(const Array<float>& frame, const Array<float>& moments, const std::vector<uint16_t>& samplesSqrtMap,
+        const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+        const Array<float>& albedo, const Array<float>& emission, const DenoiseParameters& params = DenoiseParameters(),
+        float albedoFloor = 0.0f, Array<float>* variance = nullptr)
+{
+    const size_t width = frame.dimension(0), height = frame.dimension(1), pixels = frame.elementCount();
+    const Array<float>* three[5] = { &moments, &cameraSpacePositions, &cameraSpaceMaterialNormals, &albedo, &emission };
+    for (const Array<float>* a : three)
+        if (a->elementCount() != pixels || a->dimension(0) != width || a->componentCount() != 3)
+            throw std::invalid_argument("denoise: moments, positions, normals, albedo and emission must have the frame's size and three components");
+    if (materials.elementCount() != pixels || materials.dimension(0) != width || materials.componentCount() != 1 || samplesSqrtMap.size() != pixels)
+        throw std::invalid_argument("denoise: the materials and the sample-count map must have the frame's size");
+    const std::vector<float> rgb = postprocdetail::packRgb(frame);
+    std::vector<float> out(rgb.size());
+    if (variance)
+        *variance = Array<float>(width, height, 1);
+    const wpt_denoise_params p = { params.sigmaL, params.sigmaZ, params.normalLog2, params.iterations };
+    if (wpt_postproc_denoise_demodulated_host(rgb.data(), static_cast<const float*>(moments.data()), samplesSqrtMap.data(),
+                static_cast<const float*>(cameraSpacePositions.data()), static_cast<const float*>(cameraSpaceMaterialNormals.data()),
+                static_cast<const int32_t*>(materials.data()), static_cast<const float*>(albedo.data()),
+                static_cast<const float*>(emission.data()), uint32_t(width), uint32_t(height), &p, albedoFloor, out.data(),
+                variance ? static_cast<float*>(variance->data()) : nullptr) != WPT_OK)
+        throw std::runtime_error(std::string("denoise failed: ") + wpt_last_error());
+    Array<float> r(width, height, frame.componentCount());   /* further components stay 0 */
+    r.globalTagList() = frame.globalTagList();
+    for (size_t i = 0; i < pixels; i++)
+        for (size_t c = 0; c < 3; c++)
+            r[i][c] = out[3 * i + c];
+    return r;
+}
+
+/* The same for a frame rendered with samplesSqrt^2 samples in every pixel */
+inline Array<float> denoise(const Array<float>& frame, const Array<float>& moments, unsigned int samplesSqrt,
+        const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+        const Array<float>& albedo, const Array<float>& emission, const DenoiseParameters& params = DenoiseParameters(),
+        float albedoFloor = 0.0f, Array<float>* variance = nullptr)
+{
+    if (samplesSqrt > 65535)
+        throw std::invalid_argument("denoise: samplesSqrt must not exceed 65535");
+    return denoise(frame, moments, std::vector<uint16_t>(frame.elementCount(), uint16_t(samplesSqrt)), cameraSpacePositions,
+            cameraSpaceMaterialNormals, materials, albedo, emission, params, albedoFloor, variance);
+}
+
 /* ---- image operations (postproc.hpp:112-337) ---- */
 
 namespace postprocdetail {

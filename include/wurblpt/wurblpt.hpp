@@ -802,4 +802,72 @@ inline GroundTruth getGroundTruth(const Sensor& sensor, const Camera& camera, co
     return getGroundTruth(sensor, camera, scene, t0, t0, t0, groundTruthBits, params);
 }
 
+/* What the surface behind every pixel's centre multiplies the light with (albedo) and what it emits itself (emission), with the
+ * three arrays of a GroundTruth a denoiser reads, all from one walk per pixel on the device (wpt_first_hit_colours,
+ * wurblpt_hip.h, which has the rule per material).  denoise(..., albedo, emission, ...) takes them (postproc.hpp). */
+class FirstHitColours
+{
+public:
+    Array<float> albedo;                     // 3 components
+    Array<float> emission;                   // 3
+    Array<float> cameraSpacePositions;       // as GroundTruth's
+    Array<float> cameraSpaceMaterialNormals;
+    Array<int32_t> materials;                // Scene::materialIndex() of the hitable's material, -1 where nothing is hit
+};
+
+inline FirstHitColours getFirstHitColours(unsigned int width, unsigned int height, const Camera& camera, const Scene& scene, float t0 = 0.0f,
+        const Parameters& params = Parameters())
+{
+    if (scene.bvhNeedsUpdate(t0, t0))
+        mcptFatal("Scene::updateBVH() must run before getFirstHitColours()");
+    wpt_camera cam;
+    if (!camera.describe(cam, t0))
+        mcptFatal("this camera cannot be described to the device path");
+    FlatScene flat;
+    std::string error;
+    if (!scene.flatten(flat, &error))
+        mcptFatal(error);
+    const wpt_scene_desc desc = flat.desc();
+    wpt_params p;
+    p.max_path_components = params.maxPathComponents;
+    p.rr_threshold = params.rrThreshold;
+    p.randomize_ray_over_pixel = 0;
+    p.min_hit_distance = params.minHitDistance;
+    p.min_dist_to_light = 0.0f;
+    p.max_dist_to_light = std::numeric_limits<float>::max();
+    p.min_path_len = 0.0f;
+    p.max_path_len = std::numeric_limits<float>::max();
+    p.t0 = t0;
+    p.t1 = t0;
+    FirstHitColours fh;
+    fh.albedo = Array<float>(width, height, 3);
+    fh.emission = Array<float>(width, height, 3);
+    fh.cameraSpacePositions = Array<float>(width, height, 3);
+    fh.cameraSpaceMaterialNormals = Array<float>(width, height, 3);
+    fh.materials = Array<int32_t>(width, height, 1);
+    if (wpt_device_count() <= 0)
+        mcptFatal(std::string("no HIP device: ") + wpt_last_error());
+    wpt_scene* dscene = nullptr;
+    if (wpt_scene_upload(&desc, &dscene) != WPT_OK)
+        mcptFatal(wpt_last_error());
+    void* guide[3] = { fh.cameraSpacePositions.data(), fh.cameraSpaceMaterialNormals.data(), fh.materials.data() };
+    const wpt_status st = wpt_first_hit_colours(dscene, &cam, &p, width, height, static_cast<float*>(fh.albedo.data()),
+            static_cast<float*>(fh.emission.data()), guide);
+    wpt_scene_free(dscene);
+    if (st != WPT_OK)
+        mcptFatal(wpt_last_error());
+    /* the kernel reports positions in the flattened material list; the reference reports Scene::materialIndex() */
+    for (size_t i = 0; i < fh.materials.elementCount(); i++) {
+        int32_t& m = fh.materials[i][0];
+        m = (m >= 0 && size_t(m) < flat.materialSceneIndex.size()) ? flat.materialSceneIndex[m] : -1;
+    }
+    return fh;
+}
+
+inline FirstHitColours getFirstHitColours(const Sensor& sensor, const Camera& camera, const Scene& scene, float t0 = 0.0f,
+        const Parameters& params = Parameters())
+{
+    return getFirstHitColours(sensor.width(), sensor.height(), camera, scene, t0, params);
+}
+
 }

@@ -706,6 +706,47 @@ wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* momen
  * with this step takes, decided from the step alone; both give the same bits */
 const char* wpt_postproc_denoise_form(uint32_t step);
 
+/* ---- first-hit colours: what the surface behind a pixel's centre multiplies the light with, and what it emits itself ----
+ * One ray per pixel, exactly the ray of wpt_ground_truth*: pixel centre, no jitter, lens radius 0, time params->t0 (animated
+ * instances, spheres and lens distortion are followed).  All arrays are [height][width][c], row 0 = bottom; any may be NULL:
+ *   albedo    3 floats per pixel          emission  3 floats per pixel
+ *   guide[0]  WPT_GT_CAMERA_SPACE_POSITIONS, guide[1]  WPT_GT_CAMERA_SPACE_MATERIAL_NORMALS, guide[2]  WPT_GT_MATERIALS (int32):
+ *             bit for bit what wpt_ground_truth_device writes for times[0] = params->t0 (`guide` itself may be NULL: none wanted)
+ * The colours look through WPT_MAT_TWOSIDED as the path tracer does (the back child sees the hit from its front); for the
+ * material m they arrive at, with `d` the ray's direction:
+ *   emission  rgb of Material::emitted(m, hit, d): diffuse and spot lights (cone, texture), ModPhong's emissive term; the rgb of
+ *             a time-of-flight light is 0.  No hit: the rgb of the environment map along d, +0 without one.
+ *   albedo    back side: +0, except GLASS.  Front side: LAMBERTIAN, GGX, MIRROR, MODPHONG the rgb of tex[0] / v[0] (albedo, F0,
+ *             mirror colour, diffuse colour: what the kind multiplies the throughput with); GLASS (both sides) and RGL (1, 1, 1);
+ *             NONE, LIGHT_DIFFUSE, LIGHT_SPOT and no hit +0.  ModPhong's specular colour v[1] is not part of it.
+ * Refused with WPT_ERR_INVALID_ARGUMENT before a device is needed: a NULL scene, camera or params, a width or height of 0 or
+ * above 65535, all five outputs NULL, outputs that overlap.  The device form is asynchronous on `hip_stream`. */
+wpt_status wpt_first_hit_colours_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width,
+        uint32_t height, float* albedo_device, float* emission_device, void* const guide_device[3], void* hip_stream);
+/* The same into host arrays (synchronous). */
+wpt_status wpt_first_hit_colours(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        float* albedo_host, float* emission_host, void* const guide_host[3]);
+
+/* ---- the denoiser on the demodulated frame: the surface's own colours are taken out before the filter and put back after it,
+ * so that a texture is not filtered with the noise ----
+ * `albedo`, `emission`: the planes of wpt_first_hit_colours* at the frame's size; everything else as for wpt_postproc_denoise.
+ * `albedo_floor` <= 0: the default 1.0f / 64.  Per pixel and channel c, every operation rounded on its own:
+ *   d_c = albedo_c >= albedo_floor ? albedo_c : 1.0f            u_c = (frame_c - emission_c) / d_c
+ *   v_c = n_p >= 2 ? v(frame_c, moment_c, n_p) / (d_c * d_c) : u_c * u_c        (v: the channel variance of the plain form)
+ *   the filter's colour record is (u_r, u_g, u_b, Y(sqrt(v))^2); the guide and the iterations are those of the plain form
+ *   out_c = c_c * d_c + emission_c after the last iteration (iterations = 0: u_c * d_c + emission_c)
+ * u may be negative where a lamp covers a pixel's centre but not all of its footprint.  `variance` (may be NULL): V of the
+ * DEMODULATED luminance after the last iteration, in the units of u, not of the frame.
+ * Refused as wpt_postproc_denoise is, and for a NULL albedo or emission and an albedo_floor that is NaN or infinite. */
+wpt_status wpt_postproc_denoise_demodulated(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device, const float* albedo_device,
+        const float* emission_device, uint32_t width, uint32_t height, const wpt_denoise_params* params, float albedo_floor,
+        float* out_device, float* variance_device, void* hip_stream);
+wpt_status wpt_postproc_denoise_demodulated_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, const float* albedo_host,
+        const float* emission_host, uint32_t width, uint32_t height, const wpt_denoise_params* params, float albedo_floor,
+        float* out_host, float* variance_host);
+
 /* ---- image operations (postproc.hpp:112-309): scale(), applyLensDistortion() / distort() / undistort(), despeckle(),
  * cameraSpaceDistanceToCoords() and cameraSpaceToPMDSpace() ----
  * Images are [height][width][components] floats, row 0 = bottom; every product and sum is rounded on its own; the device form,

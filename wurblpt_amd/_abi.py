@@ -139,6 +139,7 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_LOG2 = 8, 16
+DENOISE_ALBEDO_FLOOR = 1.0 / 64  # what an albedo_floor <= 0 of wpt_postproc_denoise_demodulated* stands for
 
 
 # the saved state of a progressive session (include/wurblpt_hip.h has the layout)

@@ -28,6 +28,7 @@
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
 #include "wpt_denoise_launch.h"
+#include "wpt_firsthit_launch.h"
 #include "wpt_image_ops_launch.h"
 #include "wpt_progress.h"
 #include "wpt_progress_state.h"
@@ -1632,6 +1633,32 @@ wpt_status denoiseCheck(const void* frame, const void* moments, const void* samp
     return WPT_OK;
 }
 
+/* the same for the demodulated form: the two planes of the first-hit colours beside the inputs, and the floor of the albedo */
+wpt_status denoiseDemodulatedCheck(const void* frame, const void* moments, const void* samplesSqrt, const void* positions, const void* normals,
+        const void* materials, const void* albedo, const void* emission, uint32_t width, uint32_t height, const wpt_denoise_params* params,
+        float& albedoFloor, const void* out, const void* variance, wptdn::Params& filter, uint32_t& iterations)
+{
+    if (!albedo || !emission)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the albedo or the emission plane is NULL");
+    if (!std::isfinite(albedoFloor))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: albedo_floor must be finite (<= 0: the default)");
+    WPT_TRY(denoiseCheck(frame, moments, samplesSqrt, positions, normals, materials, width, height, params, out, variance, filter, iterations));
+    const size_t pixels = size_t(width) * height;
+    const auto overlap = [](const void* a, size_t an, const void* b, size_t bn) {
+        const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+        return x < y + bn && y < x + an;
+    };
+    for (const void* plane : { albedo, emission }) {
+        if (overlap(out, pixels * 12, plane, pixels * 12))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame aliases another array of the call");
+        if (variance && overlap(variance, pixels * 4, plane, pixels * 12))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the variance plane aliases another array of the call");
+    }
+    if (albedoFloor <= 0.0f)
+        albedoFloor = wptdn::k_albedoFloorDefault;
+    return WPT_OK;
+}
+
 /* what a call of the image operations (wpt_image_ops.h) is refused for, on the device or on the host: `what` names the call,
  * the output holds outWidth x outHeight x outComps floats */
 wpt_status imageOpCheck(const char* what, const void* image, uint32_t width, uint32_t height, uint32_t comps, const void* out,
@@ -1882,6 +1909,42 @@ wpt_status wpt_postproc_denoise_host(const float* frame_host, const float* momen
 const char* wpt_postproc_denoise_form(uint32_t step)
 {
     return wptk::denoiseFormOfStep(step);
+}
+
+wpt_status wpt_postproc_denoise_demodulated(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device, const float* albedo_device,
+        const float* emission_device, uint32_t width, uint32_t height, const wpt_denoise_params* params, float albedo_floor,
+        float* out_device, float* variance_device, void* hip_stream)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseDemodulatedCheck(frame_device, moments_device, samples_sqrt_device, positions_device, normals_device, materials_device,
+            albedo_device, emission_device, width, height, params, albedo_floor, out_device, variance_device, filter, iterations));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    wptdn::Rec* scratch = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), size_t(width) * height * 4 * sizeof(wptdn::Rec), stream));
+    const hipError_t e = wptk::launchDenoiseDemodulated(frame_device, moments_device, samples_sqrt_device, positions_device, normals_device,
+            materials_device, albedo_device, emission_device, width, height, filter, iterations, albedo_floor, scratch, out_device,
+            variance_device, stream);
+    (void)hipFreeAsync(scratch, stream);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("denoise: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_denoise_demodulated_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, const float* albedo_host,
+        const float* emission_host, uint32_t width, uint32_t height, const wpt_denoise_params* params, float albedo_floor,
+        float* out_host, float* variance_host)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseDemodulatedCheck(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, albedo_host,
+            emission_host, width, height, params, albedo_floor, out_host, variance_host, filter, iterations));
+    std::vector<wptdn::Rec> scratch(size_t(width) * height * 4);
+    wptdn::denoiseDemodulatedHost(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, albedo_host,
+            emission_host, width, height, filter, iterations, albedo_floor, scratch.data(), out_host, variance_host);
+    return WPT_OK;
 }
 
 wpt_status wpt_postproc_resample(const float* image_device, uint32_t width, uint32_t height, uint32_t components, uint32_t new_width,
@@ -2172,6 +2235,95 @@ wpt_status wpt_ground_truth(wpt_scene* scene, const wpt_camera* camera, const wp
             st = fail(WPT_ERR_HIP, std::string("ground truth: ") + hipGetErrorString(e));
     }
     for (int k = 0; k < WPT_GT_ARRAY_COUNT; k++)
+        if (dev[k])
+            (void)hipFree(dev[k]);
+    return st;
+}
+
+namespace {
+
+/* what a first-hit colour pass is refused for, before a device is needed; `out`: albedo, emission and the three guide arrays */
+wpt_status firstHitCheck(const wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        void* const out[5])
+{
+    if (!scene || !camera || !params)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "first-hit colours: NULL argument");
+    if (width == 0 || height == 0 || width > wptdn::SIDE_MAX || height > wptdn::SIDE_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "first-hit colours: width and height must lie in 1 .. " + std::to_string(uint32_t(wptdn::SIDE_MAX)));
+    const size_t pixels = size_t(width) * height;
+    const size_t bytes[5] = { pixels * 12, pixels * 12, pixels * 12, pixels * 12, pixels * 4 };
+    bool any = false;
+    for (int k = 0; k < 5; k++) {
+        any = any || out[k];
+        for (int j = 0; j < k; j++) {
+            const uintptr_t x = reinterpret_cast<uintptr_t>(out[k]), y = reinterpret_cast<uintptr_t>(out[j]);
+            if (out[k] && out[j] && x < y + bytes[j] && y < x + bytes[k])
+                return fail(WPT_ERR_INVALID_ARGUMENT, "first-hit colours: two outputs overlap");
+        }
+    }
+    if (!any)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "first-hit colours: no output is wanted (all five arrays are NULL)");
+    if (camera->surround_mode > WPT_SURROUND_360)
+        return fail(WPT_ERR_UNSUPPORTED, "camera surround mode is not known to the kernel");
+    if (camera->distortion_type > WPT_DISTORTION_OPENCV)
+        return fail(WPT_ERR_UNSUPPORTED, "lens distortion model is not known to the kernel");
+    return WPT_OK;
+}
+
+}
+
+wpt_status wpt_first_hit_colours_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width,
+        uint32_t height, float* albedo_device, float* emission_device, void* const guide_device[3], void* hip_stream)
+{
+    void* const out[5] = { albedo_device, emission_device, guide_device ? guide_device[0] : nullptr, guide_device ? guide_device[1] : nullptr,
+        guide_device ? guide_device[2] : nullptr };
+    WPT_TRY(firstHitCheck(scene, camera, params, width, height, out));
+    wptk::FirstHitArgs args;
+    args.scene = scene->view;
+    args.cam = *camera;
+    args.par = *params;
+    args.par.t1 = args.par.t0; /* one moment, no exposure interval */
+    args.width = width;
+    args.height = height;
+    args.albedo = albedo_device;
+    args.emission = emission_device;
+    args.positions = static_cast<float*>(out[2]);
+    args.normals = static_cast<float*>(out[3]);
+    args.materials = static_cast<int32_t*>(out[4]);
+    wptk::launchFirstHitColours(args, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return WPT_OK;
+}
+
+wpt_status wpt_first_hit_colours(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        float* albedo_host, float* emission_host, void* const guide_host[3])
+{
+    void* const host[5] = { albedo_host, emission_host, guide_host ? guide_host[0] : nullptr, guide_host ? guide_host[1] : nullptr,
+        guide_host ? guide_host[2] : nullptr };
+    WPT_TRY(firstHitCheck(scene, camera, params, width, height, host));
+    const size_t pixels = size_t(width) * height;
+    const size_t bytes[5] = { pixels * 12, pixels * 12, pixels * 12, pixels * 12, pixels * 4 };
+    void* dev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    wpt_status st = WPT_OK;
+    for (int k = 0; k < 5 && st == WPT_OK; k++) {
+        if (host[k]) {
+            const hipError_t e = hipMalloc(&dev[k], bytes[k]);
+            if (e != hipSuccess)
+                st = fail(e == hipErrorOutOfMemory ? WPT_ERR_OUT_OF_MEMORY : WPT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        }
+    }
+    if (st == WPT_OK)
+        st = wpt_first_hit_colours_device(scene, camera, params, width, height, static_cast<float*>(dev[0]), static_cast<float*>(dev[1]), dev + 2,
+                nullptr);
+    if (st == WPT_OK) {
+        hipError_t e = hipDeviceSynchronize();
+        for (int k = 0; k < 5 && e == hipSuccess; k++)
+            if (dev[k])
+                e = hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            st = fail(WPT_ERR_HIP, std::string("first-hit colours: ") + hipGetErrorString(e));
+    }
+    for (int k = 0; k < 5; k++)
         if (dev[k])
             (void)hipFree(dev[k]);
     return st;

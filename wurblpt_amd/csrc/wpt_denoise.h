@@ -8,7 +8,8 @@
  *   guide A = P.xyz (camera space position of the first hit) and the bits of m (material index, -1 = nothing hit)
  *   guide B = n.xyz (camera space material normal)
  *   colour  = rgb and V, the variance of the luminance
- * prepare() makes them from the render's outputs, filterPixel() is one pixel of one iteration; `Fetch` says where the records
+ * prepare() makes them from the render's outputs (prepareDemodulated() with the surface's own colours taken out, which
+ * finishDemodulated() puts back), filterPixel() is one pixel of one iteration; `Fetch` says where the records
  * of a pixel lie (device memory, a workgroup's tile in LDS, host arrays).
  * Written once; compiled for the device (wpt_k_denoise.hip), for the host (wpt_postproc_denoise_host) and, outside the library
  * and without a header of HIP, by tests/denoise_check.cpp.
@@ -86,6 +87,53 @@ WPT_HD void prepare(const float* frame, const float* moments, uint32_t samplesSq
     colour.y = frame[1];
     colour.z = frame[2];
     colour.w = sigmaY * sigmaY;
+}
+
+/* ---- the demodulated form: the filter runs on (frame - emission) / albedo, the light that arrives at the first hit, and the
+ * surface's own colours are put back afterwards, so that a texture is not filtered with the noise.  `albedo` and `emission`
+ * are the planes of the first-hit colour pass (wpt_first_hit_colours*). ---- */
+constexpr float k_albedoFloorDefault = 1.0f / 64;
+
+/* what a channel is divided by: its albedo, or 1 where the albedo lies below the floor (a dark texel would blow the noise up) */
+WPT_HD float demodulationDivisor(float albedo, float albedoFloor)
+{
+    return albedo >= albedoFloor ? albedo : 1.0f;
+}
+
+/* prepare() for the demodulated form: u = (frame - emission) / d per channel, its variance is the channel's over d * d; a pixel
+ * with fewer than two samples has no estimate, and its standard deviation is taken to be |u|.  u may be negative where a lamp
+ * covers the pixel's centre but not all of its footprint. */
+WPT_HD void prepareDemodulated(const float* frame, const float* moments, uint32_t samplesSqrt, const float* position, const float* normal,
+        int32_t material, const float* albedo, const float* emission, float albedoFloor, Rec& guideA, Rec& guideB, Rec& colour)
+{
+    float u[3], v[3];
+    for (int c = 0; c < 3; c++) {
+        const float d = demodulationDivisor(albedo[c], albedoFloor);
+        u[c] = (frame[c] - emission[c]) / d;
+        v[c] = samplesSqrt >= 2 ? channelVariance(frame[c], moments[c], samplesSqrt) / (d * d) : u[c] * u[c];
+    }
+    const float sigmaY = luminance(__builtin_sqrtf(v[0]), __builtin_sqrtf(v[1]), __builtin_sqrtf(v[2]));
+    guideA.x = position[0];
+    guideA.y = position[1];
+    guideA.z = position[2];
+    guideA.w = wptm::bits_to_float((uint32_t)material);
+    guideB.x = normal[0];
+    guideB.y = normal[1];
+    guideB.z = normal[2];
+    guideB.w = 0.0f;
+    colour.x = u[0];
+    colour.y = u[1];
+    colour.z = u[2];
+    colour.w = sigmaY * sigmaY;
+}
+
+/* the filtered record back to radiance: out = c * d + emission per channel.  The record's w, the variance of the DEMODULATED
+ * luminance, is not converted. */
+WPT_HD void finishDemodulated(const Rec& colour, const float* albedo, const float* emission, float albedoFloor, float* out)
+{
+    out[0] = colour.x * demodulationDivisor(albedo[0], albedoFloor) + emission[0];
+    out[1] = colour.y * demodulationDivisor(albedo[1], albedoFloor) + emission[1];
+    out[2] = colour.z * demodulationDivisor(albedo[2], albedoFloor) + emission[2];
 }
 
 WPT_HD int32_t materialOf(const Rec& guideA)
@@ -184,6 +232,21 @@ struct HostFetch {
     const Rec& colour(int x, int y) const { return c[size_t(y) * width + size_t(x)]; }
 };
 
+/* the iterations on the host: steps 1, 2, 4, ... over the two colour buffers; returns the buffer that holds the result */
+inline Rec* iterateHost(const Rec* a, const Rec* b, Rec* from, Rec* to, uint32_t width, uint32_t height, const Params& params, uint32_t iterations)
+{
+    for (uint32_t i = 0; i < iterations; i++) {
+        const HostFetch fetch = { a, b, from, width };
+        for (uint32_t y = 0; y < height; y++)
+            for (uint32_t x = 0; x < width; x++)
+                to[size_t(y) * width + x] = filterPixel(fetch, int(x), int(y), int(width), int(height), 1 << i, params);
+        Rec* t = from;
+        from = to;
+        to = t;
+    }
+    return from;
+}
+
 /* The whole filter on the host, as the device runs it.  `scratch`: 4 * width * height records (64 bytes per pixel: the two
  * guides and the two colour buffers the iterations alternate between).  `variance` may be NULL. */
 inline void denoiseHost(const float* frame, const float* moments, const uint16_t* samplesSqrt, const float* positions, const float* normals,
@@ -194,22 +257,34 @@ inline void denoiseHost(const float* frame, const float* moments, const uint16_t
     Rec* a = scratch;
     Rec* b = scratch + pixels;
     Rec* from = scratch + 2 * pixels;
-    Rec* to = scratch + 3 * pixels;
     for (size_t p = 0; p < pixels; p++)
         prepare(frame + 3 * p, moments + 3 * p, samplesSqrt[p], positions + 3 * p, normals + 3 * p, materials[p], a[p], b[p], from[p]);
-    for (uint32_t i = 0; i < iterations; i++) {
-        const HostFetch fetch = { a, b, from, width };
-        for (uint32_t y = 0; y < height; y++)
-            for (uint32_t x = 0; x < width; x++)
-                to[size_t(y) * width + x] = filterPixel(fetch, int(x), int(y), int(width), int(height), 1 << i, params);
-        Rec* t = from;
-        from = to;
-        to = t;
-    }
+    from = iterateHost(a, b, from, scratch + 3 * pixels, width, height, params, iterations);
     for (size_t p = 0; p < pixels; p++) {
         out[3 * p] = from[p].x;
         out[3 * p + 1] = from[p].y;
         out[3 * p + 2] = from[p].z;
+        if (variance)
+            variance[p] = from[p].w;
+    }
+}
+
+/* The demodulated form on the host, as the device runs it: the same scratch, the same iterations.  `variance` (may be NULL)
+ * receives the variance of the demodulated luminance. */
+inline void denoiseDemodulatedHost(const float* frame, const float* moments, const uint16_t* samplesSqrt, const float* positions,
+        const float* normals, const int32_t* materials, const float* albedo, const float* emission, uint32_t width, uint32_t height,
+        const Params& params, uint32_t iterations, float albedoFloor, Rec* scratch, float* out, float* variance)
+{
+    const size_t pixels = size_t(width) * height;
+    Rec* a = scratch;
+    Rec* b = scratch + pixels;
+    Rec* from = scratch + 2 * pixels;
+    for (size_t p = 0; p < pixels; p++)
+        prepareDemodulated(frame + 3 * p, moments + 3 * p, samplesSqrt[p], positions + 3 * p, normals + 3 * p, materials[p], albedo + 3 * p,
+                emission + 3 * p, albedoFloor, a[p], b[p], from[p]);
+    from = iterateHost(a, b, from, scratch + 3 * pixels, width, height, params, iterations);
+    for (size_t p = 0; p < pixels; p++) {
+        finishDemodulated(from[p], albedo + 3 * p, emission + 3 * p, albedoFloor, out + 3 * p);
         if (variance)
             variance[p] = from[p].w;
     }

@@ -1,5 +1,5 @@
 /* wpt_k_denoise.hip -- the kernels of the spatial denoiser (wpt_denoise.h; wpt_postproc_denoise in wpt_capi.hip): pack the
- * render's outputs into 16-byte records, one launch per iteration over two colour buffers, unpack the result.  A tap is three
+ * render's outputs into 16-byte records (plain, or demodulated by the first-hit colours), one launch per iteration over two colour buffers, unpack the result.  A tap is three
  * 16-byte loads.  An iteration has two forms that run the same wptdn::filterPixel and so write the same bits:
  *   gather  every lane reads its 25 taps from device memory (the L2 serves the reuse between neighbours)
  *   tile    a workgroup first copies its 32 x 16 pixels and their halo of 2 * step records into LDS and reads the taps there
@@ -59,6 +59,40 @@ __global__ __launch_bounds__(PB) void denoise_unpack(const Rec* __restrict__ col
     out[3 * p] = c.x;
     out[3 * p + 1] = c.y;
     out[3 * p + 2] = c.z;
+    if (variance)
+        variance[p] = c.w;
+}
+
+/* pack and unpack of the demodulated form (wpt_denoise.h, prepareDemodulated / finishDemodulated); the iterations between them
+ * are the kernels below, unchanged */
+__global__ __launch_bounds__(PB) void denoise_pack_demodulated(const float* __restrict__ frame, const float* __restrict__ moments,
+        const uint16_t* __restrict__ samplesSqrt, const float* __restrict__ positions, const float* __restrict__ normals,
+        const int32_t* __restrict__ materials, const float* __restrict__ albedo, const float* __restrict__ emission, float albedoFloor,
+        size_t pixels, Rec* __restrict__ guideA, Rec* __restrict__ guideB, Rec* __restrict__ colour)
+{
+    const size_t p = (size_t)blockIdx.x * PB + threadIdx.x;
+    if (p >= pixels)
+        return;
+    Rec a, b, c;
+    wptdn::prepareDemodulated(frame + 3 * p, moments + 3 * p, samplesSqrt[p], positions + 3 * p, normals + 3 * p, materials[p], albedo + 3 * p,
+            emission + 3 * p, albedoFloor, a, b, c);
+    guideA[p] = a;
+    guideB[p] = b;
+    colour[p] = c;
+}
+
+__global__ __launch_bounds__(PB) void denoise_unpack_demodulated(const Rec* __restrict__ colour, const float* __restrict__ albedo,
+        const float* __restrict__ emission, float albedoFloor, size_t pixels, float* __restrict__ out, float* __restrict__ variance)
+{
+    const size_t p = (size_t)blockIdx.x * PB + threadIdx.x;
+    if (p >= pixels)
+        return;
+    const Rec c = colour[p];
+    float rgb[3];
+    wptdn::finishDemodulated(c, albedo + 3 * p, emission + 3 * p, albedoFloor, rgb);
+    out[3 * p] = rgb[0];
+    out[3 * p + 1] = rgb[1];
+    out[3 * p + 2] = rgb[2];
     if (variance)
         variance[p] = c.w;
 }
@@ -136,17 +170,12 @@ const char* denoiseFormOfStep(uint32_t step)
     return ldsFormForStep(int(step)) ? "tile" : "gather";
 }
 
-hipError_t launchDenoise(const float* frame, const float* moments, const uint16_t* samplesSqrt, const float* positions, const float* normals,
-        const int32_t* materials, uint32_t width, uint32_t height, const wptdn::Params& params, uint32_t iterations, wptdn::Rec* scratch,
-        float* out, float* variance, hipStream_t stream)
+namespace {
+
+/* the iterations in stream order; returns the buffer that holds the result */
+Rec* launchIterations(const Rec* a, const Rec* b, Rec* from, Rec* to, uint32_t width, uint32_t height, const Params& params, uint32_t iterations,
+        hipStream_t stream)
 {
-    const size_t pixels = size_t(width) * height;
-    Rec* a = scratch;
-    Rec* b = scratch + pixels;
-    Rec* from = scratch + 2 * pixels;
-    Rec* to = scratch + 3 * pixels;
-    const dim3 perPixel((uint32_t)((pixels + PB - 1) / PB));
-    hipLaunchKernelGGL(denoise_pack, perPixel, dim3(PB), 0, stream, frame, moments, samplesSqrt, positions, normals, materials, pixels, a, b, from);
     const dim3 tiles((width + TILE_W - 1) / TILE_W, (height + TILE_H - 1) / TILE_H);
     for (uint32_t i = 0; i < iterations; i++) {
         const int step = 1 << i;
@@ -158,7 +187,39 @@ hipError_t launchDenoise(const float* frame, const float* moments, const uint16_
         from = to;
         to = t;
     }
+    return from;
+}
+
+}
+
+hipError_t launchDenoise(const float* frame, const float* moments, const uint16_t* samplesSqrt, const float* positions, const float* normals,
+        const int32_t* materials, uint32_t width, uint32_t height, const wptdn::Params& params, uint32_t iterations, wptdn::Rec* scratch,
+        float* out, float* variance, hipStream_t stream)
+{
+    const size_t pixels = size_t(width) * height;
+    Rec* a = scratch;
+    Rec* b = scratch + pixels;
+    Rec* from = scratch + 2 * pixels;
+    const dim3 perPixel((uint32_t)((pixels + PB - 1) / PB));
+    hipLaunchKernelGGL(denoise_pack, perPixel, dim3(PB), 0, stream, frame, moments, samplesSqrt, positions, normals, materials, pixels, a, b, from);
+    from = launchIterations(a, b, from, scratch + 3 * pixels, width, height, params, iterations, stream);
     hipLaunchKernelGGL(denoise_unpack, perPixel, dim3(PB), 0, stream, from, pixels, out, variance);
+    return hipGetLastError();
+}
+
+hipError_t launchDenoiseDemodulated(const float* frame, const float* moments, const uint16_t* samplesSqrt, const float* positions,
+        const float* normals, const int32_t* materials, const float* albedo, const float* emission, uint32_t width, uint32_t height,
+        const wptdn::Params& params, uint32_t iterations, float albedoFloor, wptdn::Rec* scratch, float* out, float* variance, hipStream_t stream)
+{
+    const size_t pixels = size_t(width) * height;
+    Rec* a = scratch;
+    Rec* b = scratch + pixels;
+    Rec* from = scratch + 2 * pixels;
+    const dim3 perPixel((uint32_t)((pixels + PB - 1) / PB));
+    hipLaunchKernelGGL(denoise_pack_demodulated, perPixel, dim3(PB), 0, stream, frame, moments, samplesSqrt, positions, normals, materials, albedo,
+            emission, albedoFloor, pixels, a, b, from);
+    from = launchIterations(a, b, from, scratch + 3 * pixels, width, height, params, iterations, stream);
+    hipLaunchKernelGGL(denoise_unpack_demodulated, perPixel, dim3(PB), 0, stream, from, albedo, emission, albedoFloor, pixels, out, variance);
     return hipGetLastError();
 }
 

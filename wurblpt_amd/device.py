@@ -27,6 +27,7 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
            "wpt_postproc_denoise", "wpt_postproc_denoise_host", "wpt_postproc_denoise_form",
+           "wpt_first_hit_colours_device", "wpt_first_hit_colours", "wpt_postproc_denoise_demodulated", "wpt_postproc_denoise_demodulated_host",
            "wpt_postproc_resample", "wpt_postproc_resample_host", "wpt_postproc_lens_warp", "wpt_postproc_lens_warp_host",
            "wpt_postproc_despeckle", "wpt_postproc_despeckle_host", "wpt_postproc_distance_to_coords", "wpt_postproc_distance_to_coords_host",
            "wpt_postproc_despeckle_form", "wpt_set_despeckle_form", "wpt_postproc_image_ops_tile",
@@ -86,6 +87,13 @@ def lib():
                                                                        C.c_void_p]
             L.wpt_postproc_denoise_form.argtypes = [C.c_uint32]
             L.wpt_postproc_denoise_form.restype = C.c_char_p
+        if hasattr(L, "wpt_first_hit_colours"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_first_hit_colours_device.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+            L.wpt_first_hit_colours.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+            L.wpt_postproc_denoise_demodulated.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_float,
+                                                                              C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_denoise_demodulated_host.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams),
+                                                                                   C.c_float, C.c_void_p, C.c_void_p]
         if hasattr(L, "wpt_postproc_resample"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
             L.wpt_postproc_resample.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
             L.wpt_postproc_resample_host.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p]
@@ -302,6 +310,76 @@ def denoise_host(frame, moments, samples_sqrt, guide, params=None, variance_out=
     _check(lib().wpt_postproc_denoise_host(C.c_void_p(f.ctypes.data), C.c_void_p(mo.ctypes.data), C.c_void_p(m16.ctypes.data),
                                            C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data), w, h, C.byref(p),
                                            C.c_void_p(out.ctypes.data), C.c_void_p(variance.ctypes.data) if variance_out else None))
+    return (out, variance) if variance_out else out
+
+
+def denoise_demodulated(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0, variance_out=False,
+                        stream=None):
+    """wpt_postproc_denoise_demodulated: denoise() on (frame - emission) / albedo, the surface's own colours put back afterwards
+    (include/wurblpt_hip.h has the rule).  `albedo`, `emission`: CUDA float32 [h, w, 3]; None: the entries "albedo" and
+    "emission" of `guide`, the dict of DeviceScene.first_hit_colours_device.  `albedo_floor` <= 0: the default 1 / 64.  With
+    variance_out the variance of the DEMODULATED luminance [h, w] is returned as well.  Everything else as for denoise()."""
+    import numpy as np
+    import torch
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    P, n, m = _denoise_guide(guide)
+    albedo = guide["albedo"] if albedo is None else albedo
+    emission = guide["emission"] if emission is None else emission
+    for t, what in ((frame, "frame"), (moments, "moments"), (P, "positions"), (n, "normals"), (albedo, "albedo"), (emission, "emission")):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 3), "denoise: %s must be CUDA float32 [h, w, 3]" % what
+    assert m.is_cuda and m.is_contiguous() and m.dtype == torch.int32 and m.numel() == w * h, "denoise: materials must be CUDA int32 [h, w]"
+    if isinstance(samples_sqrt, (int, np.integer)):
+        if not 0 <= int(samples_sqrt) <= 65535:
+            raise ValueError("the sample count's square root must lie in [0, 65535]")
+        samples_sqrt = np.full((h, w), int(samples_sqrt), np.uint16)
+    elif not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
+        _map_int(samples_sqrt)
+    assert tuple(samples_sqrt.shape) == (h, w), "samples_sqrt: [h, w]"
+    current = torch.cuda.current_stream()
+    launch = stream if stream is not None else current
+    m16 = _map_u16_device(samples_sqrt)
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
+    variance = torch.empty((h, w), dtype=torch.float32, device=frame.device) if variance_out else None
+    if launch != current:
+        launch.wait_stream(current)
+        for t in (m16, out, variance):
+            if t is not None:
+                t.record_stream(launch)
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise_demodulated(C.c_void_p(frame.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(m16.data_ptr()),
+                                                  C.c_void_p(P.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(m.data_ptr()),
+                                                  C.c_void_p(albedo.data_ptr()), C.c_void_p(emission.data_ptr()), w, h, C.byref(p),
+                                                  float(albedo_floor), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(variance.data_ptr()) if variance_out else None, C.c_void_p(launch.cuda_stream)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_demodulated_host(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0,
+                             variance_out=False):
+    """wpt_postproc_denoise_demodulated_host: the same of numpy arrays on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    assert f.ndim == 3 and f.shape[2] == 3, "denoise: the frame must be [h, w, 3]"
+    h, w = f.shape[:2]
+    P, n, m = _denoise_guide(guide)
+    albedo = guide["albedo"] if albedo is None else albedo
+    emission = guide["emission"] if emission is None else emission
+    mo, P, n, al, em = (np.ascontiguousarray(a, dtype=np.float32) for a in (moments, P, n, albedo, emission))
+    m = np.ascontiguousarray(m, dtype=np.int32)
+    assert all(a.shape == f.shape for a in (mo, P, n, al, em)) and m.size == w * h, "denoise: arrays of the frame's size"
+    if isinstance(samples_sqrt, (int, np.integer)):
+        samples_sqrt = np.full((h, w), int(samples_sqrt), np.int64)
+    a = _map_int(samples_sqrt)
+    assert a.shape == (h, w), "samples_sqrt: [h, w]"
+    m16 = np.ascontiguousarray(a.astype(np.uint16))
+    out = np.zeros((h, w, 3), np.float32)
+    variance = np.zeros((h, w), np.float32) if variance_out else None
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise_demodulated_host(C.c_void_p(f.ctypes.data), C.c_void_p(mo.ctypes.data), C.c_void_p(m16.ctypes.data),
+                                                       C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data),
+                                                       C.c_void_p(al.ctypes.data), C.c_void_p(em.ctypes.data), w, h, C.byref(p),
+                                                       float(albedo_floor), C.c_void_p(out.ctypes.data),
+                                                       C.c_void_p(variance.ctypes.data) if variance_out else None))
     return (out, variance) if variance_out else out
 
 
@@ -1155,6 +1233,55 @@ class DeviceScene:
                                          C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs,
                                          C.c_void_p(s.cuda_stream)))
         return {GT_NAMES[k]: a for k, a in enumerate(arrays) if a is not None}
+
+    def first_hit_colours_device(self, albedo=True, emission=True, guide=True, params=None, width=None, height=None, stream=None):
+        """wpt_first_hit_colours_device: dict of CUDA tensors left in device memory: "albedo" and "emission" (float32 [h, w, 3]) and,
+        with `guide`, the three arrays of GUIDE_NAMES as ground_truth_device returns them, from the same walk: the dict can be
+        handed to denoise / denoise_demodulated as the guide.  The picture is taken at params.t0.  Asynchronous on `stream`
+        (None: torch's current stream)."""
+        import torch
+        from . import host
+        w = width or self.host.width
+        h = height or self.host.height
+        p = params if params is not None else host.default_params()
+        s = stream if stream is not None else torch.cuda.current_stream()
+        out = {}
+        with torch.cuda.stream(s):
+            for name, wanted in (("albedo", albedo), ("emission", emission)):
+                if wanted:
+                    out[name] = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+            if guide:
+                for name in GUIDE_NAMES:
+                    k = GT_NAMES.index(name)
+                    out[name] = torch.zeros((h, w, GT_COMPONENTS[k]), dtype=torch.int32 if k == 19 else torch.float32, device="cuda")
+        ptrs = (C.c_void_p * 3)(*[out[name].data_ptr() for name in GUIDE_NAMES]) if guide else None
+        _check(lib().wpt_first_hit_colours_device(self._handle, C.cast(self.host.camera, C.c_void_p), C.addressof(p), w, h,
+                                                  C.c_void_p(out["albedo"].data_ptr()) if albedo else None,
+                                                  C.c_void_p(out["emission"].data_ptr()) if emission else None, ptrs,
+                                                  C.c_void_p(s.cuda_stream)))
+        return out
+
+
+def first_hit_colours(scene, albedo=True, emission=True, guide=True, params=None, width=None, height=None):
+    """wpt_first_hit_colours on a DeviceScene: the dict of DeviceScene.first_hit_colours_device as numpy arrays (synchronous)"""
+    import numpy as np
+    from . import host
+    w = width or scene.host.width
+    h = height or scene.host.height
+    p = params if params is not None else host.default_params()
+    out = {}
+    for name, wanted in (("albedo", albedo), ("emission", emission)):
+        if wanted:
+            out[name] = np.zeros((h, w, 3), np.float32)
+    if guide:
+        for name in GUIDE_NAMES:
+            k = GT_NAMES.index(name)
+            out[name] = np.zeros((h, w, GT_COMPONENTS[k]), np.int32 if k == 19 else np.float32)
+    ptrs = (C.c_void_p * 3)(*[out[name].ctypes.data for name in GUIDE_NAMES]) if guide else None
+    _check(lib().wpt_first_hit_colours(scene._handle, C.cast(scene.host.camera, C.c_void_p), C.addressof(p), w, h,
+                                       C.c_void_p(out["albedo"].ctypes.data) if albedo else None,
+                                       C.c_void_p(out["emission"].ctypes.data) if emission else None, ptrs))
+    return out
 
 
 GT_NAMES = ("world_space_positions", "world_space_geometry_normals", "world_space_geometry_tangents",

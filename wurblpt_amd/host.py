@@ -190,6 +190,15 @@ def cornell(width, height, tall_box_material=0, short_object_material=0):
     return HostScene(h, width, height, "cornell(tall=%d,short=%d)" % (tall_box_material, short_object_material))
 
 
+def cornell_checker(width, height):
+    """The Cornell box (GGX tall box, glass short box) whose walls, floor and ceiling carry checker textures of their colour and a
+    quarter of it: a small textured scene, for what a denoiser does to a texture."""
+    L = lib()
+    L.wpt_host_cornell_checker.restype = C.c_void_p
+    L.wpt_host_cornell_checker.argtypes = [C.c_uint, C.c_uint]
+    return HostScene(L.wpt_host_cornell_checker(width, height), width, height, "cornell_checker")
+
+
 SPEED_OF_LIGHT = 299792458.0  # m/s in vacuum (the reference's constants.hpp)
 
 

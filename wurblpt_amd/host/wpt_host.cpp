@@ -63,7 +63,7 @@ void addQuadN(Scene& scene, const Material* material, const float (&p)[4][3], fl
 /* wurblpt-cornellbox.cpp:44-227; shortObjectType 0 (box) only, materials 0 = white,
  * tall box 1 = GGX metal, short box 2 = glass, 3 = glass with chromatic dispersion (not in the reference application) */
 bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, int shortObjectMaterialType, std::string& error,
-        bool spotLight = false)
+        bool spotLight = false, bool checkerWalls = false)
 {
     if (shortObjectType != 0 || shortObjectMaterialType == 1) {
         error = "cornell: only the box short object with white or glass material is built here";
@@ -72,6 +72,14 @@ bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, in
     Material* white = scene.take(new MaterialLambertian(vec3(0.725f, 0.71f, 0.68f)));
     Material* red = scene.take(new MaterialLambertian(vec3(0.63f, 0.065f, 0.05f)));
     Material* green = scene.take(new MaterialLambertian(vec3(0.14f, 0.45f, 0.091f)));
+    /* checkerWalls (not in the reference application): the walls, the floor and the ceiling carry checkers of their colour and
+     * a quarter of it; the boxes stay as they are */
+    Material* room = white;
+    if (checkerWalls) {
+        red = scene.take(new MaterialLambertian(vec3(0.5f), scene.take(new TextureChecker(vec3(0.63f, 0.065f, 0.05f), vec3(0.1575f, 0.01625f, 0.0125f), 8, 8))));
+        green = scene.take(new MaterialLambertian(vec3(0.5f), scene.take(new TextureChecker(vec3(0.14f, 0.45f, 0.091f), vec3(0.035f, 0.1125f, 0.02275f), 8, 8))));
+        room = scene.take(new MaterialLambertian(vec3(0.5f), scene.take(new TextureChecker(vec3(0.725f, 0.71f, 0.68f), vec3(0.18125f, 0.1775f, 0.17f), 8, 8))));
+    }
     /* the spot light is the application's third light variant (wurblpt-cornellbox.cpp:61-63) */
     Material* light = spotLight
         ? scene.take(new MaterialTwoSided(scene.take(new LightSpot(radians(30.0f), vec3(4.0f))), scene.take(new MaterialLambertian(vec3(0.0f)))))
@@ -95,15 +103,15 @@ bool buildCornell(Scene& scene, int tallBoxMaterialType, int shortObjectType, in
     }
     { /* floor */
         const float p[4][3] = { { -1.01f, 0.0f, 0.99f }, { 1.0f, 0.0f, 0.99f }, { 1.0f, 0.0f, -1.04f }, { -0.99f, 0.0f, -1.04f } };
-        addQuadN(scene, white, p, 0.0f, 1.0f, 0.0f);
+        addQuadN(scene, room, p, 0.0f, 1.0f, 0.0f);
     }
     { /* ceiling */
         const float p[4][3] = { { -1.02f, 1.99f, 0.99f }, { -1.02f, 1.99f, -1.04f }, { 1.0f, 1.99f, -1.04f }, { 1.0f, 1.99f, 0.99f } };
-        addQuadN(scene, white, p, 0.0f, -1.0f, 0.0f);
+        addQuadN(scene, room, p, 0.0f, -1.0f, 0.0f);
     }
     { /* back wall */
         const float p[4][3] = { { -0.99f, 0.0f, -1.04f }, { 1.0f, 0.0f, -1.04f }, { 1.0f, 1.99f, -1.04f }, { -1.02f, 1.99f, -1.04f } };
-        addQuadN(scene, white, p, 0.0f, 0.0f, 1.0f);
+        addQuadN(scene, room, p, 0.0f, 0.0f, 1.0f);
     }
     /* short box: left, right, floor, ceiling, back, front */
     {
@@ -466,6 +474,19 @@ wpt_host_scene* wpt_host_cornell(int tallBoxMaterial, int shortObjectType, int s
 {
     wpt_host_scene* hs = new wpt_host_scene;
     if (!buildCornell(hs->scene, tallBoxMaterial, shortObjectType, shortObjectMaterial, hs->error)) {
+        fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
+        delete hs;
+        return nullptr;
+    }
+    return finishScene(hs, width, height, radians(50.0f), vec3(0.0f, 1.0f, 3.2f), vec3(0.0f, 1.0f, -1.0f));
+}
+
+/* The Cornell box with GGX metal tall box and glass short box whose walls, floor and ceiling carry checker textures: a textured
+ * scene small enough for the tests, for what a denoiser does to a texture */
+wpt_host_scene* wpt_host_cornell_checker(unsigned int width, unsigned int height)
+{
+    wpt_host_scene* hs = new wpt_host_scene;
+    if (!buildCornell(hs->scene, 1, 0, 2, hs->error, false, true)) {
         fprintf(stderr, "wpt_host: %s\n", hs->error.c_str());
         delete hs;
         return nullptr;
