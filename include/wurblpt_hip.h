@@ -488,6 +488,76 @@ wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_h
 wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count,
         const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host);
 
+/* ---- sample streams ----
+ * Stream k of a width x height frame is the render in which pixel p's generator is seeded from the index p + k * width * height
+ * instead of p: seed = (uint64)p + (uint64)k * (uint64)(width * height) + 42, then splitmix64 twice as ever.  Everything else is
+ * the plain render, the strata and the factors 1 / n and 1 / n^2 included.  Stream 0 is the plain render bit for bit; the streams
+ * of one frame never share a seed index, and consecutive indices are what neighbouring pixels have.  Streams are a second,
+ * independent sample sequence for a pixel: renders of different streams can be averaged, within one launch (so that a small
+ * frame fills the device) or across calls and devices.
+ *
+ * A batch of views with a stream per view: view v is rendered from cameras_host[v] as stream streams_host[v].  streams_host:
+ * view_count numbers in host memory, or NULL for all 0, which is wpt_render_views[_device]; those are calls of these.  Frames,
+ * counters, kernels and refusals are those of a batch of views. */
+wpt_status wpt_render_view_streams_device(wpt_scene* scene, const wpt_camera* cameras_host, const uint32_t* streams_host,
+        uint32_t view_count, const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        float* frames_device, wpt_counters* counters_device, void* hip_stream);
+wpt_status wpt_render_view_streams(wpt_scene* scene, const wpt_camera* cameras_host, const uint32_t* streams_host,
+        uint32_t view_count, const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host);
+
+/* A split render: one camera in stream_count streams first_stream .. first_stream + stream_count - 1 of stream_samples_sqrt^2
+ * samples each, in ONE launch of the batch-of-views kernels into stream-ordered scratch (stream_count * width * height * 12
+ * bytes, allocated and freed in stream order), then one reduce (wpt_postproc_mean_planes over the scratch):
+ *   frame   = ((f_first + f_first+1) + ...) * (1 / (float)stream_count)         a float sum in stream order,
+ *   moments = ((f_first^2 + f_first+1^2) + ...) * (1 / (float)stream_count)     every operation rounded on its own.
+ * frame: float[height][width][3], row 0 = bottom; moments (may be NULL): the same shape, the stream moment film.  With
+ * N = stream_count it is what the variance formula of the adaptive moment film expects, (moments - frame^2) * N / (N - 1) / N,
+ * and estimates the variance of the pixel's mean from stream_count independent stream means -- unbiased whatever the strata
+ * within a stream, unlike the per-sample moment film.  For stream_count a perfect square, wpt_postproc_denoise takes frame and
+ * moments as they are with samples_sqrt = sqrt(stream_count).  With stream_count == 1 and first_stream == 0 the frame is the
+ * plain render's bits.  counters_device (may be NULL): the sum over all streams, added to.
+ * Refused with WPT_ERR_INVALID_ARGUMENT before a device is needed: stream_count == 0, a NULL frame,
+ * stream_count * width * height > WPT_VIEWS_MAX_PIXELS and first_stream + stream_count beyond 2^32.
+ * Progressive sessions, adaptive maps, the transient, light-group and time-of-flight films and the wavefront form take no streams. */
+wpt_status wpt_render_split_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t stream_samples_sqrt, uint32_t first_stream, uint32_t stream_count, float* frame_device, float* moments_device,
+        wpt_counters* counters_device, void* hip_stream);
+/* Synchronous form: frame_host and moments_host (may be NULL) in host memory. */
+wpt_status wpt_render_split(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t stream_samples_sqrt, uint32_t first_stream, uint32_t stream_count, float* frame_host, float* moments_host);
+
+/* The reduce on its own: the mean of plane_count planes of `pixels` RGB triples that start `stride` floats apart, in plane order
+ * as above, and with moment_out (may be NULL) the mean of their squares.  Asynchronous on `hip_stream`, one lane per value, no
+ * scratch.  Refused: NULL planes or mean_out, plane_count == 0, pixels == 0, planes that overlap (stride < pixels * 3 with more
+ * than one plane).  The host form computes the same bits on the CPU and needs no device; where a result is NaN both are NaN, but
+ * the NaN's sign and payload may differ (inf - inf is a negative NaN on x86, a positive one on the GPU).  The same holds for the
+ * merge below. */
+wpt_status wpt_postproc_mean_planes(const float* planes_device, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        float* mean_out_device, float* moment_out_device, void* hip_stream);
+wpt_status wpt_postproc_mean_planes_host(const float* planes_host, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        float* mean_out_host, float* moment_out_host);
+
+/* Two results of disjoint stream ranges, a over count_a streams and b over count_b, merged into the result of count_a + count_b
+ * streams:  out[i] = ((float)count_a * a[i] + (float)count_b * b[i]) / (float)(count_a + count_b)  in float, every operation
+ * rounded on its own; the same rule for frames and for moment films.  `values` floats each (pixels * 3); out may be a or b.
+ * What later launches and other devices need (first_stream exists for the same reason).  Against one reduce over the whole range
+ * the merge differs by the rounding of another order of sums, a few ulp where no cancellation occurs.  Refused: a NULL pointer,
+ * values == 0, count_a + count_b == 0.  The host form computes the same bits on the CPU and needs no device. */
+wpt_status wpt_postproc_merge_means(const float* a_device, uint32_t count_a, const float* b_device, uint32_t count_b, uint64_t values,
+        float* out_device, void* hip_stream);
+wpt_status wpt_postproc_merge_means_host(const float* a_host, uint32_t count_a, const float* b_host, uint32_t count_b, uint64_t values,
+        float* out_host);
+
+/* How to split a frame of `pixels` pixels and samples_sqrt^2 samples per pixel for a device that holds `lanes` lanes in flight
+ * (wpt_device_lanes): *stream_count = k^2 streams of *stream_samples_sqrt = samples_sqrt / k, where k is a divisor of samples_sqrt
+ * that leaves a stream at least 2 x 2 strata (or 1).  Among those in increasing order the first with k^2 * pixels >= 4 * lanes,
+ * otherwise the largest.  The total sample count is kept exactly, and the stream count is a square (see the denoiser above).
+ * 4 pixels per lane is where a batch of views is near its full rate (profiles/views_rate.txt, profiles/streams_rate.txt).
+ * A pure function that needs no device.  Refused: a zero or NULL argument. */
+wpt_status wpt_split_plan(uint64_t pixels, uint32_t samples_sqrt, uint32_t lanes, uint32_t* stream_count, uint32_t* stream_samples_sqrt);
+/* *lanes = compute units * 1024 of HIP device `device` (wpt_slices_plan's lanes_at_once): what wpt_split_plan is to be given */
+wpt_status wpt_device_lanes(int device, uint32_t* lanes);
+
 /* ---- adaptive sampling ----
  * A sample-count map gives every pixel its own count: uint16_t n_p per pixel, [height][width], row 0 = bottom.  A pixel with
  * n_p > 0 is rendered with n_p^2 samples (strata s % n_p, s / n_p) and its value is bit-identical to the plain render with

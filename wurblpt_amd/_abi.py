@@ -12,6 +12,8 @@ NODE_INNER, NODE_TRIANGLE, NODE_SPHERE, NODE_EMPTY = 0, 1, 2, 3
 MATF_TOF_LIGHT = 16
 TOF_MAX_PHASES = 8
 LIGHT_GROUPS_MAX, LIGHT_GROUP_NONE = 255, 0xff
+VIEWS_MAX_PIXELS = 0x7fffffff  # WPT_VIEWS_MAX_PIXELS: the pixels of a batch of views, and of a split render's streams
+SPLIT_PIXELS_PER_LANE = 4      # wpt_split_plan: the pixels per lane a frame is split for
 MAT_NONE, MAT_LAMBERTIAN, MAT_LIGHT_DIFFUSE, MAT_MIRROR, MAT_GGX, MAT_GLASS, MAT_MODPHONG, MAT_TWOSIDED, MAT_RGL, MAT_LIGHT_SPOT = range(10)
 
 

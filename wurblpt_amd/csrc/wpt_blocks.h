@@ -201,10 +201,9 @@ WPT_D float here(float x)
     return x;
 }
 
-template<class PS> WPT_D void pathStateInit(PS& ps, uint32_t pixel, uint32_t px, uint32_t py)
+/* the state a pixel (px, py) starts with; its generator is `prng` */
+template<class PS> WPT_D void pathStateInit(PS& ps, const Prng& prng, uint32_t px, uint32_t py)
 {
-    Prng prng;
-    prngSeed(prng, pixel);
     storePrng(ps, prng);
     const f4 one = mk4(1.0f, 1.0f, 1.0f, 1.0f);
     ps.set4(SLOT_ATT, one);
@@ -229,6 +228,20 @@ template<class PS> WPT_D void pathStateInit(PS& ps, uint32_t pixel, uint32_t px,
     ps.neeKind = 0;
     ps.time = 0.0f;
     ps.animCached = -1;
+}
+/* ... seeded from the pixel's index in its frame */
+template<class PS> WPT_D void pathStateInit(PS& ps, uint32_t pixel, uint32_t px, uint32_t py)
+{
+    Prng prng;
+    prngSeed(prng, pixel);
+    pathStateInit(ps, prng, px, py);
+}
+/* ... seeded from a 64-bit index: pixel + stream * pixels of a sample stream (batches of views) */
+template<class PS> WPT_D void pathStateInit(PS& ps, uint64_t seedIndex, uint32_t px, uint32_t py)
+{
+    Prng prng;
+    prngSeed(prng, seedIndex);
+    pathStateInit(ps, prng, px, py);
 }
 
 /* What HitableTriangle::pdfValue (hitable_triangle.hpp:405-423) derives from the corners alone: the unit face normal and

@@ -30,6 +30,7 @@
 #include "wpt_denoise_launch.h"
 #include "wpt_firsthit_launch.h"
 #include "wpt_image_ops_launch.h"
+#include "wpt_streams_launch.h"
 #include "wpt_progress.h"
 #include "wpt_progress_state.h"
 
@@ -1726,6 +1727,76 @@ wpt_status viewsCheck(const wpt_camera* cameras, uint32_t viewCount, const void*
     return WPT_OK;
 }
 
+/* what a split render is refused for before anything needs the scene or a device */
+wpt_status splitCheck(const wpt_camera* camera, uint32_t width, uint32_t height, uint32_t firstStream, uint32_t streamCount, const void* frame)
+{
+    if (streamCount == 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split: stream_count is 0");
+    if (!camera)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split: the camera is NULL");
+    if (!frame)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split: the frame is NULL");
+    if (uint64_t(streamCount) * width * height > WPT_VIEWS_MAX_PIXELS)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split: stream_count * width * height exceeds " + std::to_string(WPT_VIEWS_MAX_PIXELS) + " pixels");
+    if (uint64_t(firstStream) + streamCount > 0x100000000ull)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split: first_stream + stream_count exceeds 2^32");
+    return WPT_OK;
+}
+
+/* what a mean of planes is refused for, on the device or on the host */
+wpt_status meanCheck(const void* planes, uint32_t planeCount, uint64_t stride, uint64_t pixels, const void* mean)
+{
+    if (!planes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mean of planes: the planes are NULL");
+    if (!mean)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mean of planes: mean_out is NULL");
+    if (planeCount == 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mean of planes: plane_count is 0");
+    if (pixels == 0 || pixels > wptk::STREAMS_MAX_VALUES / 3)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mean of planes: bad pixel count");
+    if (planeCount > 1 && stride < pixels * 3)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "mean of planes: the planes overlap (stride below pixels * 3)");
+    return WPT_OK;
+}
+
+/* what a merge of two means is refused for, on the device or on the host */
+wpt_status mergeCheck(const void* a, uint32_t countA, const void* b, uint32_t countB, uint64_t values, const void* out)
+{
+    if (!a || !b || !out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "merge of means: NULL argument");
+    if (uint64_t(countA) + countB == 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "merge of means: count_a + count_b is 0");
+    if (values == 0 || values > wptk::STREAMS_MAX_VALUES)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "merge of means: bad value count");
+    return WPT_OK;
+}
+
+/* what a batch of views is refused for: viewsCheck, and with the scene at hand what needs it */
+wpt_status viewsChecked(const wpt_scene* scene, const wpt_camera* cameras, uint32_t viewCount, const wpt_params* params, uint32_t width,
+        uint32_t height, uint32_t samplesSqrt, const void* frames)
+{
+    WPT_TRY(viewsCheck(cameras, viewCount, frames, width, height));
+    if (!scene || !params)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t v = 0; v < viewCount; v++)
+        if (cameras[v].animation >= int32_t(scene->animationCount))
+            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
+    return checkFrameBlock(width, height, &samplesSqrt, 0, 0);
+}
+
+/* the launch of a batch whose cameras and stream numbers (or NULL: all 0) are in device memory, written in stream order before
+ * it; camerasHost: the same cameras, read for the launch's features */
+wpt_status viewsLaunch(wpt_scene* scene, const wpt_camera* camerasHost, const wpt_camera* camerasDevice, const uint32_t* streamsDevice,
+        uint32_t viewCount, const wpt_params* params, uint32_t width, uint32_t height, uint32_t samplesSqrt, float* frames,
+        wpt_counters* counters, void* hipStream)
+{
+    LaunchRequest rq = { scene, camerasHost, params, width, height, samplesSqrt, 0, viewCount * width * height, frames, hipStream };
+    rq.counters = counters;
+    rq.sensor = wptk::SENSOR_VIEWS;
+    rq.views = { camerasDevice, width * height, viewCount, streamsDevice };
+    return renderLaunch(rq);
+}
+
 /* what an adaptive render is refused for before anything needs the scene or a device (every 16-bit count is valid) */
 wpt_status adaptiveCheck(uint32_t width, uint32_t height, const void* map, uint32_t blockStart, uint32_t blockSize, const void* frame)
 {
@@ -2054,45 +2125,157 @@ void wpt_postproc_image_ops_tile(uint32_t* width, uint32_t* height)
         *height = wptk::IMAGE_OPS_TILE_H;
 }
 
-wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
-        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device, void* hip_stream)
+wpt_status wpt_render_view_streams_device(wpt_scene* scene, const wpt_camera* cameras_host, const uint32_t* streams_host, uint32_t view_count,
+        const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device,
+        void* hip_stream)
 {
-    WPT_TRY(viewsCheck(cameras_host, view_count, frames_device, width, height));
-    if (!scene || !params)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (uint32_t v = 0; v < view_count; v++)
-        if (cameras_host[v].animation >= int32_t(scene->animationCount))
-            return fail(WPT_ERR_INVALID_ARGUMENT, "views: camera " + std::to_string(v) + " refers to an animation outside the scene's array");
-    WPT_TRY(checkFrameBlock(width, height, &samples_sqrt, 0, 0));
+    WPT_TRY(viewsChecked(scene, cameras_host, view_count, params, width, height, samples_sqrt, frames_device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    /* the cameras go to device memory once per batch, in stream order */
-    const size_t camBytes = size_t(view_count) * sizeof(wpt_camera);
+    /* the cameras, and behind them the views' stream numbers, go to device memory once per batch, in stream order */
+    const size_t camBytes = size_t(view_count) * sizeof(wpt_camera), streamBytes = streams_host ? size_t(view_count) * sizeof(uint32_t) : 0;
+    static_assert(sizeof(wpt_camera) % alignof(uint32_t) == 0, "the stream numbers lie behind the cameras");
     wpt_camera* dCams = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dCams), camBytes, stream));
-    const hipError_t e = hipMemcpyAsync(dCams, cameras_host, camBytes, hipMemcpyHostToDevice, stream);
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dCams), camBytes + streamBytes, stream));
+    uint32_t* dStreams = streams_host ? reinterpret_cast<uint32_t*>(dCams + view_count) : nullptr;
+    hipError_t e = hipMemcpyAsync(dCams, cameras_host, camBytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && streams_host)
+        e = hipMemcpyAsync(dStreams, streams_host, streamBytes, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) {
         (void)hipFreeAsync(dCams, stream);
         return fail(WPT_ERR_HIP, std::string("views: ") + hipGetErrorString(e));
     }
-    LaunchRequest rq = { scene, cameras_host, params, width, height, samples_sqrt, 0, view_count * width * height, frames_device, hip_stream };
-    rq.counters = counters_device;
-    rq.sensor = wptk::SENSOR_VIEWS;
-    rq.views = { dCams, width * height, view_count };
-    const wpt_status st = renderLaunch(rq);
+    const wpt_status st = viewsLaunch(scene, cameras_host, dCams, dStreams, view_count, params, width, height, samples_sqrt, frames_device,
+            counters_device, hip_stream);
     (void)hipFreeAsync(dCams, stream);
     return st;
 }
 
-wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
-        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
+wpt_status wpt_render_view_streams(wpt_scene* scene, const wpt_camera* cameras_host, const uint32_t* streams_host, uint32_t view_count,
+        const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
 {
     WPT_TRY(viewsCheck(cameras_host, view_count, frames_host, width, height));
     if (!scene)
         return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
     StagedBlock frames;
     HIP_TRY(frames.allocatePixels(size_t(view_count) * width * height));
-    return finishStaged(wpt_render_views_device(scene, cameras_host, view_count, params, width, height, samples_sqrt, frames.biased(0), nullptr,
-            nullptr), scene, frames, frames_host);
+    return finishStaged(wpt_render_view_streams_device(scene, cameras_host, streams_host, view_count, params, width, height, samples_sqrt,
+            frames.biased(0), nullptr, nullptr), scene, frames, frames_host);
+}
+
+wpt_status wpt_render_views_device(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_device, wpt_counters* counters_device, void* hip_stream)
+{
+    return wpt_render_view_streams_device(scene, cameras_host, nullptr, view_count, params, width, height, samples_sqrt, frames_device,
+            counters_device, hip_stream);
+}
+
+wpt_status wpt_render_views(wpt_scene* scene, const wpt_camera* cameras_host, uint32_t view_count, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, float* frames_host)
+{
+    return wpt_render_view_streams(scene, cameras_host, nullptr, view_count, params, width, height, samples_sqrt, frames_host);
+}
+
+wpt_status wpt_render_split_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t stream_samples_sqrt, uint32_t first_stream, uint32_t stream_count, float* frame_device, float* moments_device,
+        wpt_counters* counters_device, void* hip_stream)
+{
+    WPT_TRY(splitCheck(camera, width, height, first_stream, stream_count, frame_device));
+    /* the streams are a batch of views of one camera: view i is stream first_stream + i (the host's copies are read for the
+     * launch's checks and features only, before this returns) */
+    const std::vector<wpt_camera> cameras(stream_count, *camera);
+    WPT_TRY(viewsChecked(scene, cameras.data(), stream_count, params, width, height, stream_samples_sqrt, frame_device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    /* one allocation in stream order: the streams' frames, then their cameras and numbers, which a kernel writes (nothing
+     * of the host's is read once the call has returned) */
+    const size_t values = size_t(width) * height * 3, frameBytes = values * stream_count * sizeof(float);
+    const size_t camBytes = size_t(stream_count) * sizeof(wpt_camera);
+    static_assert(alignof(wpt_camera) <= alignof(float), "the cameras lie behind the streams' frames");
+    float* scratch = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), frameBytes + camBytes + size_t(stream_count) * sizeof(uint32_t), stream));
+    wpt_camera* dCams = reinterpret_cast<wpt_camera*>(scratch + values * stream_count);
+    uint32_t* dStreams = reinterpret_cast<uint32_t*>(dCams + stream_count);
+    wpt_status st = WPT_OK;
+    hipError_t e = wptk::launchFillStreamViews(*camera, first_stream, stream_count, dCams, dStreams, stream);
+    if (e == hipSuccess) {
+        st = viewsLaunch(scene, cameras.data(), dCams, dStreams, stream_count, params, width, height, stream_samples_sqrt, scratch,
+                counters_device, hip_stream);
+        if (st == WPT_OK)
+            e = wptk::launchMeanPlanes(scratch, stream_count, values, values, frame_device, moments_device, stream);
+    }
+    (void)hipFreeAsync(scratch, stream);
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("split: ") + hipGetErrorString(e));
+    return st;
+}
+
+wpt_status wpt_render_split(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width, uint32_t height,
+        uint32_t stream_samples_sqrt, uint32_t first_stream, uint32_t stream_count, float* frame_host, float* moments_host)
+{
+    WPT_TRY(splitCheck(camera, width, height, first_stream, stream_count, frame_host));
+    if (!scene)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    StagedBlock frame, moments;
+    HIP_TRY(frame.allocatePixels(size_t(width) * height));
+    if (moments_host)
+        HIP_TRY(moments.allocatePixels(size_t(width) * height));
+    return finishStaged(wpt_render_split_device(scene, camera, params, width, height, stream_samples_sqrt, first_stream, stream_count,
+            frame.biased(0), moments.biased(0), nullptr, nullptr), scene, frame, frame_host, &moments, moments_host);
+}
+
+wpt_status wpt_postproc_mean_planes(const float* planes_device, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        float* mean_out_device, float* moment_out_device, void* hip_stream)
+{
+    WPT_TRY(meanCheck(planes_device, plane_count, stride, pixels, mean_out_device));
+    const hipError_t e = wptk::launchMeanPlanes(planes_device, plane_count, size_t(stride), pixels * 3, mean_out_device, moment_out_device,
+            static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("mean of planes: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_mean_planes_host(const float* planes_host, uint32_t plane_count, uint64_t stride, uint64_t pixels,
+        float* mean_out_host, float* moment_out_host)
+{
+    WPT_TRY(meanCheck(planes_host, plane_count, stride, pixels, mean_out_host));
+    wptstr::meanHost(planes_host, plane_count, size_t(stride), pixels * 3, mean_out_host, moment_out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_merge_means(const float* a_device, uint32_t count_a, const float* b_device, uint32_t count_b, uint64_t values,
+        float* out_device, void* hip_stream)
+{
+    WPT_TRY(mergeCheck(a_device, count_a, b_device, count_b, values, out_device));
+    const hipError_t e = wptk::launchMergeMeans(a_device, count_a, b_device, count_b, values, out_device, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess)
+        return fail(WPT_ERR_HIP, std::string("merge of means: ") + hipGetErrorString(e));
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_merge_means_host(const float* a_host, uint32_t count_a, const float* b_host, uint32_t count_b, uint64_t values,
+        float* out_host)
+{
+    WPT_TRY(mergeCheck(a_host, count_a, b_host, count_b, values, out_host));
+    wptstr::mergeHost(a_host, count_a, b_host, count_b, values, out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_split_plan(uint64_t pixels, uint32_t samples_sqrt, uint32_t lanes, uint32_t* stream_count, uint32_t* stream_samples_sqrt)
+{
+    if (!stream_count || !stream_samples_sqrt)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split plan: NULL argument");
+    if (!wptstr::splitPlan(pixels, samples_sqrt, lanes, stream_count, stream_samples_sqrt))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "split plan: pixels, samples_sqrt and lanes must be above 0");
+    return WPT_OK;
+}
+
+wpt_status wpt_device_lanes(int device, uint32_t* lanes)
+{
+    if (!lanes)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "device lanes: NULL argument");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    *lanes = uint32_t(prop.multiProcessorCount) * 1024u;
+    return WPT_OK;
 }
 
 wpt_status wpt_render_adaptive_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,

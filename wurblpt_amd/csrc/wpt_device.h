@@ -100,15 +100,20 @@ WPT_D uint64_t splitmix64(uint64_t x)
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
     return z ^ (z >> 31);
 }
-WPT_D void prngSeed(Prng& p, uint32_t pixelIndex)
+/* the generator of seed index `index`: a pixel's index in its frame, or pixel + stream * pixels of a sample stream (64 bits) */
+WPT_D void prngSeed(Prng& p, uint64_t index)
 {
-    uint64_t seed = (uint64_t)pixelIndex + 42ull;
+    uint64_t seed = index + 42ull;
     uint64_t s01 = splitmix64(seed);
     uint64_t s23 = splitmix64(s01);
     p.s0 = (uint32_t)(s01 >> 32);
     p.s1 = (uint32_t)(s01 & 0xffffffffull);
     p.s2 = (uint32_t)(s23 >> 32);
     p.s3 = (uint32_t)(s23 & 0xffffffffull);
+}
+WPT_D void prngSeed(Prng& p, uint32_t pixelIndex)
+{
+    prngSeed(p, (uint64_t)pixelIndex);
 }
 WPT_D float in01(Prng& p)
 {

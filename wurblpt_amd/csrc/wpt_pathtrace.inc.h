@@ -73,11 +73,14 @@ constexpr uint32_t LEAF_NODE_SHIFT = 16, LEAF_NODE_MAX = 0x7fffu, LEAF_CORNER_MA
 static_assert(sizeof(wpt_material) % 16 == 0 && alignof(wpt_material) <= 16, "wpt_material must be a whole number of quadwords");
 /* A batch of views (FEAT_VIEWS kernels): the launch's lane indices g in [0, viewCount * viewPixels) are view g / viewPixels,
  * pixel g % viewPixels of that view's frame; view v is rendered from cams[v] into frame + v * viewPixels * 3.  A pixel's
- * generator is seeded from its index in its own frame, so view v is the plain render of cams[v] bit for bit. */
+ * generator is seeded from its index in its own frame, so view v is the plain render of cams[v] bit for bit.
+ * Sample streams: with `streams`, pixel p of view v is seeded from the 64-bit index p + streams[v] * viewPixels instead, and
+ * everything else stays the plain render; stream 0 is the plain render, and streams of one frame never share an index. */
 struct ViewsView {
     const wpt_camera* cams; /* viewCount cameras in device memory */
     uint32_t viewPixels;    /* width * height */
     uint32_t viewCount;
+    const uint32_t* streams; /* viewCount stream numbers in device memory, or NULL: all 0 */
 };
 /* Adaptive sampling (FEAT_ADAPTIVE kernels): pixel p is rendered with n_p^2 samples, n_p = samplesSqrt[p], with the strata,
  * 1 / n_p and 1 / n_p^2 of the plain render at samplesSqrt = n_p, so that its value is that render's bit for bit; a pixel with
@@ -157,6 +160,7 @@ struct KernelArgs {
  * stay as they were */
 static_assert(sizeof(AdaptiveView) <= sizeof(BinsView) && alignof(AdaptiveView) <= alignof(BinsView), "AdaptiveView must fit in BinsView's place");
 static_assert(sizeof(SlicesView) <= sizeof(BinsView) && alignof(SlicesView) <= alignof(BinsView), "SlicesView must fit in BinsView's place");
+static_assert(sizeof(ViewsView) <= sizeof(BinsView) && alignof(ViewsView) <= alignof(BinsView), "ViewsView must fit in BinsView's place");
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
 WPT_D bool lanePixel(const KernelArgs& args, uint32_t gid, uint32_t& pixel)
@@ -412,7 +416,13 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
         } else {
             have = pixelOf(at, pixel);
         }
-        pathStateInit(ps, pixel, pixel % args.width, pixel / args.width);
+        if constexpr (VIEWS) {
+            /* the view's sample stream moves the generator's index on by whole frames, in 64 bits (ViewsView) */
+            const uint64_t stream = args.views.streams ? args.views.streams[view] : 0u;
+            pathStateInit(ps, (uint64_t)pixel + stream * args.views.viewPixels, pixel % args.width, pixel / args.width);
+        } else {
+            pathStateInit(ps, pixel, pixel % args.width, pixel / args.width);
+        }
         if constexpr (ADAPTIVE) {
             laneSqrt = have ? (uint32_t)args.adaptive.samplesSqrt[pixel] : 0u;
             ps.sampleSum = mk3(0.0f, 0.0f, 0.0f);

@@ -24,6 +24,9 @@ EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_s
            "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
            "wpt_render_block_device", "wpt_render_block",
            "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
+           "wpt_render_view_streams_device", "wpt_render_view_streams", "wpt_render_split_device", "wpt_render_split",
+           "wpt_postproc_mean_planes", "wpt_postproc_mean_planes_host", "wpt_postproc_merge_means", "wpt_postproc_merge_means_host",
+           "wpt_split_plan", "wpt_device_lanes",
            "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
            "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
            "wpt_postproc_denoise", "wpt_postproc_denoise_host", "wpt_postproc_denoise_form",
@@ -111,6 +114,19 @@ def lib():
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        if hasattr(L, "wpt_render_split"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
+            L.wpt_render_view_streams_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_void_p, C.c_uint32, C.POINTER(_abi.Params),
+                                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_render_view_streams.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_void_p, C.c_uint32, C.POINTER(_abi.Params),
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.wpt_render_split_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params)] + [C.c_uint32] * 5 + [C.c_void_p] * 4
+            L.wpt_render_split.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params)] + [C.c_uint32] * 5 + [C.c_void_p] * 2
+            L.wpt_postproc_mean_planes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_mean_planes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+            L.wpt_postproc_merge_means_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+            L.wpt_split_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.wpt_device_lanes.argtypes = [C.c_int, C.POINTER(C.c_uint32)]
         L.wpt_render_adaptive_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
                                                        C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wpt_render_adaptive_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
@@ -230,6 +246,99 @@ def mix_planes_host(planes, weights):
     _check(lib().wpt_postproc_mix_planes_host(C.c_void_p(p.ctypes.data), K, pixels * 3, pixels, C.c_void_p(w.ctypes.data),
                                               C.c_void_p(out.ctypes.data)))
     return out
+
+
+def mean_planes(planes, with_moment=False, mean_out=None, moment_out=None, stream=None):
+    """wpt_postproc_mean_planes: CUDA float32 planes [K, ..., 3] (the frames of K sample streams) reduced to their mean [..., 3],
+    ((P0 + P1) + ...) * (1 / float32(K)) in float32, planes in order, each operation rounded on its own; with_moment (or a
+    moment_out) also the mean of their squares, the stream moment film.  Asynchronous on `stream` (default: torch's current
+    stream); returns the mean, or (mean, moment)."""
+    import torch
+    assert planes.is_cuda and planes.is_contiguous() and planes.dtype == torch.float32 and planes.dim() >= 3 and planes.shape[-1] == 3
+    K = planes.shape[0]
+    if K == 0:
+        raise ValueError("mean_planes: no planes")
+    if mean_out is None:
+        mean_out = torch.empty(tuple(planes.shape[1:]), dtype=torch.float32, device=planes.device)
+    if moment_out is None and with_moment:
+        moment_out = torch.empty(tuple(planes.shape[1:]), dtype=torch.float32, device=planes.device)
+    pixels = planes[0].numel() // 3
+    for t in (mean_out, moment_out):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == pixels * 3)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _check(lib().wpt_postproc_mean_planes(C.c_void_p(planes.data_ptr()), K, pixels * 3, pixels, C.c_void_p(mean_out.data_ptr()),
+                                          C.c_void_p(moment_out.data_ptr()) if moment_out is not None else None,
+                                          C.c_void_p(s.cuda_stream)))
+    return (mean_out, moment_out) if moment_out is not None else mean_out
+
+
+def mean_planes_host(planes, with_moment=False):
+    """wpt_postproc_mean_planes_host: the same mean (and moment) of numpy planes [K, ..., 3] on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    p = np.ascontiguousarray(planes, dtype=np.float32)
+    assert p.ndim >= 3 and p.shape[-1] == 3
+    K = p.shape[0]
+    mean = np.zeros(p.shape[1:], np.float32)
+    moment = np.zeros(p.shape[1:], np.float32) if with_moment else None
+    pixels = mean.size // 3
+    _check(lib().wpt_postproc_mean_planes_host(C.c_void_p(p.ctypes.data), K, pixels * 3, pixels, C.c_void_p(mean.ctypes.data),
+                                               C.c_void_p(moment.ctypes.data) if with_moment else None))
+    return (mean, moment) if with_moment else mean
+
+
+def merge_means(a, count_a, b, count_b, out=None, stream=None):
+    """wpt_postproc_merge_means: two CUDA float32 results of one shape (frames or moment films), `a` over count_a sample streams
+    and `b` over count_b others, merged into the result of count_a + count_b streams:
+    (float32(count_a) * a + float32(count_b) * b) / float32(count_a + count_b), each operation rounded on its own.  `out` may be
+    `a` or `b`.  Asynchronous on `stream` (default: torch's current stream); returns `out`."""
+    import torch
+    for t in (a, b):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
+    assert a.shape == b.shape, "merge_means: results of one shape"
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == a.numel()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _check(lib().wpt_postproc_merge_means(C.c_void_p(a.data_ptr()), int(count_a), C.c_void_p(b.data_ptr()), int(count_b), a.numel(),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def merge_means_host(a, count_a, b, count_b):
+    """wpt_postproc_merge_means_host: the same merge of numpy arrays on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    assert a.shape == b.shape, "merge_means: results of one shape"
+    out = np.zeros(a.shape, np.float32)
+    _check(lib().wpt_postproc_merge_means_host(C.c_void_p(a.ctypes.data), int(count_a), C.c_void_p(b.ctypes.data), int(count_b), a.size,
+                                               C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def device_lanes(device=None):
+    """wpt_device_lanes: compute units * 1024 of HIP device `device` (None: the current one)"""
+    if device is None:
+        current = C.c_int(0)
+        _check(lib().wpt_current_device(C.byref(current)))
+        device = current.value
+    lanes = C.c_uint32(0)
+    _check(lib().wpt_device_lanes(int(device), C.byref(lanes)))
+    return int(lanes.value)
+
+
+def split_plan(pixels, samples_sqrt, lanes=None):
+    """wpt_split_plan: (stream_count, stream_samples_sqrt) a frame of `pixels` pixels and samples_sqrt^2 samples per pixel is split
+    into for a device that holds `lanes` lanes (None: device_lanes() of the current device); stream_count is a square and
+    stream_count * stream_samples_sqrt^2 == samples_sqrt^2.  With `lanes` given it needs no device."""
+    if lanes is None:
+        lanes = device_lanes()
+    for name, v, top in (("pixels", pixels, 2 ** 64), ("samples_sqrt", samples_sqrt, 2 ** 32), ("lanes", lanes, 2 ** 32)):
+        if not 0 <= int(v) < top:
+            raise ValueError("split_plan: %s out of range" % name)
+    count, sqrt = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().wpt_split_plan(int(pixels), int(samples_sqrt), int(lanes), C.byref(count), C.byref(sqrt)))
+    return int(count.value), int(sqrt.value)
 
 
 GUIDE_NAMES = ("camera_space_positions", "camera_space_material_normals", "materials")  # the ground truth arrays a denoiser call reads
@@ -1134,6 +1243,88 @@ class DeviceScene:
             names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
             return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
         return frames
+
+    def render_view_streams_into(self, frames, cameras, samples_sqrt, streams=None, params=None, counters=None, stream=None):
+        """render_views_into with a sample stream per view: view v is stream streams[v] of cameras[v], i.e. pixel p's generator is
+        seeded from p + streams[v] * w * h (in 64 bits) instead of p.  `streams`: V integers in [0, 2^32), or None for all 0,
+        which is render_views_into.  Stream 0 is the plain render bit for bit."""
+        import numpy as np
+        from . import host
+        V = len(cameras)
+        assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point and frames.element_size() == 4
+        assert frames.dim() == 4 and frames.shape[0] == V and frames.shape[3] == 3, "frames: [V, h, w, 3]"
+        h, w = int(frames.shape[1]), int(frames.shape[2])
+        cams = (_abi.Camera * max(V, 1))(*cameras)
+        ks = None
+        if streams is not None:
+            if len(streams) != V or any(not 0 <= int(k) < 2 ** 32 for k in streams):
+                raise ValueError("streams: one integer in [0, 2^32) per view")
+            ks = np.ascontiguousarray(np.array([int(k) for k in streams], dtype=np.uint32))
+        p = params if params is not None else host.default_params()
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
+        _check(lib().wpt_render_view_streams_device(self._handle, cams, C.c_void_p(ks.ctypes.data) if ks is not None and V else None, V,
+                                                    C.byref(p), w, h, samples_sqrt, C.c_void_p(frames.data_ptr()), cptr, sptr))
+
+    def render_view_streams(self, samples_sqrt, cameras, streams=None, params=None, with_counters=False, width=None, height=None):
+        """Synchronous convenience: returns the frames as a CUDA tensor [V, h, w, 3] (and the counters dict with_counters)."""
+        import torch
+        w = width or self.host.width
+        h = height or self.host.height
+        frames = torch.zeros((len(cameras), h, w, 3), dtype=torch.float32, device="cuda")
+        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
+        self.render_view_streams_into(frames, cameras, samples_sqrt, streams, params, counters, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        self.check()
+        if with_counters:
+            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
+            return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
+        return frames
+
+    def render_split_into(self, frame, stream_samples_sqrt, streams, first=0, moments=None, params=None, counters=None, stream=None,
+                          camera=None):
+        """wpt_render_split_device: the scene's camera (or `camera`) rendered in `streams` sample streams first .. first + streams - 1
+        of stream_samples_sqrt^2 samples each, in one launch of the batch-of-views kernels, and reduced to their mean in `frame`,
+        a CUDA float32 tensor [h, w, 3]; `moments` (optional, the same shape): the stream moment film, the mean of the stream
+        frames' squares.  Asynchronous on `stream`; the scratch (streams * h * w * 12 bytes) is allocated and freed in stream
+        order.  `counters`: optional CUDA int64 tensor [6] that the sum over all streams is added to."""
+        from . import host
+        assert frame.is_cuda and frame.is_contiguous() and frame.dtype.is_floating_point and frame.element_size() == 4
+        assert frame.dim() == 3 and frame.shape[2] == 3, "frame: [h, w, 3]"
+        h, w = int(frame.shape[0]), int(frame.shape[1])
+        if moments is not None:
+            assert moments.is_cuda and moments.is_contiguous() and moments.dtype.is_floating_point and moments.element_size() == 4
+            assert tuple(moments.shape) == tuple(frame.shape), "moments: the frame's shape"
+        if not (0 <= int(streams) < 2 ** 32 and 0 <= int(first) < 2 ** 32):
+            raise ValueError("render_split: streams and first are 32-bit counts")
+        p = params if params is not None else host.default_params()
+        cam = C.byref(camera) if camera is not None else self.host.camera
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
+        mptr = C.c_void_p(moments.data_ptr()) if moments is not None else None
+        _check(lib().wpt_render_split_device(self._handle, cam, C.byref(p), w, h, stream_samples_sqrt, int(first), int(streams),
+                                             C.c_void_p(frame.data_ptr()), mptr, cptr, sptr))
+
+    def render_split(self, stream_samples_sqrt, streams, first=0, with_moments=False, params=None, with_counters=False, width=None,
+                     height=None, camera=None):
+        """Synchronous convenience: returns the frame as numpy [h, w, 3]; with_moments (frame, moments); with_counters the counters
+        dict as a last element as well."""
+        import torch
+        w = width or self.host.width
+        h = height or self.host.height
+        frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        moments = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if with_moments else None
+        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
+        self.render_split_into(frame, stream_samples_sqrt, streams, first, moments, params, counters, torch.cuda.current_stream(), camera)
+        torch.cuda.synchronize()
+        self.check()
+        out = [frame.cpu().numpy()]
+        if with_moments:
+            out.append(moments.cpu().numpy())
+        if with_counters:
+            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
+            out.append(dict(zip(names, [int(x) for x in counters.cpu().tolist()])))
+        return out[0] if len(out) == 1 else tuple(out)
 
     def render_adaptive_into(self, frame, samples_sqrt, moments=None, block=None, params=None, stream=None):
         """Renders pixels [start, start+size) with a sample-count map on `stream` (None: torch's current stream): pixel p with
