@@ -235,7 +235,7 @@ static bool renderCase(const PinScenes::Case& c, const std::string& goldenDir, c
     return PinIO::writeNpy(fileName, shape, data.data());
 }
 
-/* test hook of libwurblpt_hip.so, not part of its public header (wpt_capi.hip) */
+/* test hook of libwurblpt_hip.so, not part of its public header (wpt_capi_selftest.hip) */
 extern "C" wpt_status wpt_selftest_hits_host(wpt_scene* scene, int n, const float* rays8_host, float* out15_host);
 
 static bool answerHitVectors(const std::string& goldenDir, const std::string& outDir)

@@ -63,7 +63,7 @@ def scene(triangles, materials, light=0, width=W, height=H):
 
 
 def need(sc):
-    """the feature bits the library finds in the scene's material records (sceneFeatures, wpt_capi.hip)"""
+    """the feature bits the library finds in the scene's material records (sceneFeatures, wpt_capi_scene.hip)"""
     bits = {_abi.MAT_TWOSIDED: TWOSIDED, _abi.MAT_GGX: GGX, _abi.MAT_GLASS: GLASS, _abi.MAT_LIGHT_SPOT: SPOT}
     types = {sc.d.materials[i].type for i in range(sc.d.material_count)}
     assert types <= set(bits) | {_abi.MAT_LAMBERTIAN, _abi.MAT_LIGHT_DIFFUSE}

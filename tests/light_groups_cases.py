@@ -75,7 +75,7 @@ def twin(name, keep, w=W, h=H):
 
 
 def need(sc, p):
-    """the feature bits the library finds in a scene and a launch (sceneFeatures and renderLaunch, wpt_capi.hip)"""
+    """the feature bits the library finds in a scene and a launch (sceneFeatures, wpt_capi_scene.hip, and renderLaunch, wpt_capi_render.hip)"""
     TEXTURES, MODPHONG, ENVMAP, LENS, TWOSIDED, GGX, GLASS, SPHERES, RGL, ANIM, SPOT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 2048
     d = sc.d
     f = 0

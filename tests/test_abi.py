@@ -45,6 +45,24 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "libwurblpt_hip.so does not export %s" % name
 
 
+# exported but not declared in the header: the test hooks, which the tests and the oracle declare for themselves
+TEST_HOOKS = {"wpt_scene_get_envmap_tables", "wpt_selftest_aabb", "wpt_selftest_hits", "wpt_selftest_hits_host", "wpt_selftest_math",
+              "wpt_selftest_rayaux", "wpt_selftest_sphere", "wpt_selftest_triangle"}
+
+
+def test_library_exports_nothing_internal():
+    """The dynamic symbol table holds the C ABI and the test hooks: no internal function with C linkage (a helper defined in an
+    unnamed namespace inside an extern "C" block is one), and nothing of the units' shared namespace wptc, which is hidden."""
+    rows = [line.split() for line in subprocess.check_output(["nm", "-D", "--defined-only", device.lib_path()]).decode().splitlines()]
+    symbols = [(r[-2], r[-1]) for r in rows if len(r) >= 2]
+    functions = sorted(name for kind, name in symbols if kind in "TtWw" and not name.startswith("_"))
+    assert "wpt_scene_upload" in functions and len(functions) > 100
+    allowed = set(declared_functions()) | TEST_HOOKS
+    assert [f for f in functions if f not in allowed] == []
+    assert TEST_HOOKS <= set(functions)
+    assert [name for _, name in symbols if "4wptc" in name] == []
+
+
 def test_no_device_is_reported_not_faked():
     """Without a GPU the library must say so; there is no CPU fallback behind the ABI."""
     import torch

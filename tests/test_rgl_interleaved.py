@@ -1,5 +1,5 @@
 """The device keeps, per measured BRDF, the colour and luminance warps' values interleaved (red, green, blue, luminance of a grid
-point in one 16-byte record: wpt_capi.hip builds the table at upload, wpt_rgl.h::rglColourInterleaved reads it) so that an evaluation's
+point in one 16-byte record: wpt_capi_scene.hip builds the table at upload, wpt_rgl.h::rglColourInterleaved reads it) so that an evaluation's
 look-ups into those two warps come from a quarter of the cache lines.  The reference's arithmetic is untouched: on the host,
 BRDF::sample / eval / pdf (powitacq_rgb.inl:1016-1183 as restated in wpt_rgl.h, whose plain path ref_probe's golden vectors pin to the
 reference) give the same bits through either table, for an isotropic and an anisotropic tensor file."""

@@ -77,7 +77,10 @@ def test_digests_and_code_objects_are_recorded_unchanged():
 
 def test_upload_has_one_statement_of_the_node_record():
     """wpt_scene_upload keeps no layout of its own: no UP macro, and the node record's word order is written in one file"""
-    capi = open(os.path.join(ROOT, "wurblpt_amd", "csrc", "wpt_capi.hip")).read()
+    csrc = os.path.join(ROOT, "wurblpt_amd", "csrc")
+    units = sorted(n for n in os.listdir(csrc) if n == "wpt_capi_common.h" or (n.startswith("wpt_capi") and n.endswith(".hip")))
+    assert "wpt_capi.hip" in units and "wpt_capi_scene.hip" in units and "wpt_capi_common.h" in units
+    capi = "".join(open(os.path.join(csrc, n)).read() for n in units)
     layout = open(os.path.join(ROOT, "wurblpt_amd", "csrc", "wpt_scene_layout.h")).read()
     assert "define UP" not in capi and "hip_runtime" not in layout
     assert "nd.lo[0], nd.hi[0], nd.lo[1], nd.lo[2]" in layout and "nd.lo[0], nd.hi[0]" not in capi

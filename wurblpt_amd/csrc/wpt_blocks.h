@@ -245,7 +245,7 @@ template<class PS> WPT_D void pathStateInit(PS& ps, uint64_t seedIndex, uint32_t
 }
 
 /* What HitableTriangle::pdfValue (hitable_triangle.hpp:405-423) derives from the corners alone: the unit face normal and
- * the face area.  Evaluated once per hot spot at upload (wpt_capi.hip) with exactly these operations; a moving light's
+ * the face area.  Evaluated once per hot spot at upload (wpt_capi_scene.hip) with exactly these operations; a moving light's
  * corners change, there they are evaluated per call. */
 WPT_D float4 hotSpotFace(f3 v0, f3 v1, f3 v2)
 {
@@ -421,7 +421,7 @@ template<class PS> WPT_D void accumulateRadiance(const wpt_params& par, f3 opl, 
  * path length lies in [edges[k], edges[k + 1]).  A lane owns its pixel for all its samples (pool and two passes included),
  * so a plain read - add - write of the pixel's values in HBM keeps the order of its contributions and needs no atomics.
  * Plane k, pixel `at`, channel c is bins[k * stride + 3 * at + c]; the launch zeroes the planes before and scales them by
- * 1 / samples after (wpt_capi.hip), as finishPixel does with the frame's accumulator.
+ * 1 / samples after (wpt_capi_sensors.hip), as finishPixel does with the frame's accumulator.
  * Light groups are the same film under a second rule for the plane (`rule` != 0): plane g takes the light whose emitter is in
  * group g.  `edges` then is the launch's table of one byte per material record, a group below binCount or BINS_GROUP_NONE, and
  * the rule's low byte the environment's group. */

@@ -1,4 +1,4 @@
-/* wpt_denoise_launch.h -- the launcher of wpt_k_denoise.hip (wpt_postproc_denoise*, wpt_capi.hip) */
+/* wpt_denoise_launch.h -- the launcher of wpt_k_denoise.hip (wpt_postproc_denoise*, wpt_capi_postproc.hip) */
 #ifndef WPT_DENOISE_LAUNCH_H
 #define WPT_DENOISE_LAUNCH_H
 

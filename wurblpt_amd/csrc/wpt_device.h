@@ -378,7 +378,7 @@ struct SceneView {
     uint32_t sphereCount;
     const wpt_animation* animations; /* key frame animations of instances and camera */
     const wpt_keyframe* keyframes;
-    /* The binary tree collapsed by one level, or NULL where the scene has no wide form (wpt_capi.hip builds it, wpt_pathtrace.inc.h
+    /* The binary tree collapsed by one level, or NULL where the scene has no wide form (wpt_capi_scene.hip builds it, wpt_pathtrace.inc.h
      * walks it).  8 quadwords per wide node: lo.x, lo.y, lo.z, hi.x, hi.y, hi.z of up to four entries (the node's grandchildren, a
      * child that is a leaf standing for itself, in the reference's order), their references (NODE_CHILD | wide node, a triangle
      * index, PRIM_SPHERE | sphere index, 0xffffffff = no entry), one spare.  Wide node 0 is the root's. */

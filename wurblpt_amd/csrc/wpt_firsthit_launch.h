@@ -1,4 +1,4 @@
-/* wpt_firsthit_launch.h -- the launcher of wpt_k_firsthit.hip (wpt_first_hit_colours*, wpt_capi.hip) */
+/* wpt_firsthit_launch.h -- the launcher of wpt_k_firsthit.hip (wpt_first_hit_colours*, wpt_capi_first_hit.hip) */
 #ifndef WPT_FIRSTHIT_LAUNCH_H
 #define WPT_FIRSTHIT_LAUNCH_H
 

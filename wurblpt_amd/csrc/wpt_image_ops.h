@@ -18,7 +18,7 @@
  * A sampling coordinate that is not finite is undefined in the reference (it asserts); here every component of that output
  * pixel is +0, on the host and on the device.
  *
- * Written once; compiled for the device (wpt_k_image_ops.hip), for the host (wpt_postproc_*_host in wpt_capi.hip) and, outside
+ * Written once; compiled for the device (wpt_k_image_ops.hip), for the host (wpt_postproc_*_host in wpt_capi_postproc.hip) and, outside
  * the library and without a header of HIP, by tests/image_ops_check.cpp.
  */
 #ifndef WPT_IMAGE_OPS_H

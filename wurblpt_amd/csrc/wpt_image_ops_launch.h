@@ -1,5 +1,5 @@
 /* wpt_image_ops_launch.h -- the launchers of wpt_k_image_ops.hip (wpt_postproc_resample, _lens_warp, _despeckle and
- * _distance_to_coords, wpt_capi.hip) */
+ * _distance_to_coords, wpt_capi_postproc.hip) */
 #ifndef WPT_IMAGE_OPS_LAUNCH_H
 #define WPT_IMAGE_OPS_LAUNCH_H
 

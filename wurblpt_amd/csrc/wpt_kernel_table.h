@@ -1,5 +1,5 @@
 /*
- * wpt_kernel_table.h -- which instantiation of wpt_pathtrace renders a launch (host only; wpt_capi.hip).
+ * wpt_kernel_table.h -- which instantiation of wpt_pathtrace renders a launch (host only; wpt_capi_render.hip).
  *
  * KERNEL_TABLE has one row per instantiation, findKernel looks a row up by its template arguments, and selectKernel is the
  * rule that names the row for a launch: a pure function of the facts it is given (no HIP call, nothing global), so that the

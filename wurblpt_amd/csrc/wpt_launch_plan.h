@@ -1,5 +1,5 @@
 /*
- * wpt_launch_plan.h -- which passes render a launch (host only; wpt_capi.hip).
+ * wpt_launch_plan.h -- which passes render a launch (host only; wpt_capi_render.hip).
  *
  * Where wpt_kernel_table.h says which kernel renders a launch, planLaunch says how it is launched: wavefront form or single
  * kernel, pixel pool or not, and one pass, two passes, one pass in the adaptive map's order, or pixels in slices.  A pure

@@ -4,7 +4,7 @@
  * every product and every sum rounded on its own (no fused multiply-add), so that the device and the host give the same bits.
  * The weights are an RGB triple per plane: a group's intensity and colour, chosen after the render.  The planes may be a
  * light-groups launch's or the transient film's.
- * Written once; compiled for the device (wpt_lightmix_kernel in wpt_capi.hip), for the host (wpt_postproc_mix_planes_host) and,
+ * Written once; compiled for the device (wpt_lightmix_kernel in wpt_capi_postproc.hip), for the host (wpt_postproc_mix_planes_host) and,
  * outside the library and without a header of HIP, by tests/lightmix_check.cpp.
  */
 #ifndef WPT_LIGHTMIX_H

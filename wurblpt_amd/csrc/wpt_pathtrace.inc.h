@@ -27,7 +27,7 @@
  *    the current subtree in depth-first order, so each device node carries that node's index
  *    ("skip") and an inner node the index of its first child: box hit & inner -> first child;
  *    leaf -> test it, then skip; otherwise -> skip.  Same visiting order, no stack, and the nodes
- *    may be STORED in any order (wpt_capi.hip lays the top of a large tree out level by level).
+ *    may be STORED in any order (wpt_scene_layout.h lays the top of a large tree out level by level).
  *
  *  - Small scenes (nodes + triangle positions up to 20 KiB, e.g. the Cornell box: 4 KiB) are
  *    copied into LDS once per workgroup and traversed from there; larger scenes are fetched
@@ -193,7 +193,7 @@ WPT_D bool lanePixel(const KernelArgs& args, uint32_t gid, uint32_t& pixel)
 enum { S_NODE = 0, S_LEAF = 1, S_SHADE = 2, S_NEEEND = 3, S_NEW = 4, S_DONE = 5, S_START = 6 /* within a long round: has a ray to start */ };
 
 /* ---- the wide walk (WIDE kernels; scenes fetched from HBM) ----
- * The binary tree collapsed by one level at upload (wpt_capi.hip, SceneView::wideNodes): a wide node holds the boxes of a
+ * The binary tree collapsed by one level at upload (wpt_capi_scene.hip, SceneView::wideNodes): a wide node holds the boxes of a
  * node's up to four grandchildren (a child that is a leaf stands for itself) in the order BVH::hit comes to them
  * (bvh.hpp:277-311), and one step tests all four from one 128-byte line.  A child whose box the ray passes through under the
  * bound of that moment waits for its turn with its entry distance -- the next one in registers, the others on a small stack --

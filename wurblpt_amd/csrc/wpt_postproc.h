@@ -2,7 +2,7 @@
  * wpt_postproc.h -- per-pixel operations of the output side: colour space conversions
  * (color.hpp:226-310) and the tone mapping / quantisation steps of postproc.hpp:44-108
  * (toSRGB, maxLuminance, uniformRationalQuantization, scaleLuminance).
- * Written once; compiled for the device (kernels in wpt_capi.hip) and by the test oracle, whose
+ * Written once; compiled for the device (kernels in wpt_capi_postproc.hip) and by the test oracle, whose
  * elementary functions are pinned to the reference's color.hpp (oracle/ref_probe.cpp).
  */
 #ifndef WPT_POSTPROC_H

@@ -1,4 +1,4 @@
-/* wpt_progress.h -- the launchers of wpt_k_progress.hip (progressive sessions, wpt_capi.hip) */
+/* wpt_progress.h -- the launchers of wpt_k_progress.hip (progressive sessions, wpt_capi_progress.hip) */
 #ifndef WPT_PROGRESS_H
 #define WPT_PROGRESS_H
 

@@ -489,7 +489,7 @@ struct RglIncident {
     ParamCtx<2> vndf, luminance, rgb;
     float d; /* 4 * sigma(u_wi) */
     /* offset of this BRDF's interleaved colour + luminance table in the pool, or WPT_RGL_NONE: the device's copy of the pool has
-     * one per BRDF whose two warps share their grids (wpt_capi.hip builds it at upload; the test oracle has none) */
+     * one per BRDF whose two warps share their grids (wpt_capi_scene.hip builds it at upload; the test oracle has none) */
     uint32_t rgbl;
 };
 template<class M>

@@ -1,5 +1,5 @@
 /*
- * wpt_scene_layout.h -- how a scene description becomes the arrays the kernels read (host only; wpt_capi.hip).
+ * wpt_scene_layout.h -- how a scene description becomes the arrays the kernels read (host only; wpt_capi_scene.hip).
  *
  * Every piece of arithmetic that decides what lies where on the device, each as a function of the description and of the two
  * option words that bear on it (the nodes in front of wpt_set_top_nodes, the WPT_WALK_* flags): validation, the triangles'

@@ -10,8 +10,8 @@
  * square.  With N = K the moment film is what the
  * variance formula of the adaptive film expects, (moment - mean^2) * N / (N - 1) / N: the variance of the pixel's mean from K
  * independent stream means, unbiased whatever the strata within a stream.
- * Written once; compiled for the device (wpt_k_streams.hip), for the host (wpt_postproc_mean_planes_host, _merge_means_host and
- * wpt_split_plan in wpt_capi.hip) and, outside the library and without a header of HIP, by tests/streams_check.cpp.
+ * Written once; compiled for the device (wpt_k_streams.hip), for the host (wpt_postproc_mean_planes_host and _merge_means_host in
+ * wpt_capi_postproc.hip, wpt_split_plan in wpt_capi.hip) and, outside the library and without a header of HIP, by tests/streams_check.cpp.
  */
 #ifndef WPT_STREAMS_H
 #define WPT_STREAMS_H

@@ -1,5 +1,5 @@
 /* wpt_streams_launch.h -- the launchers of wpt_k_streams.hip (wpt_postproc_mean_planes, _merge_means and wpt_render_split_device,
- * wpt_capi.hip) */
+ * wpt_capi_sensors.hip, wpt_capi_postproc.hip) */
 #ifndef WPT_STREAMS_LAUNCH_H
 #define WPT_STREAMS_LAUNCH_H
 

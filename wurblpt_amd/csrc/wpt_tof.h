@@ -2,7 +2,7 @@
  * wpt_tof.h -- the accumulate rule of the amplitude-modulated continuous-wave time-of-flight sensor
  * (SensorTofAmcw::accumulateRadiance, sensor_tof_amcw.hpp:227-252), restated operation for operation in float.
  * Written once; compiled for the device (FEAT_TOF kernels, wpt_blocks.h) and for the host (wpt_tof_accumulate_host in
- * wpt_capi.hip, which the tests hold against the formula).  Needs -ffp-contract=off like everything here.
+ * wpt_capi_sensors.hip, which the tests hold against the formula).  Needs -ffp-contract=off like everything here.
  *
  * A contribution of radiance.w (the near infrared channel) with the optical path length opl.w adds to a pixel's taps
  *   energy = radiance.w * 1000 * pixelArea * 0.5 * exposureTime          (left to right)
