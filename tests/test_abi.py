@@ -37,6 +37,107 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(wpt_[a-z_]+)\s*\(", text)))
 
 
+def prototypes(path, end=";"):
+    """name -> (return type, [parameter declarations]) of every `return-type wpt_name(parameters)` that `end` follows (";": a
+    prototype, "{": a definition) in a C file, its comments stripped"""
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    found = {}
+    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+(?:\s*\*)*)\s*\b(wpt_[a-z0-9_]+)\s*\(([^()]*)\)\s*" + re.escape(end), text):
+        params = " ".join(params.split())
+        found[name] = (" ".join(ret.split()).replace(" *", "*"), [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return found
+
+
+# what a scalar of the C ABI is in ctypes: (bytes, a float, signed)
+C_SCALARS = {"int": (4, False, True), "uint32_t": (4, False, False), "uint64_t": (8, False, False), "float": (4, True, False)}
+C_RESTYPES = {"wpt_status": C.c_int, "int": C.c_int, "uint32_t": C.c_uint32, "const char*": C.c_char_p, "void": None}
+
+
+def signature_faults(name, prototype, restype, argtypes, check_restype=True):
+    """what (restype, argtypes) of a signature table has that the C prototype does not: a list of messages, empty if they agree"""
+    ret, params = prototype
+    if len(argtypes) != len(params):
+        return ["%s: %d argtypes for %d parameters" % (name, len(argtypes), len(params))]
+    faults = []
+    for k, (param, cls) in enumerate(zip(params, argtypes)):
+        if "*" in param or "[" in param:  # an array parameter is a pointer
+            if not (cls in (C.c_void_p, C.c_char_p) or issubclass(cls, C._Pointer)):
+                faults.append("%s: parameter %d (%s) is a pointer, not %s" % (name, k, param, cls.__name__))
+            continue
+        ctype = " ".join(w for w in param.split()[:-1] if w != "const")  # without the parameter's name
+        if ctype not in C_SCALARS:
+            faults.append("%s: parameter %d (%s) has a type this test does not know" % (name, k, param))
+        elif not (isinstance(cls, type) and issubclass(cls, C._SimpleCData) and cls._type_ in "iIlLqQfd") or \
+                (C.sizeof(cls), cls._type_ in "fd", cls._type_ in "ilq") != C_SCALARS[ctype]:
+            faults.append("%s: parameter %d (%s) is not %s" % (name, k, param, getattr(cls, "__name__", cls)))
+    if check_restype and (ret not in C_RESTYPES or restype is not C_RESTYPES[ret]):
+        faults.append("%s: returns %s, not %s" % (name, ret, getattr(restype, "__name__", restype)))
+    return faults
+
+
+def test_signature_table_matches_the_header():
+    """_abi.FUNCTIONS, which device.lib() applies, against the prototypes of include/wurblpt_hip.h: the same names, and for every
+    function the parameter count, a pointer class for a pointer, a scalar class of the C type's size, float-ness and signedness,
+    and the return type.  The test hooks have no prototype: they are held to their definitions in the same way."""
+    declared = prototypes(HEADER)
+    assert sorted(declared) == declared_functions() and len(declared) >= 93
+    assert sorted(_abi.FUNCTIONS) == sorted(declared)
+    assert sorted(_abi.TEST_HOOK_FUNCTIONS) == sorted(TEST_HOOKS)
+    assert device.EXPORTS == list(_abi.FUNCTIONS)
+    faults = []
+    for name, (restype, argtypes) in _abi.FUNCTIONS.items():
+        faults += signature_faults(name, declared[name], restype, argtypes)
+    csrc = os.path.join(ROOT, "wurblpt_amd", "csrc")
+    defined = {**prototypes(os.path.join(csrc, "wpt_capi_selftest.hip"), "{"), **prototypes(os.path.join(csrc, "wpt_capi_scene.hip"), "{")}
+    for name, (restype, argtypes) in _abi.TEST_HOOK_FUNCTIONS.items():
+        faults += signature_faults(name, defined[name], restype, argtypes)
+    assert faults == []
+
+
+def test_signature_check_finds_a_wrong_entry():
+    """the check above is not vacuous: a lost parameter, a narrowed scalar, a scalar for a pointer and a wrong return type"""
+    proto = prototypes(HEADER)["wpt_postproc_mix_planes"]
+    restype, argtypes = _abi.FUNCTIONS["wpt_postproc_mix_planes"]
+    assert signature_faults("f", proto, restype, argtypes) == []
+    assert signature_faults("f", proto, restype, argtypes[:-1])
+    assert signature_faults("f", proto, restype, [C.c_uint32 if a is C.c_uint64 else a for a in argtypes])
+    assert signature_faults("f", proto, restype, [C.c_int if a is C.c_uint32 else a for a in argtypes])
+    assert signature_faults("f", proto, restype, [C.c_uint64] + argtypes[1:])
+    assert signature_faults("f", proto, None, argtypes)
+
+
+def test_library_functions_are_declared_at_load():
+    """after device.lib() every function of the table that the library exports carries the table's signature"""
+    lib = device.lib()
+    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.TEST_HOOK_FUNCTIONS}.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name
+
+
+def test_host_library_functions_are_declared_at_load():
+    """libwurblpt_host.so has no public header: every wpt_host_* function in its dynamic symbol table has its signature in
+    host.FUNCTIONS, which host.lib() applies, with the parameter count of its definition in wurblpt_amd/host/*.cpp"""
+    from wurblpt_amd import host
+    rows = [line.split() for line in subprocess.check_output(["nm", "-D", "--defined-only", host.lib_path()]).decode().splitlines()]
+    exported = sorted(r[-1] for r in rows if len(r) >= 2 and r[-2] in "TtWw" and r[-1].startswith("wpt_host_"))
+    assert "wpt_host_cornell" in exported and len(exported) >= 43
+    assert sorted(host.FUNCTIONS) == exported
+    lib = host.lib()
+    defined = {}
+    src = os.path.join(ROOT, "wurblpt_amd", "host")
+    for f in sorted(os.listdir(src)):
+        if f.endswith(".cpp"):
+            defined.update(prototypes(os.path.join(src, f), "{"))
+    for name, (restype, argtypes) in host.FUNCTIONS.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+        assert len(argtypes) == len(defined[name][1]), (name, defined[name][1])
+        for param, cls in zip(defined[name][1], argtypes):
+            assert ("*" in param) == (cls in (C.c_void_p, C.c_char_p) or issubclass(cls, C._Pointer)), (name, param)
+
+
 def test_library_exports_every_declared_symbol():
     fns = declared_functions()
     assert "wpt_scene_upload" in fns and "wpt_render_block_device" in fns and "wpt_render_block" in fns

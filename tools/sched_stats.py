@@ -18,7 +18,6 @@ if var:
 sc = host.sponza_like(1920, 1080) if (len(sys.argv) > 2 and sys.argv[2] == "sponza") else host.cornell(1024, 1024, 1, 2)
 ds = device.DeviceScene(sc)
 stats = torch.zeros(72, dtype=torch.int64, device="cuda")
-device.lib().wpt_set_scheduler_stats.argtypes = [C.c_void_p]
 device.lib().wpt_set_scheduler_stats(C.c_void_p(stats.data_ptr()))
 spp_sqrt = 2 if len(sys.argv) > 2 else 4
 frame, cnt = ds.render(spp_sqrt, with_counters=True)

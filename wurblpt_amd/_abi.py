@@ -156,3 +156,122 @@ STRUCT_SIZES = {
     "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
     "wpt_progress_info": (ProgressInfo, 48), "wpt_denoise_params": (DenoiseParams, 16),
 }
+
+
+# ---- the functions: name -> (restype, argtypes), applied by device.lib() when it loads the library ----
+# One entry per function the header declares; tests/test_abi.py holds every entry to the header's prototype (parameter count,
+# pointer or scalar, width, signedness, return type).  restype: _I for wpt_status and int, None for void.  A pointer the Python
+# callers hand over as a record (byref) is POINTER(record); one they hand over as an address is c_void_p.
+_I, _U, _Q, _F, _P, _S = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p, C.c_char_p
+_pU, _pQ, _pP, _pS = C.POINTER(_U), C.POINTER(_Q), C.POINTER(_P), C.POINTER(_S)
+_CAM, _PAR, _TOF, _DEN = C.POINTER(Camera), C.POINTER(Params), C.POINTER(TofSensor), C.POINTER(DenoiseParams)
+_SCP = [_P, _CAM, _PAR]  # wpt_scene* scene, const wpt_camera* camera, const wpt_params* params
+_WARP = [_P, _U, _U, _U, _CAM, _I, _P]  # wpt_postproc_lens_warp_host, wpt_postproc_distance_to_coords_host
+
+FUNCTIONS = {
+    "wpt_device_count": (_I, []),
+    "wpt_select_device": (_I, [_I]),
+    "wpt_current_device": (_I, [C.POINTER(_I)]),
+    "wpt_device_name": (_S, [_I]),
+    "wpt_device_lanes": (_I, [_I, _pU]),
+    "wpt_build_info": (_S, []),
+    "wpt_last_error": (_S, []),
+    "wpt_scene_upload": (_I, [C.POINTER(SceneDesc), _pP]),
+    "wpt_scene_free": (None, [_P]),
+    "wpt_scene_check": (_I, [_P]),
+    "wpt_scene_folded_links": (_I, [_P, _pU]),
+    "wpt_scene_bypassed_nodes": (_I, [_P, _pU]),
+    "wpt_render_block_device": (_I, _SCP + [_U] * 5 + [_P] * 3),
+    "wpt_render_block": (_I, _SCP + [_U] * 5 + [_P]),
+    "wpt_render_bands_device": (_I, [_P] * 3 + [_U] * 6 + [_P] * 3),
+    "wpt_render_bands": (_I, [_P] * 3 + [_U] * 6 + [_P]),
+    "wpt_render_transient_block_device": (_I, _SCP + [_P] + [_U] * 6 + [_P] * 3),
+    "wpt_render_transient_block": (_I, _SCP + [_P] + [_U] * 6 + [_P] * 2),
+    "wpt_render_light_groups_block_device": (_I, _SCP + [_P] + [_U] * 8 + [_P] * 3),
+    "wpt_render_light_groups_block": (_I, _SCP + [_P] + [_U] * 8 + [_P] * 2),
+    "wpt_render_tof_block_device": (_I, _SCP + [_TOF] + [_U] * 5 + [_P] * 2),
+    "wpt_render_tof_block": (_I, _SCP + [_TOF] + [_U] * 5 + [_P]),
+    "wpt_tof_accumulate_host": (_I, [_TOF, _U, _F, _F, _I, _P]),
+    "wpt_render_views_device": (_I, [_P, _CAM, _U, _PAR, _U, _U, _U] + [_P] * 3),
+    "wpt_render_views": (_I, [_P, _CAM, _U, _PAR, _U, _U, _U, _P]),
+    "wpt_render_view_streams_device": (_I, [_P, _CAM, _P, _U, _PAR, _U, _U, _U] + [_P] * 3),
+    "wpt_render_view_streams": (_I, [_P, _CAM, _P, _U, _PAR, _U, _U, _U, _P]),
+    "wpt_render_split_device": (_I, _SCP + [_U] * 5 + [_P] * 4),
+    "wpt_render_split": (_I, _SCP + [_U] * 5 + [_P] * 2),
+    "wpt_split_plan": (_I, [_Q, _U, _U, _pU, _pU]),
+    "wpt_render_adaptive_block_device": (_I, _SCP + [_U, _U, _P, _U, _U] + [_P] * 3),
+    "wpt_render_adaptive_block": (_I, _SCP + [_U, _U, _P, _U, _U] + [_P] * 2),
+    "wpt_ground_truth_device": (_I, [_P] * 6 + [_U, _U, _P, _P]),
+    "wpt_ground_truth": (_I, [_P] * 6 + [_U, _U, _P]),
+    "wpt_first_hit_colours_device": (_I, [_P] * 3 + [_U, _U] + [_P] * 4),
+    "wpt_first_hit_colours": (_I, [_P] * 3 + [_U, _U] + [_P] * 3),
+    "wpt_progress_covers": (_I, [_U, _U, _U]),
+    "wpt_progress_begin": (_I, _SCP + [_U] * 5 + [_Q, _pP]),
+    "wpt_progress_advance_device": (_I, [_P, _U, _P, _P]),
+    "wpt_progress_advance": (_I, [_P, _U, _P]),
+    "wpt_progress_rows_done": (_U, [_P]),
+    "wpt_progress_rows_total": (_U, [_P]),
+    "wpt_progress_preview_device": (_I, [_P, _P, _P]),
+    "wpt_progress_preview": (_I, [_P, _P]),
+    "wpt_progress_end": (None, [_P]),
+    "wpt_progress_state_bytes": (_I, [_P, _pQ]),
+    "wpt_progress_save": (_I, [_P, _P, _Q]),
+    "wpt_progress_restore": (_I, [_P, _P, _Q, _CAM, _PAR, _Q, _pP]),
+    "wpt_progress_state_info": (_I, [_P, _Q, C.POINTER(ProgressInfo)]),
+    "wpt_postproc_to_srgb": (_I, [_P, _P, _Q, _P]),
+    "wpt_postproc_max_luminance": (_I, [_P, _Q, _P, _P]),
+    "wpt_postproc_uniform_rational_quantization": (_I, [_P, _P, _Q, _F, _F, _P]),
+    "wpt_postproc_scale_luminance": (_I, [_P, _P, _Q, _F, _F, _P]),
+    "wpt_postproc_host": (_I, [_I, _P, _P, _Q, _F, _F]),
+    "wpt_postproc_mix_planes": (_I, [_P, _U, _Q, _Q, _P, _P, _P]),
+    "wpt_postproc_mix_planes_host": (_I, [_P, _U, _Q, _Q, _P, _P]),
+    "wpt_postproc_mean_planes": (_I, [_P, _U, _Q, _Q, _P, _P, _P]),
+    "wpt_postproc_mean_planes_host": (_I, [_P, _U, _Q, _Q, _P, _P]),
+    "wpt_postproc_merge_means": (_I, [_P, _U, _P, _U, _Q, _P, _P]),
+    "wpt_postproc_merge_means_host": (_I, [_P, _U, _P, _U, _Q, _P]),
+    "wpt_postproc_denoise": (_I, [_P] * 6 + [_U, _U, _DEN] + [_P] * 3),
+    "wpt_postproc_denoise_host": (_I, [_P] * 6 + [_U, _U, _DEN] + [_P] * 2),
+    "wpt_postproc_denoise_form": (_S, [_U]),
+    "wpt_postproc_denoise_demodulated": (_I, [_P] * 8 + [_U, _U, _DEN, _F] + [_P] * 3),
+    "wpt_postproc_denoise_demodulated_host": (_I, [_P] * 8 + [_U, _U, _DEN, _F] + [_P] * 2),
+    "wpt_postproc_resample": (_I, [_P] + [_U] * 5 + [_P, _P]),
+    "wpt_postproc_resample_host": (_I, [_P] + [_U] * 5 + [_P]),
+    "wpt_postproc_lens_warp": (_I, _WARP + [_P]),
+    "wpt_postproc_lens_warp_host": (_I, _WARP),
+    "wpt_postproc_distance_to_coords": (_I, _WARP + [_P]),
+    "wpt_postproc_distance_to_coords_host": (_I, _WARP),
+    "wpt_postproc_despeckle": (_I, [_P, _U, _U, _U, _F, _P, _P]),
+    "wpt_postproc_despeckle_host": (_I, [_P, _U, _U, _U, _F, _P]),
+    "wpt_postproc_despeckle_form": (_S, []),
+    "wpt_postproc_image_ops_tile": (None, [_pU, _pU]),
+    "wpt_set_despeckle_form": (_I, [_I]),
+    "wpt_set_launch_config": (_I, [_U, _U]),
+    "wpt_set_wavefront": (_I, [_U] * 4),
+    "wpt_set_walk": (_I, [_U]),
+    "wpt_set_top_nodes": (_I, [_U]),
+    "wpt_set_slices": (_I, [_U]),
+    "wpt_set_bypass": (_I, [_U]),
+    "wpt_set_scheduler_stats": (_I, [_P]),
+    "wpt_slices_plan": (_I, [_U, _U, _U, _pU, _pU]),
+    "wpt_last_slice_stats": (_I, [_pQ, _pQ]),
+    "wpt_fold_plan": (_I, [_P, _pU, _P]),
+    "wpt_bypass_plan": (_I, [_P, _pU, _P]),
+    "wpt_kernel_name": (_S, []),
+    "wpt_kernel_form": (_S, []),
+    "wpt_kernel_choice": (_I, [_U] * 9 + [_pS, _pS, _pU, _pQ, _pU]),
+    "wpt_kernel_table_entry": (_I, [_U, _pU, _pS]),
+    "wpt_launch_plan": (_I, [_U] * 10 + [_pU]),
+    "wpt_last_render_passes": (_U, []),
+}
+
+# exported but not declared in the header: the test hooks (wpt_capi_selftest.hip, wpt_capi_scene.hip)
+TEST_HOOK_FUNCTIONS = {
+    "wpt_selftest_math": (_I, [_I, _I, _P, _P, _P]),
+    "wpt_selftest_aabb": (_I, [_I, _P, _P, _P]),
+    "wpt_selftest_triangle": (_I, [_I, _I, _P, _P]),
+    "wpt_selftest_rayaux": (_I, [_I, _P, _P]),
+    "wpt_selftest_sphere": (_I, [_I, _P, _P, _P]),
+    "wpt_selftest_hits": (_I, [_P, _I, _P, _P]),
+    "wpt_selftest_hits_host": (_I, [_P, _I, _P, _P]),
+    "wpt_scene_get_envmap_tables": (_I, [_P] * 4),
+}

@@ -19,26 +19,7 @@ def lib_path():
 WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD, WALK_NO_BYPASS = 1, 2, 4, 8, 16, 32, 64  # wpt_set_walk (include/wurblpt_hip.h)
 SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
-EXPORTS = ["wpt_device_count", "wpt_select_device", "wpt_current_device", "wpt_scene_upload", "wpt_scene_free", "wpt_scene_check",
-           "wpt_postproc_to_srgb", "wpt_postproc_max_luminance", "wpt_postproc_uniform_rational_quantization",
-           "wpt_postproc_scale_luminance", "wpt_postproc_host", "wpt_ground_truth_device", "wpt_ground_truth", "wpt_render_bands_device", "wpt_render_bands",
-           "wpt_render_block_device", "wpt_render_block",
-           "wpt_render_transient_block_device", "wpt_render_transient_block", "wpt_render_views_device", "wpt_render_views",
-           "wpt_render_view_streams_device", "wpt_render_view_streams", "wpt_render_split_device", "wpt_render_split",
-           "wpt_postproc_mean_planes", "wpt_postproc_mean_planes_host", "wpt_postproc_merge_means", "wpt_postproc_merge_means_host",
-           "wpt_split_plan", "wpt_device_lanes",
-           "wpt_render_light_groups_block_device", "wpt_render_light_groups_block", "wpt_postproc_mix_planes", "wpt_postproc_mix_planes_host",
-           "wpt_render_adaptive_block_device", "wpt_render_adaptive_block",
-           "wpt_postproc_denoise", "wpt_postproc_denoise_host", "wpt_postproc_denoise_form",
-           "wpt_first_hit_colours_device", "wpt_first_hit_colours", "wpt_postproc_denoise_demodulated", "wpt_postproc_denoise_demodulated_host",
-           "wpt_postproc_resample", "wpt_postproc_resample_host", "wpt_postproc_lens_warp", "wpt_postproc_lens_warp_host",
-           "wpt_postproc_despeckle", "wpt_postproc_despeckle_host", "wpt_postproc_distance_to_coords", "wpt_postproc_distance_to_coords_host",
-           "wpt_postproc_despeckle_form", "wpt_set_despeckle_form", "wpt_postproc_image_ops_tile",
-           "wpt_render_tof_block_device", "wpt_render_tof_block", "wpt_tof_accumulate_host", "wpt_set_launch_config", "wpt_set_top_nodes", "wpt_set_walk", "wpt_set_slices", "wpt_slices_plan", "wpt_last_slice_stats", "wpt_scene_folded_links", "wpt_fold_plan", "wpt_scene_bypassed_nodes", "wpt_bypass_plan", "wpt_set_bypass", "wpt_set_wavefront", "wpt_kernel_name", "wpt_kernel_form", "wpt_kernel_choice", "wpt_kernel_table_entry", "wpt_launch_plan", "wpt_device_name", "wpt_build_info", "wpt_last_render_passes",
-           "wpt_progress_covers", "wpt_progress_begin", "wpt_progress_advance_device", "wpt_progress_advance", "wpt_progress_rows_done",
-           "wpt_progress_rows_total", "wpt_progress_preview_device", "wpt_progress_preview", "wpt_progress_end", "wpt_progress_state_bytes",
-           "wpt_progress_save", "wpt_progress_restore", "wpt_progress_state_info",
-           "wpt_last_error"]
+EXPORTS = list(_abi.FUNCTIONS)  # every function include/wurblpt_hip.h declares (the test hooks are not among them)
 
 
 def lib():
@@ -55,115 +36,12 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(path)
-        L.wpt_device_count.restype = C.c_int
-        L.wpt_device_name.restype = C.c_char_p
-        L.wpt_device_name.argtypes = [C.c_int]
-        L.wpt_build_info.restype = C.c_char_p
-        L.wpt_last_render_passes.restype = C.c_uint32
-        L.wpt_select_device.argtypes = [C.c_int]
-        L.wpt_scene_upload.argtypes = [C.POINTER(_abi.SceneDesc), C.POINTER(C.c_void_p)]
-        L.wpt_scene_free.argtypes = [C.c_void_p]
-        L.wpt_scene_check.argtypes = [C.c_void_p]
-        L.wpt_render_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params),
-                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-        L.wpt_render_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params),
-                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-        L.wpt_render_transient_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
-                                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        L.wpt_render_transient_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p, C.c_uint32,
-                                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        if hasattr(L, "wpt_render_light_groups_block"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_render_light_groups_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p,
-                                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_render_light_groups_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_void_p,
-                                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                        C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_mix_planes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_mix_planes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-        if hasattr(L, "wpt_postproc_denoise"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_postproc_denoise.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_void_p, C.c_void_p,
-                                                                  C.c_void_p]
-            L.wpt_postproc_denoise_host.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_void_p,
-                                                                       C.c_void_p]
-            L.wpt_postproc_denoise_form.argtypes = [C.c_uint32]
-            L.wpt_postproc_denoise_form.restype = C.c_char_p
-        if hasattr(L, "wpt_first_hit_colours"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_first_hit_colours_device.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
-            L.wpt_first_hit_colours.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
-            L.wpt_postproc_denoise_demodulated.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams), C.c_float,
-                                                                              C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_denoise_demodulated_host.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.POINTER(_abi.DenoiseParams),
-                                                                                   C.c_float, C.c_void_p, C.c_void_p]
-        if hasattr(L, "wpt_postproc_resample"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_postproc_resample.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
-            L.wpt_postproc_resample_host.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p]
-            L.wpt_postproc_lens_warp.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(_abi.Camera), C.c_int, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_lens_warp_host.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(_abi.Camera), C.c_int, C.c_void_p]
-            L.wpt_postproc_despeckle.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_float, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_despeckle_host.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_float, C.c_void_p]
-            L.wpt_postproc_distance_to_coords.argtypes = L.wpt_postproc_lens_warp.argtypes
-            L.wpt_postproc_distance_to_coords_host.argtypes = L.wpt_postproc_lens_warp_host.argtypes
-            L.wpt_postproc_despeckle_form.restype = C.c_char_p
-            L.wpt_set_despeckle_form.argtypes = [C.c_int]
-            L.wpt_postproc_image_ops_tile.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-            L.wpt_postproc_image_ops_tile.restype = None
-        L.wpt_render_views_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
-                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.wpt_render_views.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_uint32, C.POINTER(_abi.Params),
-                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-        if hasattr(L, "wpt_render_split"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_render_view_streams_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_void_p, C.c_uint32, C.POINTER(_abi.Params),
-                                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_render_view_streams.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.c_void_p, C.c_uint32, C.POINTER(_abi.Params),
-                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-            L.wpt_render_split_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params)] + [C.c_uint32] * 5 + [C.c_void_p] * 4
-            L.wpt_render_split.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params)] + [C.c_uint32] * 5 + [C.c_void_p] * 2
-            L.wpt_postproc_mean_planes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_mean_planes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
-            L.wpt_postproc_merge_means_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
-            L.wpt_split_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-            L.wpt_device_lanes.argtypes = [C.c_int, C.POINTER(C.c_uint32)]
-        L.wpt_render_adaptive_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
-                                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.wpt_render_adaptive_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32,
-                                                C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.wpt_render_tof_block_device.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.POINTER(_abi.TofSensor),
-                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.wpt_render_tof_block.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.POINTER(_abi.TofSensor),
-                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-        L.wpt_tof_accumulate_host.argtypes = [C.POINTER(_abi.TofSensor), C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_void_p]
-        if hasattr(L, "wpt_progress_begin"):  # (WPT_LIB_DIR may name an older build, which measurements compare with)
-            L.wpt_progress_covers.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
-            L.wpt_progress_begin.argtypes = [C.c_void_p, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint32, C.c_uint32, C.c_uint32,
-                                             C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
-            L.wpt_progress_advance_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.wpt_progress_advance.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-            L.wpt_progress_rows_done.argtypes = [C.c_void_p]
-            L.wpt_progress_rows_done.restype = C.c_uint32
-            L.wpt_progress_rows_total.argtypes = [C.c_void_p]
-            L.wpt_progress_rows_total.restype = C.c_uint32
-            L.wpt_progress_preview_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-            L.wpt_progress_preview.argtypes = [C.c_void_p, C.c_void_p]
-            L.wpt_progress_end.argtypes = [C.c_void_p]
-            L.wpt_progress_end.restype = None
-            L.wpt_progress_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-            L.wpt_progress_save.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-            L.wpt_progress_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(_abi.Camera), C.POINTER(_abi.Params), C.c_uint64,
-                                               C.POINTER(C.c_void_p)]
-            L.wpt_progress_state_info.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(_abi.ProgressInfo)]
-        L.wpt_set_launch_config.argtypes = [C.c_uint32, C.c_uint32]
-        L.wpt_set_wavefront.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
-        L.wpt_set_walk.argtypes = [C.c_uint32]
-        L.wpt_set_top_nodes.argtypes = [C.c_uint32]
-        L.wpt_kernel_name.restype = C.c_char_p
-        L.wpt_kernel_form.restype = C.c_char_p
-        L.wpt_last_error.restype = C.c_char_p
-        L.wpt_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.wpt_scene_get_envmap_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # the signatures of _abi.py, one loop for all; a name the library lacks is skipped (WPT_LIB_DIR may name an older build,
+        # which measurements compare with)
+        for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.TEST_HOOK_FUNCTIONS}.items():
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 
@@ -171,6 +49,43 @@ def lib():
 def _check(status):
     if status != _abi.WPT_OK:
         raise RuntimeError("wurblpt_hip: %s (status %d)" % (lib().wpt_last_error().decode(), status))
+
+
+# ---- the wrappers' common steps ----
+
+def _frame_size(host_scene, width, height):
+    """(w, h) of a launch: the given size, or the host scene's"""
+    return width or host_scene.width, height or host_scene.height
+
+
+def _params(params):
+    """the parameters of a launch: the given ones, or the defaults"""
+    from . import host
+    return params if params is not None else host.default_params()
+
+
+def _stream_ptr(stream):
+    return C.c_void_p(stream.cuda_stream) if stream is not None else None
+
+
+def _tensor_ptr(tensor):
+    return C.c_void_p(tensor.data_ptr()) if tensor is not None else None
+
+
+def _array_ptr(array):
+    return C.c_void_p(array.ctypes.data) if array is not None else None
+
+
+COUNTER_NAMES = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")  # wpt_counters
+
+
+def _new_counters(wanted):
+    import torch
+    return torch.zeros(len(COUNTER_NAMES), dtype=torch.int64, device="cuda") if wanted else None
+
+
+def _counters_dict(counters):
+    return dict(zip(COUNTER_NAMES, [int(x) for x in counters.cpu().tolist()]))
 
 
 def uniform_edges(start, width, count):
@@ -267,8 +182,7 @@ def mean_planes(planes, with_moment=False, mean_out=None, moment_out=None, strea
         assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == pixels * 3)
     s = stream if stream is not None else torch.cuda.current_stream()
     _check(lib().wpt_postproc_mean_planes(C.c_void_p(planes.data_ptr()), K, pixels * 3, pixels, C.c_void_p(mean_out.data_ptr()),
-                                          C.c_void_p(moment_out.data_ptr()) if moment_out is not None else None,
-                                          C.c_void_p(s.cuda_stream)))
+                                          _tensor_ptr(moment_out), C.c_void_p(s.cuda_stream)))
     return (mean_out, moment_out) if moment_out is not None else mean_out
 
 
@@ -282,7 +196,7 @@ def mean_planes_host(planes, with_moment=False):
     moment = np.zeros(p.shape[1:], np.float32) if with_moment else None
     pixels = mean.size // 3
     _check(lib().wpt_postproc_mean_planes_host(C.c_void_p(p.ctypes.data), K, pixels * 3, pixels, C.c_void_p(mean.ctypes.data),
-                                               C.c_void_p(moment.ctypes.data) if with_moment else None))
+                                               _array_ptr(moment)))
     return (mean, moment) if with_moment else mean
 
 
@@ -357,84 +271,15 @@ def denoise_form(step):
     return lib().wpt_postproc_denoise_form(int(step)).decode()
 
 
-def denoise(frame, moments, samples_sqrt, guide, params=None, variance_out=False, stream=None):
-    """wpt_postproc_denoise: the edge-avoiding a-trous filter with variance guidance (include/wurblpt_hip.h has the formula) on
-    CUDA tensors.  `frame`, `moments`: float32 [h, w, 3] (an adaptive render's frame and moment film); `samples_sqrt`: the map the
-    frame was rendered with (any integer tensor or array [h, w]) or one integer for all pixels; `guide`: the dict of
-    DeviceScene.ground_truth_device (GUIDE_NAMES) or the tuple (positions, normals, materials); `params`: _abi.DenoiseParams
-    (None: the defaults).  Asynchronous on `stream` (None: torch's current stream), ordered behind the work on the current
-    stream.  Returns the filtered frame, and with variance_out the variance of its luminance [h, w] as well."""
+def _denoise_args(frame, moments, samples_sqrt, guide, colours, params, variance_out, stream):
+    """What denoise (colours = ()) and denoise_demodulated (colours = (albedo, emission)) hand to the library: the checked input
+    tensors in the order of the C parameters (the map as 16-bit words among them), w, h, the parameters, the new output tensors
+    and the launch stream, ordered behind the work on torch's current stream."""
     import numpy as np
     import torch
     h, w = int(frame.shape[0]), int(frame.shape[1])
     P, n, m = _denoise_guide(guide)
-    for t, comps, what in ((frame, 3, "frame"), (moments, 3, "moments"), (P, 3, "positions"), (n, 3, "normals")):
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, comps), "denoise: %s must be CUDA float32 [h, w, %d]" % (what, comps)
-    assert m.is_cuda and m.is_contiguous() and m.dtype == torch.int32 and m.numel() == w * h, "denoise: materials must be CUDA int32 [h, w]"
-    if isinstance(samples_sqrt, (int, np.integer)):
-        if not 0 <= int(samples_sqrt) <= 65535:
-            raise ValueError("the sample count's square root must lie in [0, 65535]")
-        samples_sqrt = np.full((h, w), int(samples_sqrt), np.uint16)
-    elif not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
-        _map_int(samples_sqrt)
-    assert tuple(samples_sqrt.shape) == (h, w), "samples_sqrt: [h, w]"
-    current = torch.cuda.current_stream()
-    launch = stream if stream is not None else current
-    m16 = _map_u16_device(samples_sqrt)
-    out = torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
-    variance = torch.empty((h, w), dtype=torch.float32, device=frame.device) if variance_out else None
-    if launch != current:
-        launch.wait_stream(current)
-        for t in (m16, out, variance):
-            if t is not None:
-                t.record_stream(launch)
-    p = params if params is not None else _abi.DenoiseParams()
-    _check(lib().wpt_postproc_denoise(C.c_void_p(frame.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(m16.data_ptr()),
-                                      C.c_void_p(P.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(m.data_ptr()), w, h, C.byref(p),
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(variance.data_ptr()) if variance_out else None,
-                                      C.c_void_p(launch.cuda_stream)))
-    return (out, variance) if variance_out else out
-
-
-def denoise_host(frame, moments, samples_sqrt, guide, params=None, variance_out=False):
-    """wpt_postproc_denoise_host: the same filter of numpy arrays on the CPU, bit for bit; needs no device"""
-    import numpy as np
-    f = np.ascontiguousarray(frame, dtype=np.float32)
-    assert f.ndim == 3 and f.shape[2] == 3, "denoise: the frame must be [h, w, 3]"
-    h, w = f.shape[:2]
-    P, n, m = _denoise_guide(guide)
-    mo = np.ascontiguousarray(moments, dtype=np.float32)
-    P = np.ascontiguousarray(P, dtype=np.float32)
-    n = np.ascontiguousarray(n, dtype=np.float32)
-    m = np.ascontiguousarray(m, dtype=np.int32)
-    assert mo.shape == f.shape and P.shape == f.shape and n.shape == f.shape and m.size == w * h, "denoise: arrays of the frame's size"
-    if isinstance(samples_sqrt, (int, np.integer)):
-        samples_sqrt = np.full((h, w), int(samples_sqrt), np.int64)
-    a = _map_int(samples_sqrt)
-    assert a.shape == (h, w), "samples_sqrt: [h, w]"
-    m16 = np.ascontiguousarray(a.astype(np.uint16))
-    out = np.zeros((h, w, 3), np.float32)
-    variance = np.zeros((h, w), np.float32) if variance_out else None
-    p = params if params is not None else _abi.DenoiseParams()
-    _check(lib().wpt_postproc_denoise_host(C.c_void_p(f.ctypes.data), C.c_void_p(mo.ctypes.data), C.c_void_p(m16.ctypes.data),
-                                           C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data), w, h, C.byref(p),
-                                           C.c_void_p(out.ctypes.data), C.c_void_p(variance.ctypes.data) if variance_out else None))
-    return (out, variance) if variance_out else out
-
-
-def denoise_demodulated(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0, variance_out=False,
-                        stream=None):
-    """wpt_postproc_denoise_demodulated: denoise() on (frame - emission) / albedo, the surface's own colours put back afterwards
-    (include/wurblpt_hip.h has the rule).  `albedo`, `emission`: CUDA float32 [h, w, 3]; None: the entries "albedo" and
-    "emission" of `guide`, the dict of DeviceScene.first_hit_colours_device.  `albedo_floor` <= 0: the default 1 / 64.  With
-    variance_out the variance of the DEMODULATED luminance [h, w] is returned as well.  Everything else as for denoise()."""
-    import numpy as np
-    import torch
-    h, w = int(frame.shape[0]), int(frame.shape[1])
-    P, n, m = _denoise_guide(guide)
-    albedo = guide["albedo"] if albedo is None else albedo
-    emission = guide["emission"] if emission is None else emission
-    for t, what in ((frame, "frame"), (moments, "moments"), (P, "positions"), (n, "normals"), (albedo, "albedo"), (emission, "emission")):
+    for t, what in ((frame, "frame"), (moments, "moments"), (P, "positions"), (n, "normals")) + tuple(zip(colours, ("albedo", "emission"))):
         assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 3), "denoise: %s must be CUDA float32 [h, w, 3]" % what
     assert m.is_cuda and m.is_contiguous() and m.dtype == torch.int32 and m.numel() == w * h, "denoise: materials must be CUDA int32 [h, w]"
     if isinstance(samples_sqrt, (int, np.integer)):
@@ -454,28 +299,19 @@ def denoise_demodulated(frame, moments, samples_sqrt, guide, albedo=None, emissi
         for t in (m16, out, variance):
             if t is not None:
                 t.record_stream(launch)
-    p = params if params is not None else _abi.DenoiseParams()
-    _check(lib().wpt_postproc_denoise_demodulated(C.c_void_p(frame.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(m16.data_ptr()),
-                                                  C.c_void_p(P.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(m.data_ptr()),
-                                                  C.c_void_p(albedo.data_ptr()), C.c_void_p(emission.data_ptr()), w, h, C.byref(p),
-                                                  float(albedo_floor), C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(variance.data_ptr()) if variance_out else None, C.c_void_p(launch.cuda_stream)))
-    return (out, variance) if variance_out else out
+    return (frame, moments, m16, P, n, m) + tuple(colours), w, h, params if params is not None else _abi.DenoiseParams(), out, variance, launch
 
 
-def denoise_demodulated_host(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0,
-                             variance_out=False):
-    """wpt_postproc_denoise_demodulated_host: the same of numpy arrays on the CPU, bit for bit; needs no device"""
+def _denoise_host_args(frame, moments, samples_sqrt, guide, colours, params, variance_out):
+    """_denoise_args for the host forms: float32 / int32 numpy copies, the map as uint16, zeroed outputs"""
     import numpy as np
     f = np.ascontiguousarray(frame, dtype=np.float32)
     assert f.ndim == 3 and f.shape[2] == 3, "denoise: the frame must be [h, w, 3]"
     h, w = f.shape[:2]
     P, n, m = _denoise_guide(guide)
-    albedo = guide["albedo"] if albedo is None else albedo
-    emission = guide["emission"] if emission is None else emission
-    mo, P, n, al, em = (np.ascontiguousarray(a, dtype=np.float32) for a in (moments, P, n, albedo, emission))
+    mo, P, n, *colours = (np.ascontiguousarray(a, dtype=np.float32) for a in (moments, P, n) + tuple(colours))
     m = np.ascontiguousarray(m, dtype=np.int32)
-    assert all(a.shape == f.shape for a in (mo, P, n, al, em)) and m.size == w * h, "denoise: arrays of the frame's size"
+    assert all(a.shape == f.shape for a in [mo, P, n] + colours) and m.size == w * h, "denoise: arrays of the frame's size"
     if isinstance(samples_sqrt, (int, np.integer)):
         samples_sqrt = np.full((h, w), int(samples_sqrt), np.int64)
     a = _map_int(samples_sqrt)
@@ -483,12 +319,49 @@ def denoise_demodulated_host(frame, moments, samples_sqrt, guide, albedo=None, e
     m16 = np.ascontiguousarray(a.astype(np.uint16))
     out = np.zeros((h, w, 3), np.float32)
     variance = np.zeros((h, w), np.float32) if variance_out else None
-    p = params if params is not None else _abi.DenoiseParams()
-    _check(lib().wpt_postproc_denoise_demodulated_host(C.c_void_p(f.ctypes.data), C.c_void_p(mo.ctypes.data), C.c_void_p(m16.ctypes.data),
-                                                       C.c_void_p(P.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(m.ctypes.data),
-                                                       C.c_void_p(al.ctypes.data), C.c_void_p(em.ctypes.data), w, h, C.byref(p),
-                                                       float(albedo_floor), C.c_void_p(out.ctypes.data),
-                                                       C.c_void_p(variance.ctypes.data) if variance_out else None))
+    return [f, mo, m16, P, n, m] + colours, w, h, params if params is not None else _abi.DenoiseParams(), out, variance
+
+
+def denoise(frame, moments, samples_sqrt, guide, params=None, variance_out=False, stream=None):
+    """wpt_postproc_denoise: the edge-avoiding a-trous filter with variance guidance (include/wurblpt_hip.h has the formula) on
+    CUDA tensors.  `frame`, `moments`: float32 [h, w, 3] (an adaptive render's frame and moment film); `samples_sqrt`: the map the
+    frame was rendered with (any integer tensor or array [h, w]) or one integer for all pixels; `guide`: the dict of
+    DeviceScene.ground_truth_device (GUIDE_NAMES) or the tuple (positions, normals, materials); `params`: _abi.DenoiseParams
+    (None: the defaults).  Asynchronous on `stream` (None: torch's current stream), ordered behind the work on the current
+    stream.  Returns the filtered frame, and with variance_out the variance of its luminance [h, w] as well."""
+    inputs, w, h, p, out, variance, launch = _denoise_args(frame, moments, samples_sqrt, guide, (), params, variance_out, stream)
+    _check(lib().wpt_postproc_denoise(*[_tensor_ptr(t) for t in inputs], w, h, C.byref(p), _tensor_ptr(out), _tensor_ptr(variance),
+                                      _stream_ptr(launch)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_host(frame, moments, samples_sqrt, guide, params=None, variance_out=False):
+    """wpt_postproc_denoise_host: the same filter of numpy arrays on the CPU, bit for bit; needs no device"""
+    inputs, w, h, p, out, variance = _denoise_host_args(frame, moments, samples_sqrt, guide, (), params, variance_out)
+    _check(lib().wpt_postproc_denoise_host(*[_array_ptr(a) for a in inputs], w, h, C.byref(p), _array_ptr(out), _array_ptr(variance)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_demodulated(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0, variance_out=False,
+                        stream=None):
+    """wpt_postproc_denoise_demodulated: denoise() on (frame - emission) / albedo, the surface's own colours put back afterwards
+    (include/wurblpt_hip.h has the rule).  `albedo`, `emission`: CUDA float32 [h, w, 3]; None: the entries "albedo" and
+    "emission" of `guide`, the dict of DeviceScene.first_hit_colours_device.  `albedo_floor` <= 0: the default 1 / 64.  With
+    variance_out the variance of the DEMODULATED luminance [h, w] is returned as well.  Everything else as for denoise()."""
+    colours = (guide["albedo"] if albedo is None else albedo, guide["emission"] if emission is None else emission)
+    inputs, w, h, p, out, variance, launch = _denoise_args(frame, moments, samples_sqrt, guide, colours, params, variance_out, stream)
+    _check(lib().wpt_postproc_denoise_demodulated(*[_tensor_ptr(t) for t in inputs], w, h, C.byref(p), float(albedo_floor), _tensor_ptr(out),
+                                                  _tensor_ptr(variance), _stream_ptr(launch)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_demodulated_host(frame, moments, samples_sqrt, guide, albedo=None, emission=None, params=None, albedo_floor=0.0,
+                             variance_out=False):
+    """wpt_postproc_denoise_demodulated_host: the same of numpy arrays on the CPU, bit for bit; needs no device"""
+    colours = (guide["albedo"] if albedo is None else albedo, guide["emission"] if emission is None else emission)
+    inputs, w, h, p, out, variance = _denoise_host_args(frame, moments, samples_sqrt, guide, colours, params, variance_out)
+    _check(lib().wpt_postproc_denoise_demodulated_host(*[_array_ptr(a) for a in inputs], w, h, C.byref(p), float(albedo_floor),
+                                                       _array_ptr(out), _array_ptr(variance)))
     return (out, variance) if variance_out else out
 
 
@@ -716,10 +589,8 @@ def tof_result(phase_differences, modulation_frequency):
     re, im = d0 - d2, d3 - d1
     zero = (np.abs(d0 - d2) <= 0) & (np.abs(d1 - d3) <= 0)
     # the C library's atan2f, which the reference's std::atan2 is (numpy's own float32 arctan2 differs from it in the last bit)
-    libm = C.CDLL("libm.so.6")
-    libm.atan2f.restype = C.c_float
-    libm.atan2f.argtypes = [C.c_float, C.c_float]
-    shift = np.frompyfunc(libm.atan2f, 2, 1)(im, re).astype(np.float32)
+    atan2f = C.CFUNCTYPE(C.c_float, C.c_float, C.c_float)(("atan2f", C.CDLL("libm.so.6")))
+    shift = np.frompyfunc(atan2f, 2, 1)(im, re).astype(np.float32)
     # `phaseShift += 2.0 * pi` with the float pi: a double addition rounded to float
     shift = np.where(shift < 0, (shift.astype(np.float64) + 2.0 * float(np.float32(np.pi))).astype(np.float32), shift)
     frac_c_modfreq = np.float32(host.SPEED_OF_LIGHT / float(modulation_frequency))
@@ -737,17 +608,13 @@ def device_count():
 
 def set_slices(n):
     """wpt_set_slices: 0 = the library's plan, 1 = never, 2 .. 15 = that many units per pixel (| SLICES_DECLINE_ODD: tests)"""
-    L = lib()
-    L.wpt_set_slices.argtypes = [C.c_uint32]
-    _check(L.wpt_set_slices(n))
+    _check(lib().wpt_set_slices(n))
 
 
 def slices_plan(block_size, lanes_at_once, samples_sqrt):
     """wpt_slices_plan: (units, rows) the library cuts the pixels of such a launch into; needs no device"""
-    L = lib()
-    L.wpt_slices_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     units, rows = C.c_uint32(), C.c_uint32()
-    _check(L.wpt_slices_plan(block_size, lanes_at_once, samples_sqrt, C.byref(units), C.byref(rows)))
+    _check(lib().wpt_slices_plan(block_size, lanes_at_once, samples_sqrt, C.byref(units), C.byref(rows)))
     return int(units.value), int(rows.value)
 
 
@@ -757,21 +624,17 @@ SENSOR_FRAME, SENSOR_TRANSIENT, SENSOR_VIEWS, SENSOR_ADAPTIVE, SENSOR_TOF = rang
 def kernel_choice(need, sensor, count, node_count, tri_count, material_count, scene_has_wide=False, variant=0, walk=0):
     """wpt_kernel_choice: (name, form, (F, count, ldsScene, wide), sceneLdsBytes, materialsInLds) of the kernel the library would
     launch; needs no device"""
-    L = lib()
-    L.wpt_kernel_choice.argtypes = [C.c_uint32] * 9 + [C.POINTER(C.c_char_p)] * 2 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     name, form, key, lds_bytes, materials = C.c_char_p(), C.c_char_p(), (C.c_uint32 * 4)(), C.c_uint64(), C.c_uint32()
-    _check(L.wpt_kernel_choice(need, sensor, int(count), node_count, tri_count, material_count, int(scene_has_wide), variant, walk,
-                               C.byref(name), C.byref(form), key, C.byref(lds_bytes), C.byref(materials)))
+    _check(lib().wpt_kernel_choice(need, sensor, int(count), node_count, tri_count, material_count, int(scene_has_wide), variant, walk,
+                                   C.byref(name), C.byref(form), key, C.byref(lds_bytes), C.byref(materials)))
     return name.value.decode(), form.value.decode(), (key[0], bool(key[1]), bool(key[2]), bool(key[3])), int(lds_bytes.value), int(materials.value)
 
 
 def kernel_table():
     """wpt_kernel_table_entry: [((F, count, ldsScene, wide), name)] of every kernel the library has"""
-    L = lib()
-    L.wpt_kernel_table_entry.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
     rows = []
     key, name = (C.c_uint32 * 4)(), C.c_char_p()
-    while L.wpt_kernel_table_entry(len(rows), key, C.byref(name)) == _abi.WPT_OK:
+    while lib().wpt_kernel_table_entry(len(rows), key, C.byref(name)) == _abi.WPT_OK:
         rows.append(((key[0], bool(key[1]), bool(key[2]), bool(key[3])), name.value.decode()))
     return rows
 
@@ -784,8 +647,8 @@ def launch_plan(sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_
     """wpt_launch_plan: which passes render such a launch, as a dict: wavefront, wavefront_falls_back, pooled (bools), strategy (one of
     STRATEGIES), units, rows, passes; needs no device"""
     w = (C.c_uint32 * len(PLAN_WORDS))()
-    _check(lib().wpt_launch_plan(*[C.c_uint32(int(v)) for v in (sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_count, variant,
-                                                                wavefront_mode, slices)], w))
+    _check(lib().wpt_launch_plan(*[int(v) for v in (sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_count, variant, wavefront_mode,
+                                                    slices)], w))
     plan = dict(zip(PLAN_WORDS, (int(v) for v in w)))
     for k in ("wavefront", "wavefront_falls_back", "pooled"):
         plan[k] = bool(plan[k])
@@ -795,10 +658,8 @@ def launch_plan(sensor, count, need, scene_in_lds, block_size, samples_sqrt, cu_
 
 def last_slice_stats():
     """wpt_last_slice_stats: (taken, continued) of the most recent render call; waits for the device"""
-    L = lib()
-    L.wpt_last_slice_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     taken, continued = C.c_uint64(), C.c_uint64()
-    _check(L.wpt_last_slice_stats(C.byref(taken), C.byref(continued)))
+    _check(lib().wpt_last_slice_stats(C.byref(taken), C.byref(continued)))
     return int(taken.value), int(continued.value)
 
 
@@ -806,11 +667,9 @@ def fold_plan(host_scene, with_words=False):
     """wpt_fold_plan: the nodes whose link the kernels with the scene in LDS fold in their copy of the scene's tree; with
     with_words (count, word 7 of every node's LDS copy as numpy uint32).  Needs no device"""
     import numpy as np
-    L = lib()
-    L.wpt_fold_plan.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     folded = C.c_uint32()
     words = np.zeros(int(host_scene.d.node_count), np.uint32)
-    _check(L.wpt_fold_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(folded), C.c_void_p(words.ctypes.data) if with_words else None))
+    _check(lib().wpt_fold_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(folded), _array_ptr(words if with_words else None)))
     return (int(folded.value), words) if with_words else int(folded.value)
 
 
@@ -820,21 +679,17 @@ BYPASS_MODEL, BYPASS_ALL_ELIGIBLE = 0, 1  # wpt_set_bypass
 def set_bypass(mode):
     """wpt_set_bypass (tests): which eligible inner nodes the walk of a scene in LDS leaves out -- BYPASS_MODEL: the cost model's
     choice, BYPASS_ALL_ELIGIBLE: all of them; read when a scene is uploaded and by bypass_plan"""
-    L = lib()
-    L.wpt_set_bypass.argtypes = [C.c_uint32]
-    _check(L.wpt_set_bypass(mode))
+    _check(lib().wpt_set_bypass(mode))
 
 
 def bypass_plan(host_scene, with_words=False):
     """wpt_bypass_plan: the inner nodes that the walk of the scene's tree in LDS leaves out; with with_words (count, links, start):
     links[i] = (skip link, word 7) of node i's LDS copy as numpy uint32, start = the node a ray starts at.  Needs no device"""
     import numpy as np
-    L = lib()
-    L.wpt_bypass_plan.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     count = C.c_uint32()
     n = int(host_scene.d.node_count)
     words = np.zeros(2 * n + 1, np.uint32)
-    _check(L.wpt_bypass_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(count), C.c_void_p(words.ctypes.data) if with_words else None))
+    _check(lib().wpt_bypass_plan(C.cast(host_scene.desc, C.c_void_p), C.byref(count), _array_ptr(words if with_words else None)))
     return (int(count.value), words[:2 * n].reshape(n, 2), int(words[2 * n])) if with_words else int(count.value)
 
 
@@ -880,9 +735,7 @@ class Progressive:
         if frame is not None:
             assert frame.is_cuda and frame.is_contiguous() and frame.dtype.is_floating_point and frame.element_size() == 4
             assert frame.numel() == self.width * self.height * 3
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
-        _check(lib().wpt_progress_advance_device(self._handle, rows, fptr, sptr))
+        _check(lib().wpt_progress_advance_device(self._handle, rows, _tensor_ptr(frame), _stream_ptr(stream)))
         return self.rows_done
 
     def preview(self, out=None, stream=None):
@@ -894,8 +747,7 @@ class Progressive:
             if stream is not None:
                 stream.wait_stream(torch.cuda.current_stream())
         assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() == self.width * self.height * 3
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        _check(lib().wpt_progress_preview_device(self._handle, C.c_void_p(out.data_ptr()), sptr))
+        _check(lib().wpt_progress_preview_device(self._handle, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
         return out
 
     def save(self):
@@ -928,18 +780,14 @@ class DeviceScene:
 
     def bypassed_nodes(self):
         """wpt_scene_bypassed_nodes: the inner nodes the walk leaves out, chosen at the upload"""
-        L = lib()
-        L.wpt_scene_bypassed_nodes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         count = C.c_uint32()
-        _check(L.wpt_scene_bypassed_nodes(self._handle, C.byref(count)))
+        _check(lib().wpt_scene_bypassed_nodes(self._handle, C.byref(count)))
         return int(count.value)
 
     def folded_links(self):
         """wpt_scene_folded_links: the folded nodes, counted at the upload"""
-        L = lib()
-        L.wpt_scene_folded_links.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         folded = C.c_uint32()
-        _check(L.wpt_scene_folded_links(self._handle, C.byref(folded)))
+        _check(lib().wpt_scene_folded_links(self._handle, C.byref(folded)))
         return int(folded.value)
 
     def close(self):
@@ -962,50 +810,35 @@ class DeviceScene:
                           width=None, height=None):
         """Asynchronously renders pixels [start, start+size) into `frame`, a CUDA float32 tensor
         [h, w, 3] (full frame).  `counters`: optional CUDA int64 tensor [6] that is added to."""
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
         _check(lib().wpt_render_block_device(self._handle, self.host.camera, C.byref(p), w, h, samples_sqrt,
-                                              start, size, C.c_void_p(frame.data_ptr()), cptr, sptr))
+                                              start, size, C.c_void_p(frame.data_ptr()), _tensor_ptr(counters), _stream_ptr(stream)))
 
     def render_bands_into(self, frame, samples_sqrt, band_rows, first_band, band_stride, params=None, counters=None, stream=None,
                           width=None, height=None):
         """Asynchronously renders bands first_band, first_band + band_stride, ... of `band_rows` rows each into `frame`
         (one launch: a rank's interleaved share of the frame)."""
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
-        p = params if params is not None else host.default_params()
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
-        L = lib()
-        L.wpt_render_bands_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        _check(L.wpt_render_bands_device(self._handle, C.cast(self.host.camera, C.c_void_p), C.addressof(p), w, h, samples_sqrt,
-                                         band_rows, first_band, band_stride, C.c_void_p(frame.data_ptr()), cptr, sptr))
+        p = _params(params)
+        _check(lib().wpt_render_bands_device(self._handle, C.cast(self.host.camera, C.c_void_p), C.addressof(p), w, h, samples_sqrt,
+                                             band_rows, first_band, band_stride, C.c_void_p(frame.data_ptr()), _tensor_ptr(counters),
+                                             _stream_ptr(stream)))
 
     def render(self, samples_sqrt, block=None, params=None, with_counters=False, width=None, height=None):
         """Synchronous convenience: returns (frame as numpy [h, w, 3], counters dict or None)."""
         import torch
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
-        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
+        counters = _new_counters(with_counters)
         stream = torch.cuda.current_stream()
         self.render_block_into(frame, samples_sqrt, block, params, counters, stream, w, h)
         torch.cuda.synchronize()
         self.check()
-        cnt = None
-        if with_counters:
-            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
-            cnt = dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
-        return frame.cpu().numpy(), cnt
+        return frame.cpu().numpy(), _counters_dict(counters) if with_counters else None
 
     def progressive(self, samples_sqrt, block=None, params=None, width=None, height=None, tag=None, sensor=SENSOR_FRAME,
                     with_counters=False, bands=False):
@@ -1014,9 +847,8 @@ class DeviceScene:
         launch the session is to stand for; anything but one plain frame is refused with the library's reason."""
         from . import host
         progress_covers(sensor, with_counters, bands)
-        w = width or self.host.width
-        h = height or self.host.height
-        p = params if params is not None else host.default_params()
+        w, h = _frame_size(self.host, width, height)
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
         handle = C.c_void_p()
         _check(lib().wpt_progress_begin(self._handle, self.host.camera, C.byref(p), w, h, samples_sqrt, start, size,
@@ -1032,7 +864,7 @@ class DeviceScene:
         info = progress_state_info(state)
         if samples_sqrt is not None and int(samples_sqrt) != info["samples_sqrt"]:
             raise RuntimeError("wurblpt_hip: the state was saved with a different samples_sqrt (%d, not %d)" % (info["samples_sqrt"], samples_sqrt))
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         handle = C.c_void_p()
         _check(lib().wpt_progress_restore(self._handle, state, len(state), self.host.camera, C.byref(p),
                                           host.scene_tag(self.host) if tag is None else tag, C.byref(handle)))
@@ -1072,26 +904,22 @@ class DeviceScene:
         `frame`: CUDA float32 tensor [h, w, 3] or None; `bins`: CUDA float32 tensor [K, h, w, 3] (full frames);
         `edges`: K + 1 increasing floats (the last may be inf).  Bin k is the light whose optical path length lies in
         [edges[k], edges[k + 1]), per channel, behind the distance gate of `params`."""
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         e = _edges_array(edges)
         K = e.size - 1
         assert bins.is_cuda and bins.is_contiguous() and bins.dtype.is_floating_point and bins.element_size() == 4 and bins.numel() == K * w * h * 3
         if frame is not None:
             assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
         _check(lib().wpt_render_transient_block_device(self._handle, self.host.camera, C.byref(p), C.c_void_p(e.ctypes.data), K,
-                                                        w, h, samples_sqrt, start, size, fptr, C.c_void_p(bins.data_ptr()), sptr))
+                                                        w, h, samples_sqrt, start, size, _tensor_ptr(frame), C.c_void_p(bins.data_ptr()),
+                                                        _stream_ptr(stream)))
 
     def render_transient(self, samples_sqrt, edges, block=None, params=None, width=None, height=None):
         """Synchronous convenience: returns (frame [h, w, 3], bins [K, h, w, 3]) as numpy arrays."""
         import torch
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         K = _edges_array(edges).size - 1
         frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
         bins = torch.zeros((K, h, w, 3), dtype=torch.float32, device="cuda")
@@ -1103,12 +931,10 @@ class DeviceScene:
     def render_transient_host(self, samples_sqrt, edges, block, params=None, width=None, height=None):
         """wpt_render_transient_block: submitBlock semantics; returns (block rgb [size, 3], block bins [K, size, 3])."""
         import numpy as np
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         e = _edges_array(edges)
         K = e.size - 1
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block
         rgb = np.zeros((size, 3), dtype=np.float32)
         bins = np.zeros((K, size, 3), dtype=np.float32)
@@ -1123,29 +949,24 @@ class DeviceScene:
         `groups`: one integer per material record of the scene (host.emitters lists those that emit), a group below K or
         _abi.LIGHT_GROUP_NONE; `env_group`: the environment's.  Plane g is bit for bit the plain render of the scene in which
         only group g emits (host.mute_emitters); both gates of `params` apply to the planes as to the frame."""
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         t = _groups_table(groups, self.host.d.material_count)
         K = int(group_count)
         assert planes.is_cuda and planes.is_contiguous() and planes.dtype.is_floating_point and planes.element_size() == 4 \
             and planes.numel() == K * w * h * 3
         if frame is not None:
             assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        fptr = C.c_void_p(frame.data_ptr()) if frame is not None else None
         _check(lib().wpt_render_light_groups_block_device(self._handle, self.host.camera, C.byref(p), C.c_void_p(t.ctypes.data), t.size, K,
-                                                           int(env_group), w, h, samples_sqrt, start, size, fptr,
-                                                           C.c_void_p(planes.data_ptr()), sptr))
+                                                           int(env_group), w, h, samples_sqrt, start, size, _tensor_ptr(frame),
+                                                           C.c_void_p(planes.data_ptr()), _stream_ptr(stream)))
 
     def render_light_groups(self, samples_sqrt, groups, group_count, env_group=_abi.LIGHT_GROUP_NONE, block=None, params=None,
                             width=None, height=None):
         """Synchronous convenience: returns (frame [h, w, 3], planes [K, h, w, 3]) as numpy arrays."""
         import torch
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
         planes = torch.zeros((int(group_count), h, w, 3), dtype=torch.float32, device="cuda")
         self.render_light_groups_into(frame, planes, samples_sqrt, groups, group_count, env_group, block, params,
@@ -1158,12 +979,10 @@ class DeviceScene:
                                  width=None, height=None):
         """wpt_render_light_groups_block: submitBlock semantics; returns (block rgb [size, 3], block planes [K, size, 3])."""
         import numpy as np
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         t = _groups_table(groups, self.host.d.material_count)
         K = int(group_count)
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block
         rgb = np.zeros((size, 3), dtype=np.float32)
         planes = np.zeros((K, size, 3), dtype=np.float32)
@@ -1177,16 +996,14 @@ class DeviceScene:
         `planes`: CUDA float32 tensor [n, h, w, 3] = (a, b, total) per phase image; `sensor`: host.tof_sensor(...);
         `phases`: indices of the sensor's phase images to render (default: all of them, n = sensor.phase_count).  Plane j is
         bit for bit the one-phase launch of that phase; `params` must carry the default gates."""
-        from . import host
         w, h = self.host.width, self.host.height
         s = _tof_phases(sensor, phases)
         assert planes.is_cuda and planes.is_contiguous() and planes.dtype.is_floating_point and planes.element_size() == 4 \
             and planes.numel() == s.phase_count * w * h * 3
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(lib().wpt_render_tof_block_device(self._handle, self.host.camera, C.byref(p), C.byref(s), w, h, samples_sqrt, start, size,
-                                                  C.c_void_p(planes.data_ptr()), sptr))
+                                                  C.c_void_p(planes.data_ptr()), _stream_ptr(stream)))
 
     def render_tof(self, samples_sqrt, sensor, phases=None, block=None, params=None):
         """Synchronous convenience: returns the planes [n, h, w, 3] as a numpy array (pixels outside `block` are 0)."""
@@ -1202,84 +1019,66 @@ class DeviceScene:
     def render_tof_host(self, samples_sqrt, sensor, block, phases=None, params=None):
         """wpt_render_tof_block: submitBlock semantics; returns the block's planes [n, size, 3]."""
         import numpy as np
-        from . import host
         w, h = self.host.width, self.host.height
         s = _tof_phases(sensor, phases)
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block
         planes = np.zeros((s.phase_count, size, 3), dtype=np.float32)
         _check(lib().wpt_render_tof_block(self._handle, self.host.camera, C.byref(p), C.byref(s), w, h, samples_sqrt, start, size,
                                            C.c_void_p(planes.ctypes.data)))
         return planes
 
+    def _views_args(self, frames, cameras, params):
+        """(camera array, V, params, w, h) of a launch of a batch of views into `frames`, checked to be [V, h, w, 3]"""
+        V = len(cameras)
+        assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point and frames.element_size() == 4
+        assert frames.dim() == 4 and frames.shape[0] == V and frames.shape[3] == 3, "frames: [V, h, w, 3]"
+        return (_abi.Camera * max(V, 1))(*cameras), V, _params(params), int(frames.shape[2]), int(frames.shape[1])
+
     def render_views_into(self, frames, cameras, samples_sqrt, params=None, counters=None, stream=None):
         """Asynchronously renders a batch of views in one launch: frame v of `frames`, a CUDA float32 tensor [V, h, w, 3], from
         cameras[v] (_abi.Camera records, e.g. host.camera_looking_at).  One parameter set, frame size and sample count serve all
         views; frame v is bit for bit the plain render of cameras[v].  `counters`: optional CUDA int64 tensor [6] that the sum
         over all views is added to."""
-        from . import host
-        V = len(cameras)
-        assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point and frames.element_size() == 4
-        assert frames.dim() == 4 and frames.shape[0] == V and frames.shape[3] == 3, "frames: [V, h, w, 3]"
-        h, w = int(frames.shape[1]), int(frames.shape[2])
-        cams = (_abi.Camera * max(V, 1))(*cameras)
-        p = params if params is not None else host.default_params()
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
+        cams, V, p, w, h = self._views_args(frames, cameras, params)
         _check(lib().wpt_render_views_device(self._handle, cams, V, C.byref(p), w, h, samples_sqrt, C.c_void_p(frames.data_ptr()),
-                                             cptr, sptr))
-
-    def render_views(self, samples_sqrt, cameras, params=None, with_counters=False, width=None, height=None):
-        """Synchronous convenience: returns the frames as a CUDA tensor [V, h, w, 3] (and the counters dict with_counters)."""
-        import torch
-        w = width or self.host.width
-        h = height or self.host.height
-        frames = torch.zeros((len(cameras), h, w, 3), dtype=torch.float32, device="cuda")
-        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
-        self.render_views_into(frames, cameras, samples_sqrt, params, counters, torch.cuda.current_stream())
-        torch.cuda.synchronize()
-        self.check()
-        if with_counters:
-            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
-            return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
-        return frames
+                                             _tensor_ptr(counters), _stream_ptr(stream)))
 
     def render_view_streams_into(self, frames, cameras, samples_sqrt, streams=None, params=None, counters=None, stream=None):
         """render_views_into with a sample stream per view: view v is stream streams[v] of cameras[v], i.e. pixel p's generator is
         seeded from p + streams[v] * w * h (in 64 bits) instead of p.  `streams`: V integers in [0, 2^32), or None for all 0,
         which is render_views_into.  Stream 0 is the plain render bit for bit."""
         import numpy as np
-        from . import host
-        V = len(cameras)
-        assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point and frames.element_size() == 4
-        assert frames.dim() == 4 and frames.shape[0] == V and frames.shape[3] == 3, "frames: [V, h, w, 3]"
-        h, w = int(frames.shape[1]), int(frames.shape[2])
-        cams = (_abi.Camera * max(V, 1))(*cameras)
+        cams, V, p, w, h = self._views_args(frames, cameras, params)
         ks = None
         if streams is not None:
             if len(streams) != V or any(not 0 <= int(k) < 2 ** 32 for k in streams):
                 raise ValueError("streams: one integer in [0, 2^32) per view")
             ks = np.ascontiguousarray(np.array([int(k) for k in streams], dtype=np.uint32))
-        p = params if params is not None else host.default_params()
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
-        _check(lib().wpt_render_view_streams_device(self._handle, cams, C.c_void_p(ks.ctypes.data) if ks is not None and V else None, V,
-                                                    C.byref(p), w, h, samples_sqrt, C.c_void_p(frames.data_ptr()), cptr, sptr))
+        _check(lib().wpt_render_view_streams_device(self._handle, cams, _array_ptr(ks if V else None), V, C.byref(p), w, h, samples_sqrt,
+                                                    C.c_void_p(frames.data_ptr()), _tensor_ptr(counters), _stream_ptr(stream)))
+
+    def _render_views(self, into, cameras, with_counters, width, height):
+        """the synchronous form of a batch of views, launched by into(frames, counters, stream)"""
+        import torch
+        w, h = _frame_size(self.host, width, height)
+        frames = torch.zeros((len(cameras), h, w, 3), dtype=torch.float32, device="cuda")
+        counters = _new_counters(with_counters)
+        into(frames, counters, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        self.check()
+        return (frames, _counters_dict(counters)) if with_counters else frames
+
+    def render_views(self, samples_sqrt, cameras, params=None, with_counters=False, width=None, height=None):
+        """Synchronous convenience: returns the frames as a CUDA tensor [V, h, w, 3] (and the counters dict with_counters)."""
+        return self._render_views(lambda frames, counters, stream: self.render_views_into(frames, cameras, samples_sqrt, params, counters, stream),
+                                  cameras, with_counters, width, height)
 
     def render_view_streams(self, samples_sqrt, cameras, streams=None, params=None, with_counters=False, width=None, height=None):
         """Synchronous convenience: returns the frames as a CUDA tensor [V, h, w, 3] (and the counters dict with_counters)."""
-        import torch
-        w = width or self.host.width
-        h = height or self.host.height
-        frames = torch.zeros((len(cameras), h, w, 3), dtype=torch.float32, device="cuda")
-        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
-        self.render_view_streams_into(frames, cameras, samples_sqrt, streams, params, counters, torch.cuda.current_stream())
-        torch.cuda.synchronize()
-        self.check()
-        if with_counters:
-            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
-            return frames, dict(zip(names, [int(x) for x in counters.cpu().tolist()]))
-        return frames
+        return self._render_views(lambda frames, counters, stream: self.render_view_streams_into(frames, cameras, samples_sqrt, streams, params,
+                                                                                                 counters, stream),
+                                  cameras, with_counters, width, height)
 
     def render_split_into(self, frame, stream_samples_sqrt, streams, first=0, moments=None, params=None, counters=None, stream=None,
                           camera=None):
@@ -1288,7 +1087,6 @@ class DeviceScene:
         a CUDA float32 tensor [h, w, 3]; `moments` (optional, the same shape): the stream moment film, the mean of the stream
         frames' squares.  Asynchronous on `stream`; the scratch (streams * h * w * 12 bytes) is allocated and freed in stream
         order.  `counters`: optional CUDA int64 tensor [6] that the sum over all streams is added to."""
-        from . import host
         assert frame.is_cuda and frame.is_contiguous() and frame.dtype.is_floating_point and frame.element_size() == 4
         assert frame.dim() == 3 and frame.shape[2] == 3, "frame: [h, w, 3]"
         h, w = int(frame.shape[0]), int(frame.shape[1])
@@ -1297,24 +1095,20 @@ class DeviceScene:
             assert tuple(moments.shape) == tuple(frame.shape), "moments: the frame's shape"
         if not (0 <= int(streams) < 2 ** 32 and 0 <= int(first) < 2 ** 32):
             raise ValueError("render_split: streams and first are 32-bit counts")
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         cam = C.byref(camera) if camera is not None else self.host.camera
-        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        cptr = C.c_void_p(counters.data_ptr()) if counters is not None else None
-        mptr = C.c_void_p(moments.data_ptr()) if moments is not None else None
         _check(lib().wpt_render_split_device(self._handle, cam, C.byref(p), w, h, stream_samples_sqrt, int(first), int(streams),
-                                             C.c_void_p(frame.data_ptr()), mptr, cptr, sptr))
+                                             C.c_void_p(frame.data_ptr()), _tensor_ptr(moments), _tensor_ptr(counters), _stream_ptr(stream)))
 
     def render_split(self, stream_samples_sqrt, streams, first=0, with_moments=False, params=None, with_counters=False, width=None,
                      height=None, camera=None):
         """Synchronous convenience: returns the frame as numpy [h, w, 3]; with_moments (frame, moments); with_counters the counters
         dict as a last element as well."""
         import torch
-        w = width or self.host.width
-        h = height or self.host.height
+        w, h = _frame_size(self.host, width, height)
         frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
         moments = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if with_moments else None
-        counters = torch.zeros(6, dtype=torch.int64, device="cuda") if with_counters else None
+        counters = _new_counters(with_counters)
         self.render_split_into(frame, stream_samples_sqrt, streams, first, moments, params, counters, torch.cuda.current_stream(), camera)
         torch.cuda.synchronize()
         self.check()
@@ -1322,8 +1116,7 @@ class DeviceScene:
         if with_moments:
             out.append(moments.cpu().numpy())
         if with_counters:
-            names = ("samples", "rays", "node_visits", "leaf_tests", "pdf_tests", "scatters")
-            out.append(dict(zip(names, [int(x) for x in counters.cpu().tolist()])))
+            out.append(_counters_dict(counters))
         return out[0] if len(out) == 1 else tuple(out)
 
     def render_adaptive_into(self, frame, samples_sqrt, moments=None, block=None, params=None, stream=None):
@@ -1335,7 +1128,6 @@ class DeviceScene:
         ready.  Asynchronous for a CUDA map of torch.uint16; a CUDA map of another integer type is range-checked on the
         device, which reads one flag back (a sync of the current stream); a host map is checked on the host and uploaded."""
         import torch
-        from . import host
         if not (isinstance(samples_sqrt, torch.Tensor) and samples_sqrt.is_cuda):
             _map_int(samples_sqrt)
         assert len(samples_sqrt.shape) == 2, "samples_sqrt: [h, w]"
@@ -1351,11 +1143,10 @@ class DeviceScene:
         if launch != current:
             launch.wait_stream(current)
             m16.record_stream(launch)                   # freed only after the launch stream's use
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block if block is not None else (0, w * h)
-        mptr = C.c_void_p(moments.data_ptr()) if moments is not None else None
         _check(lib().wpt_render_adaptive_block_device(self._handle, self.host.camera, C.byref(p), w, h, C.c_void_p(m16.data_ptr()),
-                                                       start, size, C.c_void_p(frame.data_ptr()), mptr, C.c_void_p(launch.cuda_stream)))
+                                                       start, size, C.c_void_p(frame.data_ptr()), _tensor_ptr(moments), _stream_ptr(launch)))
 
     def render_adaptive(self, samples_sqrt, with_moments=False, block=None, params=None):
         """Synchronous convenience: returns the frame as a new CUDA tensor [h, w, 3] (zeros where n_p = 0), and with_moments
@@ -1373,26 +1164,22 @@ class DeviceScene:
         """wpt_render_adaptive_block: submitBlock semantics.  `block_rgb` and `block_moments` (or None): numpy float32
         [size, 3], written in place for the block's pixels with n_p > 0 and left as they are elsewhere."""
         import numpy as np
-        from . import host
         a = _map_int(samples_sqrt)
         h, w = a.shape
         m = np.ascontiguousarray(a.astype(np.uint16))
-        p = params if params is not None else host.default_params()
+        p = _params(params)
         start, size = block
         for b in (block_rgb, block_moments):
             assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.size == size * 3)
         _check(lib().wpt_render_adaptive_block(self._handle, self.host.camera, C.byref(p), w, h, C.c_void_p(m.ctypes.data), start, size,
-                                               C.c_void_p(block_rgb.ctypes.data),
-                                               C.c_void_p(block_moments.ctypes.data) if block_moments is not None else None))
+                                               C.c_void_p(block_rgb.ctypes.data), _array_ptr(block_moments)))
         return block_rgb, block_moments
 
     def render_block_host(self, samples_sqrt, block, params=None, width=None, height=None):
         """wpt_render_block: MPICoordinator::submitBlock semantics, host buffer of size*3 floats."""
         import numpy as np
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
-        p = params if params is not None else host.default_params()
+        w, h = _frame_size(self.host, width, height)
+        p = _params(params)
         start, size = block
         out = np.zeros((size, 3), dtype=np.float32)
         _check(lib().wpt_render_block(self._handle, self.host.camera, C.byref(p), w, h, samples_sqrt, start, size,
@@ -1405,24 +1192,19 @@ class DeviceScene:
         GroundTruth bits (None: the three arrays a denoiser call reads, GUIDE_NAMES), left in device memory.  Asynchronous on
         `stream` (None: torch's current stream).  times = (t0, tPrev, tNext) for animated instances."""
         import torch
-        from . import host
         if bits is None:
             bits = sum(1 << GT_NAMES.index(name) for name in GUIDE_NAMES)
-        w = width or self.host.width
-        h = height or self.host.height
-        p = params if params is not None else host.default_params()
+        w, h = _frame_size(self.host, width, height)
+        p = _params(params)
         s = stream if stream is not None else torch.cuda.current_stream()
         with torch.cuda.stream(s):
-            arrays = [torch.zeros((h, w, GT_COMPONENTS[k]), dtype=torch.int32 if k == 19 else torch.float32, device="cuda")
-                      if bits & (1 << k) else None for k in range(20)]
+            arrays = _gt_alloc(torch, w, h, bits, device="cuda")
         ptrs = (C.c_void_p * 20)(*[a.data_ptr() if a is not None else None for a in arrays])
-        L = lib()
-        L.wpt_ground_truth_device.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         tm = (C.c_float * 3)(*times) if times is not None else None
-        _check(L.wpt_ground_truth_device(self._handle, C.cast(self.host.camera, C.c_void_p),
-                                         C.addressof(camera_prev) if camera_prev is not None else None,
-                                         C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs,
-                                         C.c_void_p(s.cuda_stream)))
+        _check(lib().wpt_ground_truth_device(self._handle, C.cast(self.host.camera, C.c_void_p),
+                                             C.addressof(camera_prev) if camera_prev is not None else None,
+                                             C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs,
+                                             C.c_void_p(s.cuda_stream)))
         return {GT_NAMES[k]: a for k, a in enumerate(arrays) if a is not None}
 
     def first_hit_colours_device(self, albedo=True, emission=True, guide=True, params=None, width=None, height=None, stream=None):
@@ -1431,47 +1213,26 @@ class DeviceScene:
         handed to denoise / denoise_demodulated as the guide.  The picture is taken at params.t0.  Asynchronous on `stream`
         (None: torch's current stream)."""
         import torch
-        from . import host
-        w = width or self.host.width
-        h = height or self.host.height
-        p = params if params is not None else host.default_params()
+        w, h = _frame_size(self.host, width, height)
+        p = _params(params)
         s = stream if stream is not None else torch.cuda.current_stream()
-        out = {}
         with torch.cuda.stream(s):
-            for name, wanted in (("albedo", albedo), ("emission", emission)):
-                if wanted:
-                    out[name] = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
-            if guide:
-                for name in GUIDE_NAMES:
-                    k = GT_NAMES.index(name)
-                    out[name] = torch.zeros((h, w, GT_COMPONENTS[k]), dtype=torch.int32 if k == 19 else torch.float32, device="cuda")
+            out = _first_hit_alloc(torch, w, h, albedo, emission, guide, device="cuda")
         ptrs = (C.c_void_p * 3)(*[out[name].data_ptr() for name in GUIDE_NAMES]) if guide else None
         _check(lib().wpt_first_hit_colours_device(self._handle, C.cast(self.host.camera, C.c_void_p), C.addressof(p), w, h,
-                                                  C.c_void_p(out["albedo"].data_ptr()) if albedo else None,
-                                                  C.c_void_p(out["emission"].data_ptr()) if emission else None, ptrs,
-                                                  C.c_void_p(s.cuda_stream)))
+                                                  _tensor_ptr(out.get("albedo")), _tensor_ptr(out.get("emission")), ptrs, C.c_void_p(s.cuda_stream)))
         return out
 
 
 def first_hit_colours(scene, albedo=True, emission=True, guide=True, params=None, width=None, height=None):
     """wpt_first_hit_colours on a DeviceScene: the dict of DeviceScene.first_hit_colours_device as numpy arrays (synchronous)"""
     import numpy as np
-    from . import host
-    w = width or scene.host.width
-    h = height or scene.host.height
-    p = params if params is not None else host.default_params()
-    out = {}
-    for name, wanted in (("albedo", albedo), ("emission", emission)):
-        if wanted:
-            out[name] = np.zeros((h, w, 3), np.float32)
-    if guide:
-        for name in GUIDE_NAMES:
-            k = GT_NAMES.index(name)
-            out[name] = np.zeros((h, w, GT_COMPONENTS[k]), np.int32 if k == 19 else np.float32)
+    w, h = _frame_size(scene.host, width, height)
+    p = _params(params)
+    out = _first_hit_alloc(np, w, h, albedo, emission, guide)
     ptrs = (C.c_void_p * 3)(*[out[name].ctypes.data for name in GUIDE_NAMES]) if guide else None
     _check(lib().wpt_first_hit_colours(scene._handle, C.cast(scene.host.camera, C.c_void_p), C.addressof(p), w, h,
-                                       C.c_void_p(out["albedo"].ctypes.data) if albedo else None,
-                                       C.c_void_p(out["emission"].ctypes.data) if emission else None, ptrs))
+                                       _array_ptr(out.get("albedo")), _array_ptr(out.get("emission")), ptrs))
     return out
 
 
@@ -1485,11 +1246,26 @@ GT_COMPONENTS = (3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 1, 1, 2, 3, 3, 3, 3, 2, 2, 1)
 GT_ALL = (1 << 20) - 1
 
 
+def _gt_alloc(xp, width, height, bits, **where):
+    """The zeroed outputs of a ground truth call from the array maker `xp` (numpy, or torch with where = its device): a list of
+    20, array k [height, width, GT_COMPONENTS[k]] (float32; "materials": int32) where bit k of `bits` is set and None elsewhere"""
+    return [xp.zeros((height, width, GT_COMPONENTS[k]), dtype=xp.int32 if GT_NAMES[k] == "materials" else xp.float32, **where)
+            if bits & (1 << k) else None for k in range(20)]
+
+
+def _first_hit_alloc(xp, width, height, albedo, emission, guide, **where):
+    """the zeroed outputs of a first-hit call as a dict: "albedo" and "emission" where wanted and, with `guide`, GUIDE_NAMES"""
+    out = {name: xp.zeros((height, width, 3), dtype=xp.float32, **where) for name, wanted in (("albedo", albedo), ("emission", emission)) if wanted}
+    if guide:
+        arrays = _gt_alloc(xp, width, height, sum(1 << GT_NAMES.index(name) for name in GUIDE_NAMES), **where)
+        out.update((name, arrays[GT_NAMES.index(name)]) for name in GUIDE_NAMES)
+    return out
+
+
 def gt_arrays(width, height, bits=GT_ALL):
     """Host arrays for a ground truth call: (list of numpy arrays or None, ctypes pointer array)."""
     import numpy as np
-    arrays = [np.zeros((height, width, GT_COMPONENTS[k]), np.int32 if k == 19 else np.float32) if bits & (1 << k) else None
-              for k in range(20)]
+    arrays = _gt_alloc(np, width, height, bits)
     ptrs = (C.c_void_p * 20)(*[a.ctypes.data if a is not None else None for a in arrays])
     return arrays, ptrs
 
@@ -1497,17 +1273,13 @@ def gt_arrays(width, height, bits=GT_ALL):
 def ground_truth(scene, bits=GT_ALL, camera_prev=None, camera_next=None, params=None, width=None, height=None, times=None):
     """wpt_ground_truth on a DeviceScene: dict name -> numpy array [h, w, comps] of the requested GroundTruth bits.
     times = (t0, tPrev, tNext) for animated instances."""
-    from . import host
-    w = width or scene.host.width
-    h = height or scene.host.height
-    p = params if params is not None else host.default_params()
+    w, h = _frame_size(scene.host, width, height)
+    p = _params(params)
     arrays, ptrs = gt_arrays(w, h, bits)
-    L = lib()
-    L.wpt_ground_truth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     tm = (C.c_float * 3)(*times) if times is not None else None
-    _check(L.wpt_ground_truth(scene._handle, C.cast(scene.host.camera, C.c_void_p),
-                              C.addressof(camera_prev) if camera_prev is not None else None,
-                              C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs))
+    _check(lib().wpt_ground_truth(scene._handle, C.cast(scene.host.camera, C.c_void_p),
+                                  C.addressof(camera_prev) if camera_prev is not None else None,
+                                  C.addressof(camera_next) if camera_next is not None else None, tm, C.addressof(p), w, h, ptrs))
     return {GT_NAMES[k]: a for k, a in enumerate(arrays) if a is not None}
 
 
@@ -1519,9 +1291,7 @@ def postproc(op, rgb, a=0.0, b=0.0):
     pixels = rgb.size // 3
     code = {"srgb": 0, "urq": 1, "scale": 2, "maxlum": 3}[op]
     out = np.zeros(rgb.shape, np.uint8) if code == 0 else (np.zeros(1, np.float32) if code == 3 else np.zeros(rgb.shape, np.float32))
-    L = lib()
-    L.wpt_postproc_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float]
-    _check(L.wpt_postproc_host(code, C.c_void_p(rgb.ctypes.data), C.c_void_p(out.ctypes.data), pixels, a, b))
+    _check(lib().wpt_postproc_host(code, C.c_void_p(rgb.ctypes.data), C.c_void_p(out.ctypes.data), pixels, a, b))
     return float(out[0]) if code == 3 else out
 
 
@@ -1533,9 +1303,7 @@ def selftest_aabb(boxes, rays):
     tr = torch.as_tensor(np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8), device="cuda")
     assert tb.shape[0] == tr.shape[0]
     out = torch.empty(tb.shape[0], dtype=torch.int32, device="cuda")
-    L = lib()
-    L.wpt_selftest_aabb.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.wpt_selftest_aabb(tb.shape[0], C.c_void_p(tb.data_ptr()), C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
+    _check(lib().wpt_selftest_aabb(tb.shape[0], C.c_void_p(tb.data_ptr()), C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
     return out.cpu().numpy()
 
 
@@ -1547,9 +1315,7 @@ def selftest_triangle(form, cases):
     import torch
     tc = torch.as_tensor(np.ascontiguousarray(cases, dtype=np.float32).reshape(-1, 17), device="cuda")
     out = torch.zeros((tc.shape[0], 8), dtype=torch.int32, device="cuda")
-    L = lib()
-    L.wpt_selftest_triangle.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    _check(L.wpt_selftest_triangle(form, tc.shape[0], C.c_void_p(tc.data_ptr()), C.c_void_p(out.data_ptr())))
+    _check(lib().wpt_selftest_triangle(form, tc.shape[0], C.c_void_p(tc.data_ptr()), C.c_void_p(out.data_ptr())))
     return out.cpu().numpy().view(np.uint32)
 
 
@@ -1560,9 +1326,7 @@ def selftest_rayaux(dirs):
     import torch
     td = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device="cuda")
     out = torch.zeros((td.shape[0], 2, 9), dtype=torch.float32, device="cuda")
-    L = lib()
-    L.wpt_selftest_rayaux.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    _check(L.wpt_selftest_rayaux(td.shape[0], C.c_void_p(td.data_ptr()), C.c_void_p(out.data_ptr())))
+    _check(lib().wpt_selftest_rayaux(td.shape[0], C.c_void_p(td.data_ptr()), C.c_void_p(out.data_ptr())))
     return out.cpu().numpy()
 
 
@@ -1575,9 +1339,7 @@ def selftest_sphere(spheres, rays):
     tr = torch.as_tensor(np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8), device="cuda")
     assert ts.shape[0] == tr.shape[0]
     out = torch.zeros((ts.shape[0], 2), dtype=torch.float32, device="cuda")
-    L = lib()
-    L.wpt_selftest_sphere.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.wpt_selftest_sphere(ts.shape[0], C.c_void_p(ts.data_ptr()), C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
+    _check(lib().wpt_selftest_sphere(ts.shape[0], C.c_void_p(ts.data_ptr()), C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
     return out.cpu().numpy()
 
 
@@ -1588,9 +1350,7 @@ def selftest_hits(scene, rays8):
     import torch
     tr = torch.as_tensor(np.ascontiguousarray(rays8, dtype=np.float32).reshape(-1, 8), device="cuda")
     out = torch.zeros((tr.shape[0], 15), dtype=torch.float32, device="cuda")
-    L = lib()
-    L.wpt_selftest_hits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    _check(L.wpt_selftest_hits(scene._handle, tr.shape[0], C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
+    _check(lib().wpt_selftest_hits(scene._handle, tr.shape[0], C.c_void_p(tr.data_ptr()), C.c_void_p(out.data_ptr())))
     return out.cpu().numpy()
 
 

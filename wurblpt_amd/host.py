@@ -17,6 +17,59 @@ def lib_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get("WPT_LIB_DIR", "lib"), "libwurblpt_host.so")
 
 
+_I, _U, _F, _P, _S, _Q = C.c_int, C.c_uint, C.c_float, C.c_void_p, C.c_char_p, C.c_ulonglong
+_SCENE = _P  # wpt_host_scene*: what a scene maker returns and HostScene keeps
+
+# name -> (restype, argtypes) of every function libwurblpt_host.so exports (wurblpt_amd/host/*.cpp), applied by lib();
+# tests/test_abi.py holds the table to the library's symbols and to the definitions' parameter counts
+FUNCTIONS = {
+    "wpt_host_cornell": (_SCENE, [_I, _I, _I, _U, _U]),
+    "wpt_host_cornell_checker": (_SCENE, [_U, _U]),
+    "wpt_host_random_triangles": (_SCENE, [_U, _U, _I, _U, _U, _F]),
+    "wpt_host_lds_edge_scene": (_SCENE, [_U, _U, _I, _U, _U, _U]),
+    "wpt_host_sponza_like": (_SCENE, [_U, _F, _U, _U, _I, _U, _U]),
+    "wpt_host_courtyard_like": (_SCENE, [_U, _U, _U, _U, _U]),
+    "wpt_host_measured_like": (_SCENE, [_U, _F, _U, _U, _I, _S, _S, _U, _U]),
+    "wpt_host_animated": (_SCENE, [_I, _F, _F, _U, _U]),
+    "wpt_host_furnace": (_SCENE, [_I, _I, _U, _U]),
+    "wpt_host_mis_test": (_SCENE, [_I, _U, _U, _U]),
+    "wpt_host_texture_probe": (_SCENE, [_I, _U, _U]),
+    "wpt_host_spheres": (_SCENE, [_I, _U, _U]),
+    "wpt_host_spot_scene": (_SCENE, [_I, _U, _U]),
+    "wpt_host_tof_scene": (_SCENE, [_I, _I, _F, _F, _U, _U]),
+    "wpt_host_light_groups_scene": (_SCENE, [_I, _F, _F, _S, _S, _U, _U]),
+    "wpt_host_rgl_scene": (_SCENE, [_I, _S, _S, _U, _U]),
+    "wpt_host_import_obj": (_SCENE, [_S, _U, _F, _F, _F, _P, _P, _F, _U, _U]),
+    "wpt_host_import_obj_env": (_SCENE, [_S, _S, _I, _U, _F, _F, _P, _P, _F, _U, _U]),
+    "wpt_host_scene_desc": (C.POINTER(_abi.SceneDesc), [_SCENE]),
+    "wpt_host_scene_camera": (C.POINTER(_abi.Camera), [_SCENE]),
+    "wpt_host_scene_bvh_levels": (_U, [_SCENE]),
+    "wpt_host_scene_free": (None, [_SCENE]),
+    "wpt_host_scene_set_distortion": (None, [_SCENE, _I, _F, _F, _F, _F, _F]),
+    "wpt_host_scene_set_camera_mode": (None, [_SCENE, _I, _F]),
+    "wpt_host_scene_material_scene_index": (None, [_SCENE, _P]),
+    "wpt_host_scene_tag": (C.c_uint64, [C.POINTER(_abi.SceneDesc)]),
+    "wpt_host_default_params": (None, [C.POINTER(_abi.Params)]),
+    "wpt_host_bvh_build": (_U, [_U, _P, _P, C.POINTER(_U)]),
+    "wpt_host_rgl_build": (_Q, [_S, _P, _P, _Q]),
+    "wpt_host_lookat": (None, [_P] * 4),
+    "wpt_host_generate_mesh": (_U, [_I, _I, _I, _F, _P, _P, _U, C.POINTER(_U)]),
+    "wpt_host_image_load": (_Q, [_S, _P, _P, _Q]),
+    "wpt_host_image_save": (_I, [_S, _U, _U, _U, _U, _P]),
+    "wpt_host_mcpt": (_I, [_SCENE, _U, _U, _U, _F, _F, _P, _U]),
+    "wpt_host_get_ground_truth": (_I, [_SCENE, _U, _U, _P, _P, _P, _P]),
+    "wpt_host_postproc": (_I, [_I, _U, _U, _U, _P, _P, _F, _F]),
+    # no wrapper below: the tests call these through lib() (tests/test_oracle_golden.py, tests/test_import.py)
+    "wpt_host_transformation": (None, [_P, _F, _P, _P, _P, _P]),
+    "wpt_host_transformation_chains": (None, [_P]),
+    "wpt_host_projection": (None, [_F, _F, _P]),
+    "wpt_host_animation_at": (None, [_P, _U, _I, _P, _P]),
+    "wpt_host_compute_normals": (None, [_U, _P, _U, _P, _I, _P]),
+    "wpt_host_compute_tangents": (None, [_U, _P, _P, _P, _U, _P, _P]),
+    "wpt_host_obj_dump": (_I, [_S, _S]),
+}
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -30,34 +83,10 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(path)
-        L.wpt_host_cornell.restype = C.c_void_p
-        L.wpt_host_cornell.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint]
-        L.wpt_host_random_triangles.restype = C.c_void_p
-        L.wpt_host_random_triangles.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_uint, C.c_float]
-        L.wpt_host_sponza_like.restype = C.c_void_p
-        L.wpt_host_sponza_like.argtypes = [C.c_uint, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_uint]
-        L.wpt_host_furnace.restype = C.c_void_p
-        L.wpt_host_furnace.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint]
-        L.wpt_host_spheres.restype = C.c_void_p
-        L.wpt_host_spheres.argtypes = [C.c_int, C.c_uint, C.c_uint]
-        L.wpt_host_rgl_scene.restype = C.c_void_p
-        L.wpt_host_rgl_scene.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_uint, C.c_uint]
-        L.wpt_host_rgl_build.restype = C.c_ulonglong
-        L.wpt_host_rgl_build.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_ulonglong]
-        L.wpt_host_measured_like.restype = C.c_void_p
-        L.wpt_host_measured_like.argtypes = [C.c_uint, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_char_p, C.c_char_p, C.c_uint, C.c_uint]
-        L.wpt_host_courtyard_like.restype = C.c_void_p
-        L.wpt_host_courtyard_like.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]
-        L.wpt_host_scene_desc.restype = C.POINTER(_abi.SceneDesc)
-        L.wpt_host_scene_desc.argtypes = [C.c_void_p]
-        L.wpt_host_scene_camera.restype = C.POINTER(_abi.Camera)
-        L.wpt_host_scene_camera.argtypes = [C.c_void_p]
-        L.wpt_host_scene_bvh_levels.restype = C.c_uint
-        L.wpt_host_scene_bvh_levels.argtypes = [C.c_void_p]
-        L.wpt_host_scene_free.argtypes = [C.c_void_p]
-        L.wpt_host_default_params.argtypes = [C.POINTER(_abi.Params)]
-        L.wpt_host_bvh_build.restype = C.c_uint
-        L.wpt_host_bvh_build.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint)]
+        for name, (restype, argtypes) in FUNCTIONS.items():
+            fn = getattr(L, name, None)  # (WPT_LIB_DIR may name an older build, which lacks the newer names)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 
@@ -109,29 +138,20 @@ class HostScene:
 def set_distortion(scene, model, k1=0.0, k2=0.0, k3=0.0, p1=0.0, p2=0.0):
     """Lens distortion for the scene's camera: model 1 RadialAndPlanar(k1,k2,p1,p2), 2 RadialOnly(k1,k2,k3),
     3 OpenCV(k1,k2,k3,p1,p2), 0 none."""
-    L = lib()
-    L.wpt_host_scene_set_distortion.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]
-    L.wpt_host_scene_set_distortion.restype = None
-    L.wpt_host_scene_set_distortion(scene._handle_for_camera, model, k1, k2, k3, p1, p2)
+    lib().wpt_host_scene_set_distortion(scene._handle_for_camera, model, k1, k2, k3, p1, p2)
 
 
 def set_camera_mode(scene, surround_mode=0, stereoscopic_distance=0.0):
     """Camera::surroundMode (0 off, 1 = 180 degrees, 2 = 360 degrees) and ::stereoscopicDistance."""
-    L = lib()
-    L.wpt_host_scene_set_camera_mode.argtypes = [C.c_void_p, C.c_int, C.c_float]
-    L.wpt_host_scene_set_camera_mode.restype = None
-    L.wpt_host_scene_set_camera_mode(scene._handle_for_camera, surround_mode, stereoscopic_distance)
+    lib().wpt_host_scene_set_camera_mode(scene._handle_for_camera, surround_mode, stereoscopic_distance)
 
 
 def lookat(eye, target, up=(0.0, 1.0, 0.0)):
     """Transformation::fromLookAt(eye, target, up) as wpt_host_lookat gives it: 35 float32 -- translation (3), rotation
     quaternion x y z w (4), scaling (3), then toMat4 (16) and toNormalMatrix (9)."""
-    L = lib()
-    L.wpt_host_lookat.argtypes = [C.c_void_p] * 4
-    L.wpt_host_lookat.restype = None
     e, t, u = (np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(3)) for x in (eye, target, up))
     out = np.zeros(35, dtype=np.float32)
-    L.wpt_host_lookat(C.c_void_p(e.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(u.ctypes.data), C.c_void_p(out.ctypes.data))
+    lib().wpt_host_lookat(C.c_void_p(e.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(u.ctypes.data), C.c_void_p(out.ctypes.data))
     return out
 
 
@@ -193,10 +213,7 @@ def cornell(width, height, tall_box_material=0, short_object_material=0):
 def cornell_checker(width, height):
     """The Cornell box (GGX tall box, glass short box) whose walls, floor and ceiling carry checker textures of their colour and a
     quarter of it: a small textured scene, for what a denoiser does to a texture."""
-    L = lib()
-    L.wpt_host_cornell_checker.restype = C.c_void_p
-    L.wpt_host_cornell_checker.argtypes = [C.c_uint, C.c_uint]
-    return HostScene(L.wpt_host_cornell_checker(width, height), width, height, "cornell_checker")
+    return HostScene(lib().wpt_host_cornell_checker(width, height), width, height, "cornell_checker")
 
 
 SPEED_OF_LIGHT = 299792458.0  # m/s in vacuum (the reference's constants.hpp)
@@ -227,10 +244,7 @@ def tof_scene(width, height, variant=0, twin=0, t0=0.0, t1=0.0):
     faces it; 4: the room's wall and light alone; 5: a ToF light with an emission texture facing the camera and a cube it lights.
     twin 1 replaces LightTof(r, angle) by LightSpot(angle, vec3(r)): under SensorRGB its x channel is the ToF scene's fourth;
     twin 2 by LightSpot(angle, vec3(0)): what an RGB sensor sees of the ToF scene."""
-    L = lib()
-    L.wpt_host_tof_scene.restype = C.c_void_p
-    L.wpt_host_tof_scene.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint, C.c_uint]
-    return HostScene(L.wpt_host_tof_scene(variant, twin, t0, t1, width, height), width, height, "tof_scene(variant=%d,twin=%d)" % (variant, twin))
+    return HostScene(lib().wpt_host_tof_scene(variant, twin, t0, t1, width, height), width, height, "tof_scene(variant=%d,twin=%d)" % (variant, twin))
 
 
 def random_triangles(n, seed, width, height, with_texcoords=True, aperture=0.0):
@@ -248,10 +262,7 @@ def lds_edge_scene(triangles, materials, light=0, seed=1, width=40, height=32):
     GGX and K - 3 a glass record.  Clutter triangle c has record K - 1 - c % K and the room's quads go on from there, so the
     highest records are the ones in use and, where there are more records than surfaces, the low ones belong to no triangle.
     Lights 1 and 2 make twins: the same geometry and records but for the light's front side."""
-    L = lib()
-    L.wpt_host_lds_edge_scene.restype = C.c_void_p
-    L.wpt_host_lds_edge_scene.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_uint, C.c_uint]
-    h = L.wpt_host_lds_edge_scene(triangles, materials, light, seed, width, height)
+    h = lib().wpt_host_lds_edge_scene(triangles, materials, light, seed, width, height)
     return HostScene(h, width, height, "lds_edge_scene(%d,%d,light=%d,seed=%d)" % (triangles, materials, light, seed))
 
 
@@ -267,10 +278,7 @@ def animated(width, height, variant=0, t0=0.0, t1=1.0):
     """A room with a turning cube, a swinging panel, a sliding light and a moving camera, bounded for the exposure
     interval [t0, t1] (pass the same t0, t1 in the render parameters).  variant bit 0: thin lens; bit 1: static
     camera; bit 2: static instances."""
-    L = lib()
-    L.wpt_host_animated.restype = C.c_void_p
-    L.wpt_host_animated.argtypes = [C.c_int, C.c_float, C.c_float, C.c_uint, C.c_uint]
-    return HostScene(L.wpt_host_animated(variant, t0, t1, width, height), width, height, "animated(variant=%d)" % variant)
+    return HostScene(lib().wpt_host_animated(variant, t0, t1, width, height), width, height, "animated(variant=%d)" % variant)
 
 
 def courtyard_like(width, height, seed=2, triangles=10_000_000, tex_size=1024):
@@ -293,20 +301,14 @@ def furnace(width, height, material=0, slices=64):
 def mis_test(width, height, with_hot_spots=True, light_mask=15):
     """The scene of wurblpt-mis-test.cpp: four GGX plates under four sphere lights in a white room; the lights are hot
     spots (next-event estimation with MIS) or not (material sampling alone).  light_mask: bit i = light i exists."""
-    L = lib()
-    L.wpt_host_mis_test.restype = C.c_void_p
-    L.wpt_host_mis_test.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint]
-    h = L.wpt_host_mis_test(1 if with_hot_spots else 0, light_mask, width, height)
+    h = lib().wpt_host_mis_test(1 if with_hot_spots else 0, light_mask, width, height)
     return HostScene(h, width, height, "mis_test(hot_spots=%d,lights=%d)" % (with_hot_spots, light_mask))
 
 
 def texture_probe(width, height, compat=0):
     """A textured quad light in front of a float environment map, for checking what a camera ray sees directly
     (wpt_host_texture_probe); compat 0 = Mitsuba, 1 = surround video orientation of the environment."""
-    L = lib()
-    L.wpt_host_texture_probe.restype = C.c_void_p
-    L.wpt_host_texture_probe.argtypes = [C.c_int, C.c_uint, C.c_uint]
-    return HostScene(L.wpt_host_texture_probe(compat, width, height), width, height, "texture_probe(compat=%d)" % compat)
+    return HostScene(lib().wpt_host_texture_probe(compat, width, height), width, height, "texture_probe(compat=%d)" % compat)
 
 
 def spheres(width, height, variant=0):
@@ -323,10 +325,7 @@ def spot_scene(width, height, variant=0):
     (MaterialTwoSided(LightSpot(radians(30), vec3(4)), MaterialLambertian(vec3(0)))), 1 = a stage (floor, back wall, a
     sphere) under coloured spots, one with a checker-textured emission and one a sphere, 2 = the Cornell box with GGX tall
     box, glass short box and the spot ceiling light."""
-    L = lib()
-    L.wpt_host_spot_scene.restype = C.c_void_p
-    L.wpt_host_spot_scene.argtypes = [C.c_int, C.c_uint, C.c_uint]
-    return HostScene(L.wpt_host_spot_scene(variant, width, height), width, height, "spot_scene(variant=%d)" % variant)
+    return HostScene(lib().wpt_host_spot_scene(variant, width, height), width, height, "spot_scene(variant=%d)" % variant)
 
 
 def light_groups_scene(width, height, variant=0, t0=0.0, t1=0.0, dispersive=False):
@@ -338,11 +337,8 @@ def light_groups_scene(width, height, variant=0, t0=0.0, t1=0.0, dispersive=Fals
     panel, bounded for the exposure interval [t0, t1] (pass the same t0, t1 in the render parameters); 3 = two lamps over two
     plates with the measured BRDFs of the committed fixtures (rgl_fixture).  dispersive (variant 0 only): the glass cube has a
     refractive index per channel, so the channels' optical path lengths differ."""
-    L = lib()
-    L.wpt_host_light_groups_scene.restype = C.c_void_p
-    L.wpt_host_light_groups_scene.argtypes = [C.c_int, C.c_float, C.c_float, C.c_char_p, C.c_char_p, C.c_uint, C.c_uint]
-    h = L.wpt_host_light_groups_scene(variant | (16 if dispersive else 0), t0, t1, rgl_fixture("iso").encode(),
-                                      rgl_fixture("aniso").encode(), width, height)
+    h = lib().wpt_host_light_groups_scene(variant | (16 if dispersive else 0), t0, t1, rgl_fixture("iso").encode(),
+                                          rgl_fixture("aniso").encode(), width, height)
     return HostScene(h, width, height, "light_groups_scene(variant=%d)" % variant)
 
 
@@ -442,39 +438,30 @@ IMPORT_DISABLE_LIGHT_SOURCES, IMPORT_DISABLE_HOT_SPOTS, IMPORT_TWO_SIDED_MATERIA
 def import_obj(filename, width, height, eye, at, vfov_degrees=45.0, import_bits=0, scale=1.0, rotate_y_degrees=0.0, env_radiance=0.0):
     """importIntoScene (include/wurblpt/import.hpp) of an OBJ file, an optional constant environment and a
     look-at camera; None if the file cannot be imported."""
-    L = lib()
-    L.wpt_host_import_obj.restype = C.c_void_p
-    L.wpt_host_import_obj.argtypes = [C.c_char_p, C.c_uint, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_uint, C.c_uint]
     e = (C.c_float * 3)(*eye)
     a = (C.c_float * 3)(*at)
-    h = L.wpt_host_import_obj(filename.encode(), import_bits, scale, rotate_y_degrees, env_radiance, e, a, vfov_degrees, width, height)
+    h = lib().wpt_host_import_obj(filename.encode(), import_bits, scale, rotate_y_degrees, env_radiance, e, a, vfov_degrees, width, height)
     return HostScene(h, width, height, "import_obj(%s)" % os.path.basename(filename)) if h else None
 
 
 def import_obj_env(filename, envmap, width, height, eye, at, vfov_degrees=45.0, import_bits=0, scale=1.0, rotate_y_degrees=0.0, importance_n=0):
     """importIntoScene of an OBJ file under an environment map read from an image file, as wurblpt-sponza.cpp:46-59 sets
     its scene up; importance_n > 0: initializeImportanceSampling(importance_n).  None if a file cannot be read."""
-    L = lib()
-    L.wpt_host_import_obj_env.restype = C.c_void_p
-    L.wpt_host_import_obj_env.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_uint, C.c_uint]
     e = (C.c_float * 3)(*eye)
     a = (C.c_float * 3)(*at)
-    h = L.wpt_host_import_obj_env(filename.encode(), envmap.encode(), importance_n, import_bits, scale, rotate_y_degrees, e, a, vfov_degrees, width, height)
+    h = lib().wpt_host_import_obj_env(filename.encode(), envmap.encode(), importance_n, import_bits, scale, rotate_y_degrees, e, a, vfov_degrees, width, height)
     return HostScene(h, width, height, "import_obj_env(%s, %s)" % (os.path.basename(filename), os.path.basename(envmap))) if h else None
 
 
 def image_load(filename):
     """Decodes an image file with the importer's decoders: numpy array [h, w, comps], row 0 = bottom."""
-    L = lib()
-    L.wpt_host_image_load.restype = C.c_ulonglong
-    L.wpt_host_image_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_ulonglong]
     info = (C.c_uint * 4)()
-    n = L.wpt_host_image_load(filename.encode(), info, None, 0)
+    n = lib().wpt_host_image_load(filename.encode(), info, None, 0)
     if n == 0:
         return None
     dtype = [np.uint8, np.uint16, np.float32][info[3]]
     out = np.zeros((info[1], info[0], info[2]), dtype=dtype)
-    L.wpt_host_image_load(filename.encode(), info, C.c_void_p(out.ctypes.data), n)
+    lib().wpt_host_image_load(filename.encode(), info, C.c_void_p(out.ctypes.data), n)
     return out
 
 
@@ -484,9 +471,7 @@ def mcpt(scene, samples_sqrt, t0=0.0, t1=0.0, width=None, height=None, workers=1
     w = width or scene.width
     h = height or scene.height
     frame = np.zeros((h, w, 3), np.float32)
-    L = lib()
-    L.wpt_host_mcpt.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_float, C.c_void_p, C.c_uint]
-    if not L.wpt_host_mcpt(scene._handle, w, h, samples_sqrt, t0, t1, C.c_void_p(frame.ctypes.data), workers):
+    if not lib().wpt_host_mcpt(scene._handle, w, h, samples_sqrt, t0, t1, C.c_void_p(frame.ctypes.data), workers):
         raise RuntimeError("mcpt failed")
     return frame
 
@@ -497,10 +482,7 @@ def scene_tag(scene):
     materials, textures, texels, hotspots, spheres, rgl_brdfs, rgl_data, animations, keyframes; each as its length in bytes, 8
     bytes little endian, then its bytes) and the environment map's type, compat, tex, N and cube_tex.  Computed by the C++
     function itself, so the two sides cannot drift apart."""
-    L = lib()
-    L.wpt_host_scene_tag.restype = C.c_uint64
-    L.wpt_host_scene_tag.argtypes = [C.POINTER(_abi.SceneDesc)]
-    return int(L.wpt_host_scene_tag(scene.desc))
+    return int(lib().wpt_host_scene_tag(scene.desc))
 
 
 MESH_KINDS = {"quad": 0, "cube": 1, "cube_side": 2, "disk": 3, "sphere": 4, "cylinder": 5, "closed_cylinder": 6, "cone": 7,
@@ -510,14 +492,11 @@ MESH_KINDS = {"quad": 0, "cube": 1, "cube_side": 2, "disk": 3, "sphere": 4, "cyl
 def generate_mesh(kind, a=1, b=1, f=0.0):
     """A mesh of include/wurblpt/generator.hpp: (vertices float32 [n, 11] = position, normal, texcoord, tangent; indices
     uint32 [triangles, 3])."""
-    L = lib()
-    L.wpt_host_generate_mesh.restype = C.c_uint
-    L.wpt_host_generate_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]
     cap = 1 << 16
     v = np.zeros((cap, 11), np.float32)
     ind = np.zeros(3 * cap, np.uint32)
     ni = C.c_uint(0)
-    n = L.wpt_host_generate_mesh(MESH_KINDS[kind], a, b, f, C.c_void_p(v.ctypes.data), C.c_void_p(ind.ctypes.data), cap, C.byref(ni))
+    n = lib().wpt_host_generate_mesh(MESH_KINDS[kind], a, b, f, C.c_void_p(v.ctypes.data), C.c_void_p(ind.ctypes.data), cap, C.byref(ni))
     assert n <= cap and ni.value <= 3 * cap
     return v[:n].copy(), ind[:ni.value].reshape(-1, 3).copy()
 
@@ -525,10 +504,7 @@ def generate_mesh(kind, a=1, b=1, f=0.0):
 def material_scene_index(scene):
     """Scene::materialIndex() of every flattened material (what getGroundTruth reports for it)."""
     out = np.zeros(scene.d.material_count, np.int32)
-    L = lib()
-    L.wpt_host_scene_material_scene_index.argtypes = [C.c_void_p, C.c_void_p]
-    L.wpt_host_scene_material_scene_index.restype = None
-    L.wpt_host_scene_material_scene_index(scene._handle, C.c_void_p(out.ctypes.data))
+    lib().wpt_host_scene_material_scene_index(scene._handle, C.c_void_p(out.ctypes.data))
     return out
 
 
@@ -539,13 +515,11 @@ def get_ground_truth(scene, bits=(1 << 20) - 1, prev_from_at=None, next_from_at=
     w = width or scene.width
     h = height or scene.height
     arrays, ptrs = device.gt_arrays(w, h, bits)
-    L = lib()
-    L.wpt_host_get_ground_truth.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     tm = (C.c_float * 3)(*times) if times is not None else None
     pf = np.ascontiguousarray(prev_from_at, np.float32) if prev_from_at is not None else None
     nf = np.ascontiguousarray(next_from_at, np.float32) if next_from_at is not None else None
-    if not L.wpt_host_get_ground_truth(scene._handle, w, h, C.c_void_p(pf.ctypes.data) if pf is not None else None,
-                                       C.c_void_p(nf.ctypes.data) if nf is not None else None, tm, ptrs):
+    if not lib().wpt_host_get_ground_truth(scene._handle, w, h, C.c_void_p(pf.ctypes.data) if pf is not None else None,
+                                           C.c_void_p(nf.ctypes.data) if nf is not None else None, tm, ptrs):
         raise RuntimeError("getGroundTruth failed")
     return {device.GT_NAMES[k]: a for k, a in enumerate(arrays) if a is not None}
 
@@ -556,10 +530,8 @@ def image_save(filename, img):
     if img.ndim == 2:
         img = img[:, :, None]
     code = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}[img.dtype]
-    L = lib()
-    L.wpt_host_image_save.argtypes = [C.c_char_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
-    return bool(L.wpt_host_image_save(filename.encode(), img.shape[1], img.shape[0], img.shape[2], code,
-                                      C.c_void_p(img.ctypes.data)))
+    return bool(lib().wpt_host_image_save(filename.encode(), img.shape[1], img.shape[0], img.shape[2], code,
+                                          C.c_void_p(img.ctypes.data)))
 
 
 def postproc(op, img, a=0.0, b=0.0):
@@ -570,10 +542,8 @@ def postproc(op, img, a=0.0, b=0.0):
     code = {"srgb": 0, "urq": 1, "scale": 2, "maxlum": 3}[op]
     out = (np.zeros(img.shape[:2] + (3,), np.uint8) if code == 0 else
            np.zeros(1, np.float32) if code == 3 else np.zeros(img.shape, np.float32))
-    L = lib()
-    L.wpt_host_postproc.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
-    if not L.wpt_host_postproc(code, img.shape[1], img.shape[0], img.shape[2], C.c_void_p(img.ctypes.data),
-                               C.c_void_p(out.ctypes.data), a, b):
+    if not lib().wpt_host_postproc(code, img.shape[1], img.shape[0], img.shape[2], C.c_void_p(img.ctypes.data),
+                                   C.c_void_p(out.ctypes.data), a, b):
         raise RuntimeError("post-processing failed")
     return float(out[0]) if code == 3 else out
 
