@@ -903,7 +903,12 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
  *                           parent's link, because its box test repeats the parent's on the same inputs: wpt_fold.h); the
  *                           links that go round nodes are built on the fold, so this flag keeps those away too
  *   WPT_WALK_NO_BYPASS      the kernels with the scene in LDS test every node of the folded tree (A/B runs and tests; by default
- *                           links that lead to an inner node of the scene's plan, wpt_bypass_plan below, lead to its first child) */
+ *                           links that lead to an inner node of the scene's plan, wpt_bypass_plan below, lead to its first child)
+ *   WPT_WALK_SMALL_WORKGROUPS  launches of the kernel with rotated corners keep its workgroups of 256 lanes (A/B runs and tests;
+ *                           by default such a launch runs as one workgroup of 1024 lanes per compute unit with the node array
+ *                           in LDS once per sign octant of a ray's direction, so that a box test sorts no slab distances --
+ *                           where no box of the tree has a NaN bound or lo > hi and the copies fit the unit's 160 KiB:
+ *                           wpt_kernel_workgroup) */
 #define WPT_WALK_WIDE 1u
 #define WPT_WALK_FULL_SHADOW 2u
 #define WPT_WALK_COUNT_PRODUCT 4u
@@ -911,6 +916,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
 #define WPT_WALK_SELECT_CORNERS 16u
 #define WPT_WALK_NO_FOLD 32u
 #define WPT_WALK_NO_BYPASS 64u
+#define WPT_WALK_SMALL_WORKGROUPS 128u
 wpt_status wpt_set_walk(uint32_t flags);
 /* Nodes whose link the kernels with the scene in LDS fold in their copy of the tree: inner nodes that go past one or more inner
  * first children with their own box.
@@ -993,6 +999,11 @@ const char* wpt_kernel_name(void);
  * leaf per triangle (the description admits it); its leaf tests read the leaf's node for the skip link, as every other kernel
  * with the scene in LDS does, where otherwise they find it in the triangle's corner records. */
 const char* wpt_kernel_form(void);
+/* Lanes per workgroup of the path-tracing kernel the most recent render call launched: 256, or 1024 for the large form of the
+ * kernel with rotated corners (WPT_WALK_SMALL_WORKGROUPS above).  *ordered_boxes (or NULL): 1 if that launch walked ordered box
+ * copies, else 0.  wpt_kernel_name, wpt_kernel_form and wpt_kernel_choice do not tell the two apart: the large form is a
+ * decision of the launch on top of that choice. */
+uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes);
 /* Which instantiation of the single kernel renders a launch, from the facts the library decides by: a pure function that needs
  * no device (tests).  need: the feature bits of the scene and the launch's cameras (wpt_device.h, FEAT_*; FEAT_ANIM for a moving
  * scene, a moving camera or an exposure interval); sensor: 0 one frame, 1 transient film, 2 batch of views, 3 adaptive sampling,

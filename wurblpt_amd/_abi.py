@@ -258,6 +258,7 @@ FUNCTIONS = {
     "wpt_bypass_plan": (_I, [_P, _pU, _P]),
     "wpt_kernel_name": (_S, []),
     "wpt_kernel_form": (_S, []),
+    "wpt_kernel_workgroup": (_U, [_pU]),
     "wpt_kernel_choice": (_I, [_U] * 9 + [_pS, _pS, _pU, _pQ, _pU]),
     "wpt_kernel_table_entry": (_I, [_U, _pU, _pS]),
     "wpt_launch_plan": (_I, [_U] * 10 + [_pU]),

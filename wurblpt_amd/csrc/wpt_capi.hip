@@ -31,11 +31,15 @@ std::atomic<const char*> g_kernelForm{""}; /* wpt_kernel_form */
 /* the pair of counters the most recent render call's kernel adds to (wpt_last_slice_stats), or NULL if it was not sliced */
 std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
 
+/* lanes per workgroup of the most recent render call's path-tracing kernel, bit 31: its boxes were ordered (wpt_kernel_workgroup) */
+std::atomic<uint32_t> g_lastWorkgroup{uint32_t(WG)};
+
 static_assert(wptk::PLAN_WG == uint32_t(WG) && wptk::PLAN_SLICE_SLOT_MAX == wptk::SLICE_SLOT_MASK && wptk::SLICE_UNITS_TARGET <= wptk::SLICE_UNITS_MAX
         && wptk::PLAN_FRAME == wptk::SENSOR_FRAME && wptk::PLAN_VIEWS == wptk::SENSOR_VIEWS && wptk::PLAN_ADAPTIVE == wptk::SENSOR_ADAPTIVE
         && wptk::PLAN_SENSORS == wptk::SENSOR_COUNT, "wpt_launch_plan.h restates the kernels' constants and the sensors");
 static_assert(wptl::NODE_CHILD == NODE_CHILD && wptl::NODE_INDEX_MASK == NODE_INDEX_MASK && wptl::PRIM_SPHERE == PRIM_SPHERE && wptl::WIDE_STACK == WIDE_STACK
-        && wptl::WIDE_NONE == WIDE_NONE && wptl::LDS_SCENE_MAX_BYTES == LDS_SCENE_MAX_BYTES, "wpt_scene_layout.h restates the kernels' node words and limits");
+        && wptl::WIDE_NONE == WIDE_NONE && wptl::LDS_SCENE_MAX_BYTES == LDS_SCENE_MAX_BYTES && wptl::ORDERED_COPIES == wptk::ORDERED_COPIES,
+        "wpt_scene_layout.h restates the kernels' node words and limits");
 static_assert(wptw::LEAF_NODE_SHIFT == wptk::LEAF_NODE_SHIFT && wptw::LEAF_NODE_MAX == wptk::LEAF_NODE_MAX && wptw::LEAF_CORNER_MASK == wptk::LEAF_CORNER_MASK
         && LDS_SCENE_MAX_BYTES / 32 <= wptw::LEAF_NODE_MAX && LDS_SCENE_MAX_BYTES / 16 <= wptw::LEAF_CORNER_MASK,
         "wpt_leaf_words.h restates the rotated kernels' leaf word, which has room for every tree that fits LDS");
@@ -60,6 +64,13 @@ void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned 
     g_kernelForm.store(form, std::memory_order_relaxed);
     g_lastPasses.store(passes, std::memory_order_relaxed);
     g_lastSliceStats.store(sliceStats, std::memory_order_relaxed);
+    g_lastWorkgroup.store(uint32_t(WG), std::memory_order_relaxed);
+}
+
+/* ... and, behind recordLaunch, the workgroup of a launch that was not one of WG lanes with the plain node array */
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes)
+{
+    g_lastWorkgroup.store(lanes | (orderedBoxes ? 0x80000000u : 0u), std::memory_order_relaxed);
 }
 
 /* wpt_kernel_form of a launch: "rotated corners" for that form of the kernel with the scene in LDS -- with ", leaf links from
@@ -164,6 +175,14 @@ const char* wpt_kernel_form(void)
     return g_kernelForm.load(std::memory_order_relaxed);
 }
 
+uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes)
+{
+    const uint32_t w = g_lastWorkgroup.load(std::memory_order_relaxed);
+    if (ordered_boxes)
+        *ordered_boxes = w >> 31;
+    return w & 0x7fffffffu;
+}
+
 uint32_t wpt_last_render_passes(void)
 {
     return g_lastPasses.load(std::memory_order_relaxed);
@@ -231,7 +250,8 @@ wpt_status wpt_set_top_nodes(uint32_t nodes)
 
 wpt_status wpt_set_walk(uint32_t flags)
 {
-    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD | WPT_WALK_NO_BYPASS))
+    if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD | WPT_WALK_NO_BYPASS
+            | WPT_WALK_SMALL_WORKGROUPS))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     settings.walk = flags;
     return WPT_OK;

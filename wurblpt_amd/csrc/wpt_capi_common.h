@@ -107,6 +107,9 @@ struct wpt_scene {
      * where the corners lie, and per triangle its leaf's skip link), wptw::leafWordsSize words each.  leafOneToOne: every
      * triangle has exactly one leaf, so the leaf pass of those kernels takes its links from the corner records */
     bool leafOneToOne = false;
+    /* ... and, where every box of the tree has lo <= hi (no NaN bound either), the node array once per sign octant of a ray's
+     * direction for the kernels of 1024 lanes (wpt_scene_layout.h, orderedBoxCopies); else NULL */
+    const float4* orderedNodes = nullptr;
     uint32_t bypassedNodes = 0; /* wpt_scene_bypassed_nodes */
     uint32_t animationCount;
     std::vector<void*> allocations;
@@ -142,6 +145,7 @@ extern Settings settings;
 /* what the process's most recent render call ran (wpt_capi.hip has the words and their readers), the form's name and the
  * kernel table's row of an instantiation: see their definitions there */
 void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned long long* sliceStats);
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes);
 const char* kernelForm(bool rotated, uint32_t units = 0, bool leafLinksFromNodes = false);
 wpt_status lookupKernel(uint32_t features, bool count, bool ldsScene, bool wide, const wptk::KernelEntry** entry);
 

@@ -42,11 +42,11 @@ unsigned long long* sliceStatsOfCurrentDevice()
 
 /* the single kernel of a launch, as every execution below launches it */
 struct SingleKernel {
-    const wptk::KernelEntry* kernel;
+    void (*launch)(const wptk::KernelArgs&, dim3 grid, size_t sceneLdsBytes, hipStream_t);
     dim3 grid;
     size_t sceneLdsBytes;
     hipStream_t stream;
-    void operator()(const wptk::KernelArgs& a) const { kernel->launch(a, grid, sceneLdsBytes, stream); }
+    void operator()(const wptk::KernelArgs& a) const { launch(a, grid, sceneLdsBytes, stream); }
 };
 
 /* TWO_PASSES: one timed row of strata of every pixel, then the rest in the order of those times.  false, and nothing
@@ -221,7 +221,14 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
                 args.materialsInLds |= wptk::LDS_LEAF_LINKS;
         }
     }
-    const SingleKernel run = { kernel, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
+    /* the large form of the kernel with rotated corners and of its twin, where the launch can take it (wpt_kernel_table.h) */
+    size_t largeLdsBytes = 0;
+    const bool large = wptk::selectLargeForm(choice, settings.walk, scene->orderedNodes != nullptr, args.sv.boxesMayBeNan != 0, scene->nodeCount, &largeLdsBytes);
+    if (large && wptk::LARGE_ORDERED)
+        args.sv.rglData = reinterpret_cast<const float*>(scene->orderedNodes); /* (the kernel reads the copies there) */
+    const SingleKernel run = large
+            ? SingleKernel{ wptk::launchPathtraceLarge<FEAT_BASIC | FEAT_ROTATED>, dim3((args.blockSize + WG_LARGE - 1) / WG_LARGE), largeLdsBytes, stream }
+            : SingleKernel{ kernel->launch, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
     bool done = false;
     unsigned long long* sliceStats = nullptr;
     if (args.pool && plan.strategy == wptk::TWO_PASSES)
@@ -229,11 +236,14 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
     else if (args.pool && plan.strategy == wptk::ADAPTIVE_ORDER)
         done = runAdaptiveOrder(args, run, scratch);
     else if (args.pool && plan.strategy == wptk::SLICED)
-        done = (sliceStats = runSliced(args, SingleKernel{ slicedTwin, run.grid, run.sceneLdsBytes, stream }, plan, scratch)) != nullptr;
+        done = (sliceStats = runSliced(args, SingleKernel{ large ? wptk::launchPathtraceLarge<FEAT_BASIC | FEAT_ROTATED | FEAT_SLICED> : slicedTwin->launch, run.grid, run.sceneLdsBytes, stream },
+                plan, scratch)) != nullptr;
     if (!done)
         run(args);
     recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0, choice.rotated && !scene->leafOneToOne), done ? plan.passes : 1u,
             sliceStats);
+    if (large)
+        recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED);
     return hipGetLastError();
 }
 

@@ -264,6 +264,10 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
             WPT_TRY(uploadArray(s, words.data(), words.size(), &onDevice));
             s->ldsLinks = const_cast<uint32_t*>(onDevice);
             s->bypassedNodes = plan.outCount;
+            /* the ordered box copies, for a tree that has them */
+            std::vector<wptl::Quad> ordered;
+            if (wptl::orderedBoxCopies(ldsNodes.data(), desc->node_count, &ordered))
+                WPT_TRY(uploadQuads(s, ordered, &s->orderedNodes));
         }
     }
     {

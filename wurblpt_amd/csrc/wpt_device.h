@@ -284,6 +284,22 @@ template<bool CHECK = true> WPT_D bool boxTest(f3 lo, f3 hi, f3 org, f3 inv, flo
     return hit;
 }
 
+/* AABB::mayHit for a ray and a box that are mirrored on the ray's negative axes (origin, reciprocal and the box's bounds negated
+ * there, the bounds swapped: wpt_scene_layout.h, orderedBoxCopies), for rays whose slab distances are numbers (rayMayNan below)
+ * and boxes with lo <= hi.  Negation is exact, so the six distances are those of boxTest on the originals bit for bit; all
+ * reciprocals are positive, and subtraction and multiplication are monotone under round-to-nearest, so on every axis the
+ * distance to lo is the smaller one: the minima and maxima that sort each pair fall away.  What is left are the same two
+ * numbers boxTest compares (up to the sign of a zero, which cannot change the comparison). */
+WPT_D bool boxTestOrdered(f3 lo, f3 hi, f3 org, f3 inv, float amin, float amax)
+{
+    const v2f tx = (v2f { lo.x, hi.x } - v2f { org.x, org.x }) * v2f { inv.x, inv.x };
+    const v2f t0yz = (v2f { lo.y, lo.z } - v2f { org.y, org.z }) * v2f { inv.y, inv.z };
+    const v2f t1yz = (v2f { hi.y, hi.z } - v2f { org.y, org.z }) * v2f { inv.y, inv.z };
+    const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(tx.x, t0yz.x), t0yz.y), amin);
+    const float tmax = __builtin_fminf(__builtin_fminf(__builtin_fminf(tx.y, t1yz.x), t1yz.y), amax);
+    return tmin <= tmax;
+}
+
 /* Can a slab distance (box - origin) * (1 / direction) of this ray be NaN for a box whose coordinates are numbers?  Only as
  * 0 * inf or inf - inf: a reciprocal that is zero, infinite or NaN (a direction component that is infinite, zero -- also a
  * denormal whose reciprocal overflows -- or NaN), or an origin that is not finite.  For every other ray the six distances are

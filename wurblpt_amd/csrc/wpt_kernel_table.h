@@ -179,6 +179,24 @@ inline KernelChoice selectKernel(const KernelFacts& f)
     return c;
 }
 
+/* The large form (wpt_pathtrace_large): a decision of the launch on top of the choice above, which stays what it reports.  A
+ * launch of the kernel with rotated corners runs as one workgroup of WG_LARGE lanes per compute unit, with the node array once
+ * per sign octant behind the scene, where the scene has those copies (every box of its tree has lo <= hi: hasOrderedCopies), no
+ * bound is NaN, the request fits what one workgroup may declare, and wpt_set_walk(WPT_WALK_SMALL_WORKGROUPS) does not keep the
+ * workgroups of WG lanes.  *sceneLdsBytes: the large launcher's. */
+inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrderedCopies, bool boxesMayBeNan, uint32_t nodeCount, size_t* sceneLdsBytes)
+{
+    size_t bytes = c.sceneLdsBytes;
+    if (LARGE_ORDERED) {
+        uint32_t base, stride;
+        const uint32_t nodeQuads = 2 * nodeCount + 2;
+        bytes = size_t(orderedPlaces(nodeQuads, uint32_t(c.sceneLdsBytes / 16) - nodeQuads, base, stride)) * 16;
+    }
+    *sceneLdsBytes = bytes;
+    return c.rotated && c.ldsScene && c.features == (FEAT_BASIC | FEAT_ROTATED) && !(walk & WPT_WALK_SMALL_WORKGROUPS) && hasOrderedCopies
+            && !boxesMayBeNan && COLD_BYTES_LARGE + bytes <= LDS_BYTES_PER_CU;
+}
+
 } /* namespace wptk */
 
 #endif

@@ -375,6 +375,57 @@ inline uint32_t countFoldedLinks(const uint32_t* nodes, uint32_t nodeCount, uint
     return folded;
 }
 
+/* Ordered box copies (the 1024-lane kernels with the scene in LDS, wpt_pathtrace.inc.h): the node array of a tree that fits LDS
+ * once per sign octant of a ray's direction, eight copies of 2 * nodeCount + 2 quadwords one behind the other.  Copy k has bit a
+ * set for a negative axis a, and on such an axis a record holds (-hi, -lo) in the places of (lo, hi): a ray that walks with that
+ * axis mirrored (origin and reciprocal negated) finds the near bound where lo stands and the far bound where hi stands on every
+ * axis, so that its box test sorts nothing.  Negation is exact, so the six slab distances are the ones the ray computes from the
+ * plain record, bit for bit.  Links and words are copied as they are, and so is the padding behind the last node, where the
+ * kernels put their null node; copy 0 is deviceNodes' array byte for byte.  `nodes`: device nodes, eight words each (the padding
+ * node is added here).  The argument needs lo <= hi on every axis of every node, which a NaN bound fails too: such a tree has no
+ * ordered copies (false, *out empty) and is walked from the plain record. */
+constexpr uint32_t ORDERED_COPIES = 8;
+
+inline bool orderedBoxCopies(const uint32_t* nodes, uint32_t nodeCount, std::vector<Quad>* out)
+{
+    out->clear();
+    std::vector<Quad> plain(2 * size_t(nodeCount) + 2, quad(0.0f, 0.0f, 0.0f, 0.0f));
+    if (nodeCount > 0)
+        memcpy(plain.data(), nodes, 2 * size_t(nodeCount) * sizeof(Quad));
+    for (uint32_t i = 0; i < nodeCount; i++) {
+        const Quad &q0 = plain[2 * size_t(i)], &q1 = plain[2 * size_t(i) + 1];
+        if (!(q0.x <= q0.y && q0.z <= q1.x && q0.w <= q1.y))
+            return false;
+    }
+    std::vector<Quad> copies;
+    copies.reserve(ORDERED_COPIES * plain.size());
+    for (uint32_t k = 0; k < ORDERED_COPIES; k++)
+        for (uint32_t i = 0; i <= nodeCount; i++) {
+            Quad q0 = plain[2 * size_t(i)], q1 = plain[2 * size_t(i) + 1];
+            if (i < nodeCount) {
+                if (k & 1u) {
+                    const float lo = q0.x;
+                    q0.x = -q0.y;
+                    q0.y = -lo;
+                }
+                if (k & 2u) {
+                    const float lo = q0.z;
+                    q0.z = -q1.x;
+                    q1.x = -lo;
+                }
+                if (k & 4u) {
+                    const float lo = q0.w;
+                    q0.w = -q1.y;
+                    q1.y = -lo;
+                }
+            }
+            copies.push_back(q0);
+            copies.push_back(q1);
+        }
+    out->swap(copies);
+    return true;
+}
+
 /* The wide form (wpt_pathtrace.inc.h): the binary tree collapsed by one level, eight quadwords per wide node (lo.x lo.y lo.z
  * hi.x hi.y hi.z of the up to four entries, their references, one spare).  Wide nodes are made for the root and for every inner
  * node that is an entry of a wide node, in depth-first order (a wide node's first inner entry follows it).  The walk's argument

@@ -17,6 +17,7 @@ def lib_path():
 
 
 WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD, WALK_NO_BYPASS = 1, 2, 4, 8, 16, 32, 64  # wpt_set_walk (include/wurblpt_hip.h)
+WALK_SMALL_WORKGROUPS = 128
 SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
 EXPORTS = list(_abi.FUNCTIONS)  # every function include/wurblpt_hip.h declares (the test hooks are not among them)
@@ -661,6 +662,13 @@ def last_slice_stats():
     taken, continued = C.c_uint64(), C.c_uint64()
     _check(lib().wpt_last_slice_stats(C.byref(taken), C.byref(continued)))
     return int(taken.value), int(continued.value)
+
+
+def kernel_workgroup():
+    """wpt_kernel_workgroup: (lanes per workgroup, ordered boxes) of the most recent render call's path-tracing kernel"""
+    ordered = C.c_uint32()
+    lanes = lib().wpt_kernel_workgroup(C.byref(ordered))
+    return int(lanes), bool(ordered.value)
 
 
 def fold_plan(host_scene, with_words=False):
