@@ -215,6 +215,138 @@ inline Array<float> denoise(const Array<float>& frame, const Array<float>& momen
             cameraSpaceMaterialNormals, materials, albedo, emission, params, albedoFloor, variance);
 }
 
+/* The parameters of temporal accumulation (wpt_temporal_params in wurblpt_hip.h, which has the rule) */
+class TemporalParameters
+{
+public:
+    float maxHistory = 32.0f;         // longest history length, in frames
+    float normalCosMin = 0.9f;        // smallest accepted cosine between the current and the reprojected normal
+    float positionTolerance = 0.02f;  // relative to the distance from the previous camera
+};
+
+/* Temporal accumulation in front of the denoiser: a pixel's estimate is carried from frame to frame, so that in regions that stay
+ * visible F frames of n samples count as F * n samples (wpt_postproc_temporal_accumulate_host; wurblpt_hip.h has the rule and
+ * the layout of a history).  Owns the two histories it alternates between (96 bytes per pixel).  Every frame of the sequence
+ * must be rendered with its own samples, and all arrays have the accumulator's size.  Runs on the CPU, with the bits of the
+ * device's form. */
+class TemporalAccumulator
+{
+private:
+    size_t _width, _height;
+    TemporalParameters _params;
+    std::vector<float> _histories[2];
+    unsigned int _newest;   // index of the newest history
+    bool _filled;           // false until the first frame came in, and after reset()
+    TagList _tags;
+
+    const float* newest(const char* what) const
+    {
+        if (!_filled)
+            throw std::logic_error(std::string("TemporalAccumulator::") + what + ": no frame was accumulated yet");
+        return _histories[_newest].data();
+    }
+
+    Array<float> plane(const char* what, size_t planeIndex, size_t first, size_t comps) const
+    {
+        const float* h = newest(what) + planeIndex * _width * _height * 4;
+        Array<float> r(_width, _height, comps);
+        r.globalTagList() = _tags;
+        for (size_t i = 0; i < _width * _height; i++)
+            for (size_t c = 0; c < comps; c++)
+                r[i][c] = h[4 * i + first + c];
+        return r;
+    }
+
+    void run(const Array<float>& frame, const Array<float>& moments, const std::vector<uint16_t>& samplesSqrtMap,
+            const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+            const Array<float>* pixelSpaceOffsetToPrev, const Array<float>* cameraSpaceOffsetToPrev)
+    {
+        const size_t pixels = _width * _height;
+        if (frame.elementCount() != pixels || frame.dimension(0) != _width || frame.componentCount() < 3)
+            throw std::invalid_argument("TemporalAccumulator: the frame must have the accumulator's size and at least three components");
+        const struct { const Array<float>* a; size_t comps; } sized[5] = { { &moments, 3 }, { &cameraSpacePositions, 3 },
+            { &cameraSpaceMaterialNormals, 3 }, { pixelSpaceOffsetToPrev, 2 }, { cameraSpaceOffsetToPrev, 3 } };
+        for (const auto& s : sized)
+            if (s.a && (s.a->elementCount() != pixels || s.a->dimension(0) != _width || s.a->componentCount() != s.comps))
+                throw std::invalid_argument("TemporalAccumulator: every array must have the accumulator's size; moments, positions and "
+                        "normals three components, the pixel offsets two, the camera offsets three");
+        if (materials.elementCount() != pixels || materials.dimension(0) != _width || materials.componentCount() != 1 || samplesSqrtMap.size() != pixels)
+            throw std::invalid_argument("TemporalAccumulator: the materials and the sample-count map must have the accumulator's size");
+        const std::vector<float> rgb = postprocdetail::packRgb(frame);
+        const unsigned int target = _filled ? 1u - _newest : 0u;
+        const wpt_temporal_params p = { _params.maxHistory, _params.normalCosMin, _params.positionTolerance, 0u };
+        if (wpt_postproc_temporal_accumulate_host(rgb.data(), static_cast<const float*>(moments.data()), samplesSqrtMap.data(),
+                    static_cast<const float*>(cameraSpacePositions.data()), static_cast<const float*>(cameraSpaceMaterialNormals.data()),
+                    static_cast<const int32_t*>(materials.data()),
+                    pixelSpaceOffsetToPrev ? static_cast<const float*>(pixelSpaceOffsetToPrev->data()) : nullptr,
+                    cameraSpaceOffsetToPrev ? static_cast<const float*>(cameraSpaceOffsetToPrev->data()) : nullptr,
+                    _filled ? _histories[_newest].data() : nullptr, uint32_t(_width), uint32_t(_height), &p, _histories[target].data(),
+                    nullptr) != WPT_OK)
+            throw std::runtime_error(std::string("temporal accumulation failed: ") + wpt_last_error());
+        _newest = target;
+        _filled = true;
+        _tags = frame.globalTagList();
+    }
+
+public:
+    TemporalAccumulator(size_t width, size_t height, const TemporalParameters& params = TemporalParameters()) :
+        _width(width), _height(height), _params(params), _newest(0), _filled(false)
+    {
+        if (width == 0 || height == 0 || width > 65535 || height > 65535)
+            throw std::invalid_argument("TemporalAccumulator: width and height must lie in 1 .. 65535");
+        for (std::vector<float>& h : _histories)
+            h.resize(width * height * (WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL / sizeof(float)));
+    }
+
+    size_t width() const { return _width; }
+    size_t height() const { return _height; }
+
+    /* the next frame of a scene and a camera at rest: an adaptive or split render's result and moment film, its sample-count map,
+     * and a GroundTruth's cameraSpacePositions, cameraSpaceMaterialNormals and materials */
+    void accumulate(const Array<float>& frame, const Array<float>& moments, const std::vector<uint16_t>& samplesSqrtMap,
+            const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials)
+    {
+        run(frame, moments, samplesSqrtMap, cameraSpacePositions, cameraSpaceMaterialNormals, materials, nullptr, nullptr);
+    }
+
+    /* the next frame with motion: a GroundTruth's pixelSpaceOffsetToPrev and cameraSpaceOffsetToPrev beside the above */
+    void accumulate(const Array<float>& frame, const Array<float>& moments, const std::vector<uint16_t>& samplesSqrtMap,
+            const Array<float>& cameraSpacePositions, const Array<float>& cameraSpaceMaterialNormals, const Array<int32_t>& materials,
+            const Array<float>& pixelSpaceOffsetToPrev, const Array<float>& cameraSpaceOffsetToPrev)
+    {
+        run(frame, moments, samplesSqrtMap, cameraSpacePositions, cameraSpaceMaterialNormals, materials, &pixelSpaceOffsetToPrev,
+                &cameraSpaceOffsetToPrev);
+    }
+
+    /* of the newest history: the accumulated frame (three components, the last frame's tags), the variance of its luminance and
+     * the history length per pixel (one component each) */
+    Array<float> frame() const { return plane("frame", 2, 0, 3); }
+    Array<float> variance() const { return plane("variance", 2, 3, 1); }
+    Array<float> length() const { return plane("length", 1, 3, 1); }
+
+    /* the newest history's records, [3][height][width][4] floats (wurblpt_hip.h has the layout) */
+    const float* history() const { return newest("history"); }
+
+    /* the newest history filtered by the denoiser's iterations (wpt_postproc_denoise_history_host); `variance` (optional)
+     * receives the variance of the result's luminance */
+    Array<float> denoised(const DenoiseParameters& params = DenoiseParameters(), Array<float>* variance = nullptr) const
+    {
+        const float* h = newest("denoised");
+        Array<float> r(_width, _height, 3);
+        r.globalTagList() = _tags;
+        if (variance)
+            *variance = Array<float>(_width, _height, 1);
+        const wpt_denoise_params p = { params.sigmaL, params.sigmaZ, params.normalLog2, params.iterations };
+        if (wpt_postproc_denoise_history_host(h, uint32_t(_width), uint32_t(_height), &p, static_cast<float*>(r.data()),
+                    variance ? static_cast<float*>(variance->data()) : nullptr) != WPT_OK)
+            throw std::runtime_error(std::string("denoise failed: ") + wpt_last_error());
+        return r;
+    }
+
+    /* forget the history: the next frame is a first frame (a cut, a camera jump) */
+    void reset() { _filled = false; }
+};
+
 /* ---- image operations (postproc.hpp:112-337) ---- */
 
 namespace postprocdetail {

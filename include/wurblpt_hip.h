@@ -817,6 +817,72 @@ wpt_status wpt_postproc_denoise_demodulated_host(const float* frame_host, const 
         const float* emission_host, uint32_t width, uint32_t height, const wpt_denoise_params* params, float albedo_floor,
         float* out_host, float* variance_host);
 
+/* ---- temporal accumulation: a pixel's estimate carried from frame to frame along the scene's motion, in front of the denoiser ----
+ * Frame f of a sequence is rendered with its own sample streams (wpt_render_split*, first_stream = f * K), so that frames are
+ * independent estimates; where a surface stays visible, F frames of n samples then count as F * n samples before the spatial
+ * filter runs.  A HISTORY is the denoiser's own three 16-byte records per pixel, kept: [3][height][width] records of four floats
+ * (WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel), row 0 = bottom,
+ *   plane 0 (A)  P.xyz and the bits of m                         plane 1 (B)  n.xyz and the history length N as a float
+ *   plane 2 (C)  the accumulated rgb and V, the variance of its luminance
+ * Callers may read and build histories.  wpt_postproc_temporal_accumulate writes a new history from the current frame and the
+ * previous one; wpt_postproc_denoise_history runs the denoiser's iterations on a history as it is.
+ * Inputs as for wpt_postproc_denoise, and the two motion arrays of wpt_ground_truth* at the frame's size:
+ *   pixel_offset_to_prev   WPT_GT_PIXEL_SPACE_OFFSET_TO_PREV (dx, dy), from pixel centre to pixel centre, in pixels
+ *   camera_offset_to_prev  WPT_GT_CAMERA_SPACE_OFFSET_TO_PREV (3 floats)
+ * both NULL: the caller declares the scene and the camera at rest.  For pixel p = (x, y) the preparation of the denoiser gives
+ * the current records A = (P, m), B = (n, .) and C = (rgb, V_cur); the new records are A, B' and C'.  In float, every operation
+ * rounded on its own, in this order:
+ *   history_prev == NULL (the first frame): C' = C, B'.w = 1.
+ *   Source of the history.  Both offset arrays NULL: the single tap (x, y) with weight 1, and E = P.  Otherwise, m < 0 (nothing
+ *   hit; the ground truth pass writes offset 0 there): reset.  Otherwise fx = (float)x + dx, fy = (float)y + dy;
+ *   !(fx > -1 && fx < width && fy > -1 && fy < height): reset (NaN too).  ix = floorf(fx), wx1 = fx - ix, wx0 = 1 - wx1, the same
+ *   for y; the taps are (ix + i, iy + j), j outer, i inner, with the weights w = wy_j * wx_i; E = P + camera_offset_to_prev[p],
+ *   the point as the previous camera saw it.
+ *   A tap q counts if its weight is not 0, it lies in the frame, m_q == m and, for m >= 0, n . n_q >= normal_cos_min and with
+ *   D = P_q - E: D . D <= (tol * tol) * (E . E), tol = position_tolerance.  (A tap of weight 0 is never read, so whole-pixel
+ *   shifts are exact.)  No tap counts: reset, C' = C, B'.w = 1.
+ *   Otherwise sw = sum(w), H = sum(w * C_q.rgb) / sw, V_H = sum(w * C_q.w) / sw, N_H = sum(w * B_q.w) / sw;
+ *   N' = min(N_H + 1, max_history), a = 1 / N', b = 1 - a;  C'.rgb = b * H + a * C.rgb,  C'.w = (b * b) * V_H + (a * a) * V_cur
+ *   (the variance of a weighted mean of independent estimates),  B'.w = N'.
+ *   A pixel the current frame did not sample (samples_sqrt[p] == 0): with a counting tap C' = (H, V_H) and B'.w = N_H, the history
+ *   carried over; without one C' = C and B'.w = 0, so that the next sampled frame replaces it entirely.
+ * The normals compared are camera-space normals of two different frames: a camera that turns between frames turns a static
+ * surface's normal with it, and normal_cos_min has to cover that turn.  Lighting that changes between frames is not detected;
+ * max_history is the only guard.  `length_out` (may be NULL): B'.w, one float per pixel.
+ * Refused with WPT_ERR_INVALID_ARGUMENT before a device is needed: a NULL frame, moments, samples_sqrt, positions, normals,
+ * materials or history_out; a width or height of 0 or above 65535; exactly one of the two offset arrays NULL; history_out that
+ * is or overlaps history_prev (taps gather from neighbours: nothing works in place); max_history not finite or below 1;
+ * normal_cos_min outside [-1, 1]; position_tolerance negative or not finite; reserved != 0.  The inputs must be finite, except
+ * the offsets, which may be anything.  The device form is one launch, asynchronous on `hip_stream`, and takes no scratch.  The
+ * host form computes the same bits on the CPU and needs no device. */
+#define WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL 48u
+typedef struct wpt_temporal_params {
+    float max_history;        /* default 32: the longest history length, in frames */
+    float normal_cos_min;     /* default 0.9: the smallest accepted cosine between the current and the tap's normal */
+    float position_tolerance; /* default 0.02: relative to the distance from the previous camera */
+    uint32_t reserved;        /* must be 0 */
+} wpt_temporal_params;
+/* `params` NULL: the defaults */
+wpt_status wpt_postproc_temporal_accumulate(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device,
+        const float* pixel_offset_to_prev_device, const float* camera_offset_to_prev_device, const void* history_prev_device,
+        uint32_t width, uint32_t height, const wpt_temporal_params* params, void* history_out_device, float* length_out_device,
+        void* hip_stream);
+wpt_status wpt_postproc_temporal_accumulate_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, const float* pixel_offset_to_prev_host,
+        const float* camera_offset_to_prev_host, const void* history_prev_host, uint32_t width, uint32_t height,
+        const wpt_temporal_params* params, void* history_out_host, float* length_out_host);
+/* The denoiser's iterations (wpt_postproc_denoise above) on a history: guide and colours are the history's planes, there is no
+ * preparation; on the history of a first frame the result is wpt_postproc_denoise's of the same inputs, bit for bit.
+ * iterations = 0 unpacks the accumulated frame and its variance, which is how a caller reads them.  The history is never
+ * written.  `variance` may be NULL.  Refused as wpt_postproc_denoise is (a NULL history or `out`, the sizes, the parameters,
+ * outputs that overlap the history or each other).  The device form is asynchronous on `hip_stream`; its scratch (32 bytes per
+ * pixel, none with no iterations) is allocated and freed in stream order. */
+wpt_status wpt_postproc_denoise_history(const void* history_device, uint32_t width, uint32_t height, const wpt_denoise_params* params,
+        float* out_device, float* variance_device, void* hip_stream);
+wpt_status wpt_postproc_denoise_history_host(const void* history_host, uint32_t width, uint32_t height, const wpt_denoise_params* params,
+        float* out_host, float* variance_host);
+
 /* ---- image operations (postproc.hpp:112-309): scale(), applyLensDistortion() / distort() / undistort(), despeckle(),
  * cameraSpaceDistanceToCoords() and cameraSpaceToPMDSpace() ----
  * Images are [height][width][components] floats, row 0 = bottom; every product and sum is rounded on its own; the device form,

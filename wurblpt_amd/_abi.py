@@ -144,6 +144,17 @@ DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_LOG2 = 8, 16
 DENOISE_ALBEDO_FLOOR = 1.0 / 64  # what an albedo_floor <= 0 of wpt_postproc_denoise_demodulated* stands for
 
 
+class TemporalParams(C.Structure):
+    """wpt_temporal_params; the defaults are the header's"""
+    _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("position_tolerance", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, max_history=32.0, normal_cos_min=0.9, position_tolerance=0.02, reserved=0):
+        super().__init__(max_history, normal_cos_min, position_tolerance, reserved)
+
+
+TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL: three records of four floats
+
+
 # the saved state of a progressive session (include/wurblpt_hip.h has the layout)
 PROGRESS_MAGIC, PROGRESS_STATE_VERSION, PROGRESS_HEADER_BYTES, PROGRESS_CARRY_BYTES = 0x50545057, 1, 224, 32
 
@@ -155,6 +166,7 @@ STRUCT_SIZES = {
     "wpt_keyframe": (Keyframe, 44), "wpt_animation": (Animation, 8),
     "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
     "wpt_progress_info": (ProgressInfo, 48), "wpt_denoise_params": (DenoiseParams, 16),
+    "wpt_temporal_params": (TemporalParams, 16),
 }
 
 
@@ -165,6 +177,7 @@ STRUCT_SIZES = {
 _I, _U, _Q, _F, _P, _S = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p, C.c_char_p
 _pU, _pQ, _pP, _pS = C.POINTER(_U), C.POINTER(_Q), C.POINTER(_P), C.POINTER(_S)
 _CAM, _PAR, _TOF, _DEN = C.POINTER(Camera), C.POINTER(Params), C.POINTER(TofSensor), C.POINTER(DenoiseParams)
+_TMP = C.POINTER(TemporalParams)
 _SCP = [_P, _CAM, _PAR]  # wpt_scene* scene, const wpt_camera* camera, const wpt_params* params
 _WARP = [_P, _U, _U, _U, _CAM, _I, _P]  # wpt_postproc_lens_warp_host, wpt_postproc_distance_to_coords_host
 
@@ -234,6 +247,10 @@ FUNCTIONS = {
     "wpt_postproc_denoise_form": (_S, [_U]),
     "wpt_postproc_denoise_demodulated": (_I, [_P] * 8 + [_U, _U, _DEN, _F] + [_P] * 3),
     "wpt_postproc_denoise_demodulated_host": (_I, [_P] * 8 + [_U, _U, _DEN, _F] + [_P] * 2),
+    "wpt_postproc_temporal_accumulate": (_I, [_P] * 9 + [_U, _U, _TMP] + [_P] * 3),
+    "wpt_postproc_temporal_accumulate_host": (_I, [_P] * 9 + [_U, _U, _TMP] + [_P] * 2),
+    "wpt_postproc_denoise_history": (_I, [_P, _U, _U, _DEN] + [_P] * 3),
+    "wpt_postproc_denoise_history_host": (_I, [_P, _U, _U, _DEN] + [_P] * 2),
     "wpt_postproc_resample": (_I, [_P] + [_U] * 5 + [_P, _P]),
     "wpt_postproc_resample_host": (_I, [_P] + [_U] * 5 + [_P]),
     "wpt_postproc_lens_warp": (_I, _WARP + [_P]),

@@ -1,7 +1,7 @@
 /*
  * wpt_capi_postproc.hip -- of include/wurblpt_hip.h: the output side, every wpt_postproc_* (sRGB, quantisation, luminance; mix,
- * mean and merge of planes; both denoisers; resample, lens warp, despeckle, distance to coordinates) and wpt_set_despeckle_form.
- * Nothing here needs the path tracer: the rules per pixel are in wpt_postproc.h, wpt_lightmix.h, wpt_denoise.h, wpt_image_ops.h
+ * mean and merge of planes; both denoisers, temporal accumulation; resample, lens warp, despeckle, distance to coordinates) and wpt_set_despeckle_form.
+ * Nothing here needs the path tracer: the rules per pixel are in wpt_postproc.h, wpt_lightmix.h, wpt_denoise.h, wpt_temporal.h, wpt_image_ops.h
  * and wpt_streams.h, written once for the device and the host.  Each call's checks stand above its entry points.
  */
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "wpt_postproc.h"
 #include "wpt_lightmix.h"
 #include "wpt_denoise_launch.h"
+#include "wpt_temporal_launch.h"
 #include "wpt_image_ops_launch.h"
 #include "wpt_streams_launch.h"
 
@@ -247,15 +248,10 @@ wpt_status wpt_postproc_merge_means_host(const float* a_host, uint32_t count_a, 
     return WPT_OK;
 }
 
-/* what a denoiser call is refused for, on the device or on the host; fills in the defaults and the filter's own parameters */
-static wpt_status denoiseCheck(const void* frame, const void* moments, const void* samplesSqrt, const void* positions, const void* normals,
-        const void* materials, uint32_t width, uint32_t height, const wpt_denoise_params* params, const void* out, const void* variance,
-        wptdn::Params& filter, uint32_t& iterations)
+/* the part of a denoiser call's checks that the frame's size and the parameters make up; fills in the defaults and the filter's own
+ * parameters */
+static wpt_status denoiseParamsCheck(uint32_t width, uint32_t height, const wpt_denoise_params* params, wptdn::Params& filter, uint32_t& iterations)
 {
-    if (!frame || !moments || !samplesSqrt || !positions || !normals || !materials)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: an input is NULL");
-    if (!out)
-        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame is NULL");
     if (width == 0 || height == 0 || width > wptdn::SIDE_MAX || height > wptdn::SIDE_MAX)
         return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: width and height must lie in 1 .. " + std::to_string(uint32_t(wptdn::SIDE_MAX)));
     const wpt_denoise_params defaults = { 1.0f, 0.1f, 7u, 5u };
@@ -266,6 +262,23 @@ static wpt_status denoiseCheck(const void* frame, const void* moments, const voi
         return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: normal_log2 must lie in 0 .. " + std::to_string(WPT_DENOISE_MAX_NORMAL_LOG2));
     if (!(std::isfinite(p.sigma_l) && p.sigma_l > 0.0f) || !(std::isfinite(p.sigma_z) && p.sigma_z > 0.0f))
         return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: sigma_l and sigma_z must be finite and positive");
+    filter.sigmaL = p.sigma_l;
+    filter.sigmaZ2 = p.sigma_z * p.sigma_z;
+    filter.normalLog2 = p.normal_log2;
+    iterations = p.iterations;
+    return WPT_OK;
+}
+
+/* what a denoiser call is refused for, on the device or on the host */
+static wpt_status denoiseCheck(const void* frame, const void* moments, const void* samplesSqrt, const void* positions, const void* normals,
+        const void* materials, uint32_t width, uint32_t height, const wpt_denoise_params* params, const void* out, const void* variance,
+        wptdn::Params& filter, uint32_t& iterations)
+{
+    if (!frame || !moments || !samplesSqrt || !positions || !normals || !materials)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: an input is NULL");
+    if (!out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame is NULL");
+    WPT_TRY(denoiseParamsCheck(width, height, params, filter, iterations));
     /* the byte ranges of the arrays: an output may overlap neither an input nor the other output */
     const size_t pixels = size_t(width) * height;
     const struct { const void* at; size_t bytes; } in[] = { { frame, pixels * 12 }, { moments, pixels * 12 }, { samplesSqrt, pixels * 2 },
@@ -276,10 +289,6 @@ static wpt_status denoiseCheck(const void* frame, const void* moments, const voi
         if (variance && k < 6 && overlaps(variance, pixels * 4, in[k].at, in[k].bytes))
             return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the variance plane aliases another array of the call");
     }
-    filter.sigmaL = p.sigma_l;
-    filter.sigmaZ2 = p.sigma_z * p.sigma_z;
-    filter.normalLog2 = p.normal_log2;
-    iterations = p.iterations;
     return WPT_OK;
 }
 
@@ -370,6 +379,115 @@ wpt_status wpt_postproc_denoise_demodulated_host(const float* frame_host, const 
     std::vector<wptdn::Rec> scratch(size_t(width) * height * 4);
     wptdn::denoiseDemodulatedHost(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, albedo_host,
             emission_host, width, height, filter, iterations, albedo_floor, scratch.data(), out_host, variance_host);
+    return WPT_OK;
+}
+
+/* what a call of temporal accumulation (wpt_temporal.h) is refused for, on the device or on the host; fills in the defaults and
+ * the rule's own parameters */
+static wpt_status temporalCheck(const void* frame, const void* moments, const void* samplesSqrt, const void* positions, const void* normals,
+        const void* materials, const void* pixelOffsets, const void* cameraOffsets, const void* prev, uint32_t width, uint32_t height,
+        const wpt_temporal_params* params, const void* out, const void* lengthOut, wpttm::Params& rule)
+{
+    if (!frame || !moments || !samplesSqrt || !positions || !normals || !materials)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: an input is NULL");
+    if (!out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: history_out is NULL");
+    if (width == 0 || height == 0 || width > wptdn::SIDE_MAX || height > wptdn::SIDE_MAX)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: width and height must lie in 1 .. " + std::to_string(uint32_t(wptdn::SIDE_MAX)));
+    if (!pixelOffsets != !cameraOffsets)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: the two offset arrays must both be given or both be NULL");
+    const size_t pixels = size_t(width) * height, historyBytes = pixels * WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL;
+    if (prev && overlaps(out, historyBytes, prev, historyBytes))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: history_out is or overlaps history_prev (nothing works in place)");
+    if (lengthOut && (overlaps(lengthOut, pixels * 4, out, historyBytes) || (prev && overlaps(lengthOut, pixels * 4, prev, historyBytes))))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: length_out overlaps a history");
+    const wpt_temporal_params defaults = { 32.0f, 0.9f, 0.02f, 0u };
+    const wpt_temporal_params& p = params ? *params : defaults;
+    if (!(std::isfinite(p.max_history) && p.max_history >= 1.0f))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: max_history must be finite and at least 1");
+    if (!(p.normal_cos_min >= -1.0f && p.normal_cos_min <= 1.0f))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: normal_cos_min must lie in -1 .. 1");
+    if (!(std::isfinite(p.position_tolerance) && p.position_tolerance >= 0.0f))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: position_tolerance must be finite and not negative");
+    if (p.reserved != 0)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "temporal accumulation: reserved must be 0");
+    rule.maxHistory = p.max_history;
+    rule.normalCosMin = p.normal_cos_min;
+    rule.tolerance2 = p.position_tolerance * p.position_tolerance;
+    return WPT_OK;
+}
+
+/* what a denoiser call on a history is refused for, on the device or on the host */
+static wpt_status denoiseHistoryCheck(const void* history, uint32_t width, uint32_t height, const wpt_denoise_params* params, const void* out,
+        const void* variance, wptdn::Params& filter, uint32_t& iterations)
+{
+    if (!history)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the history is NULL");
+    if (!out)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame is NULL");
+    WPT_TRY(denoiseParamsCheck(width, height, params, filter, iterations));
+    const size_t pixels = size_t(width) * height, historyBytes = pixels * WPT_TEMPORAL_HISTORY_BYTES_PER_PIXEL;
+    if (overlaps(out, pixels * 12, history, historyBytes) || (variance && overlaps(out, pixels * 12, variance, pixels * 4)))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the output frame aliases another array of the call");
+    if (variance && overlaps(variance, pixels * 4, history, historyBytes))
+        return fail(WPT_ERR_INVALID_ARGUMENT, "denoise: the variance plane aliases another array of the call");
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_temporal_accumulate(const float* frame_device, const float* moments_device, const uint16_t* samples_sqrt_device,
+        const float* positions_device, const float* normals_device, const int32_t* materials_device,
+        const float* pixel_offset_to_prev_device, const float* camera_offset_to_prev_device, const void* history_prev_device,
+        uint32_t width, uint32_t height, const wpt_temporal_params* params, void* history_out_device, float* length_out_device,
+        void* hip_stream)
+{
+    wpttm::Params rule;
+    WPT_TRY(temporalCheck(frame_device, moments_device, samples_sqrt_device, positions_device, normals_device, materials_device,
+            pixel_offset_to_prev_device, camera_offset_to_prev_device, history_prev_device, width, height, params, history_out_device,
+            length_out_device, rule));
+    return hipStatus("temporal accumulation", wptk::launchTemporalAccumulate(frame_device, moments_device, samples_sqrt_device, positions_device,
+            normals_device, materials_device, pixel_offset_to_prev_device, camera_offset_to_prev_device,
+            static_cast<const wptdn::Rec*>(history_prev_device), width, height, rule, static_cast<wptdn::Rec*>(history_out_device),
+            length_out_device, static_cast<hipStream_t>(hip_stream)));
+}
+
+wpt_status wpt_postproc_temporal_accumulate_host(const float* frame_host, const float* moments_host, const uint16_t* samples_sqrt_host,
+        const float* positions_host, const float* normals_host, const int32_t* materials_host, const float* pixel_offset_to_prev_host,
+        const float* camera_offset_to_prev_host, const void* history_prev_host, uint32_t width, uint32_t height,
+        const wpt_temporal_params* params, void* history_out_host, float* length_out_host)
+{
+    wpttm::Params rule;
+    WPT_TRY(temporalCheck(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, pixel_offset_to_prev_host,
+            camera_offset_to_prev_host, history_prev_host, width, height, params, history_out_host, length_out_host, rule));
+    wpttm::accumulateHost(frame_host, moments_host, samples_sqrt_host, positions_host, normals_host, materials_host, pixel_offset_to_prev_host,
+            camera_offset_to_prev_host, static_cast<const wptdn::Rec*>(history_prev_host), width, height, rule,
+            static_cast<wptdn::Rec*>(history_out_host), length_out_host);
+    return WPT_OK;
+}
+
+wpt_status wpt_postproc_denoise_history(const void* history_device, uint32_t width, uint32_t height, const wpt_denoise_params* params,
+        float* out_device, float* variance_device, void* hip_stream)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseHistoryCheck(history_device, width, height, params, out_device, variance_device, filter, iterations));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    StreamScratch owner(stream);
+    wptdn::Rec* scratch = nullptr;
+    if (iterations > 0)
+        WPT_TRY(hipStatus("denoise", owner.get(size_t(width) * height * 2, &scratch)));
+    return hipStatus("denoise", wptk::launchDenoiseHistory(static_cast<const wptdn::Rec*>(history_device), width, height, filter, iterations,
+            scratch, out_device, variance_device, stream));
+}
+
+wpt_status wpt_postproc_denoise_history_host(const void* history_host, uint32_t width, uint32_t height, const wpt_denoise_params* params,
+        float* out_host, float* variance_host)
+{
+    wptdn::Params filter;
+    uint32_t iterations;
+    WPT_TRY(denoiseHistoryCheck(history_host, width, height, params, out_host, variance_host, filter, iterations));
+    std::vector<wptdn::Rec> scratch(iterations > 0 ? size_t(width) * height * 2 : 0);
+    wpttm::denoiseHistoryHost(static_cast<const wptdn::Rec*>(history_host), width, height, filter, iterations, scratch.data(), out_host,
+            variance_host);
     return WPT_OK;
 }
 

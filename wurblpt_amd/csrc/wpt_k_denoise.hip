@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "wpt_denoise_launch.h"
+#include "wpt_temporal_launch.h"
 
 /* the largest step that takes the tile form; 0: none.  At most 2: the tile of step 4 would need 72 KB.  (A second build with
  * EXTRA=-DWPT_DENOISE_LDS_MAX_STEP=... is how tools/denoise_rate.py measures one form against the other.) */
@@ -220,6 +221,30 @@ hipError_t launchDenoiseDemodulated(const float* frame, const float* moments, co
             emission, albedoFloor, pixels, a, b, from);
     from = launchIterations(a, b, from, scratch + 3 * pixels, width, height, params, iterations, stream);
     hipLaunchKernelGGL(denoise_unpack_demodulated, perPixel, dim3(PB), 0, stream, from, albedo, emission, albedoFloor, pixels, out, variance);
+    return hipGetLastError();
+}
+
+/* the filter on a history (wpt_temporal.h): the guides and the first iteration's colours are the history's planes, which no
+ * iteration writes; no pack */
+hipError_t launchDenoiseHistory(const wptdn::Rec* history, uint32_t width, uint32_t height, const wptdn::Params& params, uint32_t iterations,
+        wptdn::Rec* scratch, float* out, float* variance, hipStream_t stream)
+{
+    const size_t pixels = size_t(width) * height;
+    const Rec* a = history;
+    const Rec* b = history + pixels;
+    const Rec* from = history + 2 * pixels;
+    const dim3 tiles((width + TILE_W - 1) / TILE_W, (height + TILE_H - 1) / TILE_H);
+    for (uint32_t i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        Rec* to = scratch + (i & 1u) * pixels;
+        if (ldsFormForStep(step))
+            hipLaunchKernelGGL(denoise_iterate_tile, tiles, dim3(TILE_W, TILE_H), 0, stream, a, b, from, to, int(width), int(height), step, params);
+        else
+            hipLaunchKernelGGL(denoise_iterate_gather, tiles, dim3(TILE_W, TILE_H), 0, stream, a, b, from, to, int(width), int(height), step, params);
+        from = to;
+    }
+    const dim3 perPixel((uint32_t)((pixels + PB - 1) / PB));
+    hipLaunchKernelGGL(denoise_unpack, perPixel, dim3(PB), 0, stream, from, pixels, out, variance);
     return hipGetLastError();
 }
 

@@ -272,10 +272,10 @@ def denoise_form(step):
     return lib().wpt_postproc_denoise_form(int(step)).decode()
 
 
-def _denoise_args(frame, moments, samples_sqrt, guide, colours, params, variance_out, stream):
-    """What denoise (colours = ()) and denoise_demodulated (colours = (albedo, emission)) hand to the library: the checked input
-    tensors in the order of the C parameters (the map as 16-bit words among them), w, h, the parameters, the new output tensors
-    and the launch stream, ordered behind the work on torch's current stream."""
+def _denoise_inputs(frame, moments, samples_sqrt, guide, colours, stream):
+    """The input side of a denoiser call, shared with temporal_accumulate: the checked input tensors in the order of the C
+    parameters (the map as 16-bit words among them), w, h and the launch stream, ordered behind the work on torch's current
+    stream.  Nothing is allocated but the map's 16-bit copy, where one is needed."""
     import numpy as np
     import torch
     h, w = int(frame.shape[0]), int(frame.shape[1])
@@ -293,14 +293,30 @@ def _denoise_args(frame, moments, samples_sqrt, guide, colours, params, variance
     current = torch.cuda.current_stream()
     launch = stream if stream is not None else current
     m16 = _map_u16_device(samples_sqrt)
-    out = torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
-    variance = torch.empty((h, w), dtype=torch.float32, device=frame.device) if variance_out else None
     if launch != current:
         launch.wait_stream(current)
-        for t in (m16, out, variance):
+        m16.record_stream(launch)
+    return (frame, moments, m16, P, n, m) + tuple(colours), w, h, launch
+
+
+def _launch_outputs(launch, *tensors):
+    """new output tensors of a launch on a stream that is not torch's current one: theirs to keep until that stream has passed"""
+    import torch
+    if launch != torch.cuda.current_stream():
+        for t in tensors:
             if t is not None:
                 t.record_stream(launch)
-    return (frame, moments, m16, P, n, m) + tuple(colours), w, h, params if params is not None else _abi.DenoiseParams(), out, variance, launch
+
+
+def _denoise_args(frame, moments, samples_sqrt, guide, colours, params, variance_out, stream):
+    """What denoise (colours = ()) and denoise_demodulated (colours = (albedo, emission)) hand to the library: _denoise_inputs,
+    the parameters and the new output tensors."""
+    import torch
+    inputs, w, h, launch = _denoise_inputs(frame, moments, samples_sqrt, guide, colours, stream)
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
+    variance = torch.empty((h, w), dtype=torch.float32, device=frame.device) if variance_out else None
+    _launch_outputs(launch, out, variance)
+    return inputs, w, h, params if params is not None else _abi.DenoiseParams(), out, variance, launch
 
 
 def _denoise_host_args(frame, moments, samples_sqrt, guide, colours, params, variance_out):
@@ -363,6 +379,102 @@ def denoise_demodulated_host(frame, moments, samples_sqrt, guide, albedo=None, e
     inputs, w, h, p, out, variance = _denoise_host_args(frame, moments, samples_sqrt, guide, colours, params, variance_out)
     _check(lib().wpt_postproc_denoise_demodulated_host(*[_array_ptr(a) for a in inputs], w, h, C.byref(p), float(albedo_floor),
                                                        _array_ptr(out), _array_ptr(variance)))
+    return (out, variance) if variance_out else out
+
+
+MOTION_NAMES = ("pixel_space_offset_to_prev", "camera_space_offset_to_prev")  # the ground truth arrays temporal accumulation follows
+
+
+def temporal_params(max_history=32.0, normal_cos_min=0.9, position_tolerance=0.02):
+    """wpt_temporal_params with the header's defaults"""
+    return _abi.TemporalParams(max_history, normal_cos_min, position_tolerance)
+
+
+def _motion(motion):
+    """(pixel offsets, camera offsets) of a temporal call: a dict with MOTION_NAMES (as ground_truth / ground_truth_device return
+    it), the two arrays, or None for a scene and a camera at rest"""
+    if motion is None:
+        return None, None
+    if isinstance(motion, dict):
+        return tuple(motion[name] for name in MOTION_NAMES)
+    pixel, camera = motion
+    return pixel, camera
+
+
+def temporal_accumulate(frame, moments, samples_sqrt, guide, motion=None, history=None, params=None, length_out=False, stream=None):
+    """wpt_postproc_temporal_accumulate: the current frame and the previous history into a new history (include/wurblpt_hip.h has
+    the rule and the layout) on CUDA tensors.  `frame`, `moments`, `samples_sqrt`, `guide`: as for denoise(), the dicts of
+    ground_truth_device and first_hit_colours_device included; `motion`: a dict with MOTION_NAMES (float32 [h, w, 2] and
+    [h, w, 3]) or None for a scene and a camera at rest; `history`: the previous call's result, None for the first frame (it is
+    read, never written); `params`: temporal_params() (None: the defaults).  Asynchronous on `stream` (None: torch's current
+    stream), ordered behind the work on the current stream; as with denoise(), the caller keeps the inputs -- `history` and the
+    offsets among them -- alive and unchanged until that stream has passed the call.  Returns the new history, a float32 tensor
+    [3, h, w, 4], and with length_out the history length per pixel [h, w] as well."""
+    import torch
+    inputs, w, h, launch = _denoise_inputs(frame, moments, samples_sqrt, guide, (), stream)
+    pixel, camera = _motion(motion)
+    for t, comps, what in ((pixel, 2, MOTION_NAMES[0]), (camera, 3, MOTION_NAMES[1])):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, comps)), \
+            "temporal_accumulate: %s must be CUDA float32 [h, w, %d]" % (what, comps)
+    assert history is None or (history.is_cuda and history.is_contiguous() and history.dtype == torch.float32
+                               and tuple(history.shape) == (3, h, w, 4)), "temporal_accumulate: the history must be CUDA float32 [3, h, w, 4]"
+    out = torch.empty((3, h, w, 4), dtype=torch.float32, device=frame.device)
+    length = torch.empty((h, w), dtype=torch.float32, device=frame.device) if length_out else None
+    _launch_outputs(launch, out, length)
+    p = params if params is not None else _abi.TemporalParams()
+    _check(lib().wpt_postproc_temporal_accumulate(*[_tensor_ptr(t) for t in inputs], _tensor_ptr(pixel), _tensor_ptr(camera), _tensor_ptr(history),
+                                                  w, h, C.byref(p), _tensor_ptr(out), _tensor_ptr(length), _stream_ptr(launch)))
+    return (out, length) if length_out else out
+
+
+def temporal_accumulate_host(frame, moments, samples_sqrt, guide, motion=None, history=None, params=None, length_out=False):
+    """wpt_postproc_temporal_accumulate_host: the same of numpy arrays on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    inputs, w, h, _, _, _ = _denoise_host_args(frame, moments, samples_sqrt, guide, (), None, False)
+    pixel, camera = (None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in _motion(motion))
+    assert (pixel is None or pixel.shape == (h, w, 2)) and (camera is None or camera.shape == (h, w, 3)), "temporal_accumulate: offsets [h, w, 2] and [h, w, 3]"
+    if history is not None:
+        history = np.ascontiguousarray(history, dtype=np.float32)
+        assert history.shape == (3, h, w, 4), "temporal_accumulate: the history must be [3, h, w, 4]"
+    out = np.zeros((3, h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32) if length_out else None
+    p = params if params is not None else _abi.TemporalParams()
+    _check(lib().wpt_postproc_temporal_accumulate_host(*[_array_ptr(a) for a in inputs], _array_ptr(pixel), _array_ptr(camera), _array_ptr(history),
+                                                       w, h, C.byref(p), _array_ptr(out), _array_ptr(length)))
+    return (out, length) if length_out else out
+
+
+def denoise_history(history, params=None, variance_out=False, stream=None):
+    """wpt_postproc_denoise_history: denoise()'s iterations on a history of temporal_accumulate (CUDA float32 [3, h, w, 4]), which
+    is not written.  `params`: _abi.DenoiseParams (None: the defaults); iterations=0 returns the accumulated frame and its
+    variance.  Asynchronous on `stream` as denoise() is.  Returns the frame [h, w, 3], and with variance_out the variance of its
+    luminance [h, w] as well."""
+    import torch
+    assert history.is_cuda and history.is_contiguous() and history.dtype == torch.float32 and history.dim() == 4 \
+        and history.shape[0] == 3 and history.shape[3] == 4, "denoise_history: the history must be CUDA float32 [3, h, w, 4]"
+    h, w = int(history.shape[1]), int(history.shape[2])
+    current = torch.cuda.current_stream()
+    launch = stream if stream is not None else current
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=history.device)
+    variance = torch.empty((h, w), dtype=torch.float32, device=history.device) if variance_out else None
+    if launch != current:
+        launch.wait_stream(current)
+    _launch_outputs(launch, out, variance)
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise_history(_tensor_ptr(history), w, h, C.byref(p), _tensor_ptr(out), _tensor_ptr(variance), _stream_ptr(launch)))
+    return (out, variance) if variance_out else out
+
+
+def denoise_history_host(history, params=None, variance_out=False):
+    """wpt_postproc_denoise_history_host: the same of a numpy history on the CPU, bit for bit; needs no device"""
+    import numpy as np
+    history = np.ascontiguousarray(history, dtype=np.float32)
+    assert history.ndim == 4 and history.shape[0] == 3 and history.shape[3] == 4, "denoise_history: the history must be [3, h, w, 4]"
+    h, w = history.shape[1:3]
+    out = np.zeros((h, w, 3), np.float32)
+    variance = np.zeros((h, w), np.float32) if variance_out else None
+    p = params if params is not None else _abi.DenoiseParams()
+    _check(lib().wpt_postproc_denoise_history_host(_array_ptr(history), w, h, C.byref(p), _array_ptr(out), _array_ptr(variance)))
     return (out, variance) if variance_out else out
 
 
