@@ -974,7 +974,11 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
  *                           by default such a launch runs as one workgroup of 1024 lanes per compute unit with the node array
  *                           in LDS once per sign octant of a ray's direction, so that a box test sorts no slab distances --
  *                           where no box of the tree has a NaN bound or lo > hi and the copies fit the unit's 160 KiB:
- *                           wpt_kernel_workgroup) */
+ *                           wpt_kernel_workgroup)
+ *   WPT_WALK_HIT_DATA_IN_HBM  launches in that form of 1024 lanes fetch a hit's data from global memory like every other kernel
+ *                           (A/B runs and tests; by default they keep, behind the node copies and as far as a compute unit's
+ *                           LDS has room, a record per triangle with its shading attributes, the hot spots and the instances'
+ *                           normal matrices: wpt_kernel_hit_data) */
 #define WPT_WALK_WIDE 1u
 #define WPT_WALK_FULL_SHADOW 2u
 #define WPT_WALK_COUNT_PRODUCT 4u
@@ -983,6 +987,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes);
 #define WPT_WALK_NO_FOLD 32u
 #define WPT_WALK_NO_BYPASS 64u
 #define WPT_WALK_SMALL_WORKGROUPS 128u
+#define WPT_WALK_HIT_DATA_IN_HBM 256u
 wpt_status wpt_set_walk(uint32_t flags);
 /* Nodes whose link the kernels with the scene in LDS fold in their copy of the tree: inner nodes that go past one or more inner
  * first children with their own box.
@@ -1070,6 +1075,16 @@ const char* wpt_kernel_form(void);
  * copies, else 0.  wpt_kernel_name, wpt_kernel_form and wpt_kernel_choice do not tell the two apart: the large form is a
  * decision of the launch on top of that choice. */
 uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes);
+/* What of a hit's data the path-tracing kernel of the most recent render call read from LDS instead of global memory: a sum of
+ * WPT_HIT_DATA_RECORDS (per triangle the shading attributes and the instance, material and flag words), WPT_HIT_DATA_HOTSPOTS
+ * (the hot spots with their faces) and WPT_HIT_DATA_NORMALS (the normal matrices of the instances that transformed triangles
+ * name).  The large form of 1024 lanes is built for all three, for the first two and for none, and a launch runs the largest of
+ * these whose parts fit in front of its paths' words; 0 for every other kernel and under WPT_WALK_HIT_DATA_IN_HBM.  The frame is
+ * the same bit for bit either way. */
+#define WPT_HIT_DATA_RECORDS 1u
+#define WPT_HIT_DATA_HOTSPOTS 2u
+#define WPT_HIT_DATA_NORMALS 4u
+uint32_t wpt_kernel_hit_data(void);
 /* Which instantiation of the single kernel renders a launch, from the facts the library decides by: a pure function that needs
  * no device (tests).  need: the feature bits of the scene and the launch's cameras (wpt_device.h, FEAT_*; FEAT_ANIM for a moving
  * scene, a moving camera or an exposure interval); sensor: 0 one frame, 1 transient film, 2 batch of views, 3 adaptive sampling,

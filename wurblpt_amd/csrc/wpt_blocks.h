@@ -351,9 +351,21 @@ WPT_D void hotSpotsMeanPdfPair(const SceneView& sv, Tri4 tri4, f3 org, f3 dirA, 
             const f3 orgR = rotated(org, auxKz(h));
             const uint32_t off = rotatedCopyOffset(auxKz(h), sv.triCount);
             float sum = 0.0f;
+            /* (the large form with the hot spots in LDS: the light's triangle and its face from there, at a wave-uniform place) */
+            [[maybe_unused]] const bool inLds = hitDataInLds(tri4, HIT_DATA_HOTSPOTS);
             for (uint32_t i = 0; i < sv.hotspotCount; i++) {
-                const uint32_t p = off + 3 * sv.hotspots[i].prim;
-                sum += hotSpotPdfValueRotated(tri4(p), tri4(p + 1), tri4(p + 2), orgR, dir, h, sv.hotspotFace[i]);
+                if constexpr (HasLdsHitData<Tri4>::value) {
+                    if (inLds) {
+                        const uint32_t p = off + 3 * __float_as_uint(tri4.hotspot(i, 1).x);
+                        sum += hotSpotPdfValueRotated(tri4(p), tri4(p + 1), tri4(p + 2), orgR, dir, h, tri4.hotspot(i, 0));
+                    } else {
+                        const uint32_t p = off + 3 * sv.hotspots[i].prim;
+                        sum += hotSpotPdfValueRotated(tri4(p), tri4(p + 1), tri4(p + 2), orgR, dir, h, sv.hotspotFace[i]);
+                    }
+                } else {
+                    const uint32_t p = off + 3 * sv.hotspots[i].prim;
+                    sum += hotSpotPdfValueRotated(tri4(p), tri4(p + 1), tri4(p + 2), orgR, dir, h, sv.hotspotFace[i]);
+                }
             }
             return sum * here(sv.invHotspotCount);
         };
@@ -850,21 +862,47 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
         idx = idx < sv.hotspotCount - 1 ? idx : sv.hotspotCount - 1;
         const wpt_hotspot& hs = sv.hotspots[idx];
         f3 directDir;
-        uint32_t hotSpotPrim = hs.prim;
-        if ((F & FEAT_SPHERES) && hs.kind == WPT_HOTSPOT_SPHERE) {
-            const DirectionDraw draw = sphereDirection(sphereNow<F>(sv, ps, sv.spheres[hs.prim]), h.p, prng);
-            directDir = draw.dir;
-            prng = draw.prng;
-            hotSpotPrim = PRIM_SPHERE | hs.prim;
-        } else {
-            /* HitableTriangle::direction (hitable_triangle.hpp:425-443) */
+        uint32_t hotSpotPrim;
+        if constexpr (HasLdsHitData<Tri4>::value) {
+            /* the large form (triangle lights at rest): the chosen light's record from LDS where the hot spots are there, each
+             * lane its own -- prim transform p0.x p0.y | p0.z p1.x p1.y p1.z | p2.x p2.y p2.z - | M's four columns
+             * (wpt_lds_places.h) -- and HitableTriangle::direction as below */
+            static_assert(!(F & (FEAT_SPHERES | FEAT_ANIM)), "hot spots in LDS: triangle lights at rest");
             const f3 bary = inTriangle(in01x2(prng));
-            f3 p = add(add(scl(bary.x, ld3(hs.p0)), scl(bary.y, ld3(hs.p1))), scl(bary.z, ld3(hs.p2)));
-            if (hs.transform)
-                p = mat4mulPoint(hs.M, p);
-            if ((F & FEAT_ANIM) && hs.animation >= 0)
-                p = animatePoint(animationMatrix(sv, ps, hs.animation), p);
+            f3 p;
+            if (hitDataInLds(tri4, HIT_DATA_HOTSPOTS)) {
+                const float4 q1 = tri4.hotspot(idx, 1), q2 = tri4.hotspot(idx, 2), q3 = tri4.hotspot(idx, 3);
+                hotSpotPrim = __float_as_uint(q1.x);
+                p = add(add(scl(bary.x, mk3(q1.z, q1.w, q2.x)), scl(bary.y, mk3(q2.y, q2.z, q2.w))), scl(bary.z, mk3(q3.x, q3.y, q3.z)));
+                if (__float_as_uint(q1.y)) {
+                    const float4 m0 = tri4.hotspot(idx, 4), m1 = tri4.hotspot(idx, 5), m2 = tri4.hotspot(idx, 6), m3 = tri4.hotspot(idx, 7);
+                    const float M[16] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w };
+                    p = mat4mulPoint(M, p);
+                }
+            } else {
+                hotSpotPrim = hs.prim;
+                p = add(add(scl(bary.x, ld3(hs.p0)), scl(bary.y, ld3(hs.p1))), scl(bary.z, ld3(hs.p2)));
+                if (hs.transform)
+                    p = mat4mulPoint(hs.M, p);
+            }
             directDir = normalize(sub(p, h.p));
+        } else {
+            hotSpotPrim = hs.prim;
+            if ((F & FEAT_SPHERES) && hs.kind == WPT_HOTSPOT_SPHERE) {
+                const DirectionDraw draw = sphereDirection(sphereNow<F>(sv, ps, sv.spheres[hs.prim]), h.p, prng);
+                directDir = draw.dir;
+                prng = draw.prng;
+                hotSpotPrim = PRIM_SPHERE | hs.prim;
+            } else {
+                /* HitableTriangle::direction (hitable_triangle.hpp:425-443) */
+                const f3 bary = inTriangle(in01x2(prng));
+                f3 p = add(add(scl(bary.x, ld3(hs.p0)), scl(bary.y, ld3(hs.p1))), scl(bary.z, ld3(hs.p2)));
+                if (hs.transform)
+                    p = mat4mulPoint(hs.M, p);
+                if ((F & FEAT_ANIM) && hs.animation >= 0)
+                    p = animatePoint(animationMatrix(sv, ps, hs.animation), p);
+                directDir = normalize(sub(p, h.p));
+            }
         }
         section(4);
         float hotSpotsPdf, directPdf;

@@ -33,6 +33,10 @@ std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
 
 /* lanes per workgroup of the most recent render call's path-tracing kernel, bit 31: its boxes were ordered (wpt_kernel_workgroup) */
 std::atomic<uint32_t> g_lastWorkgroup{uint32_t(WG)};
+/* WPT_HIT_DATA_* of the parts the most recent render call's kernel kept in LDS (wpt_kernel_hit_data) */
+std::atomic<uint32_t> g_lastHitData{0};
+static_assert(WPT_HIT_DATA_RECORDS == wptk::HIT_DATA_RECORDS && WPT_HIT_DATA_HOTSPOTS == wptk::HIT_DATA_HOTSPOTS && WPT_HIT_DATA_NORMALS == wptk::HIT_DATA_NORMALS,
+        "wpt_lds_places.h restates the header's names of the parts");
 
 static_assert(wptk::PLAN_WG == uint32_t(WG) && wptk::PLAN_SLICE_SLOT_MAX == wptk::SLICE_SLOT_MASK && wptk::SLICE_UNITS_TARGET <= wptk::SLICE_UNITS_MAX
         && wptk::PLAN_FRAME == wptk::SENSOR_FRAME && wptk::PLAN_VIEWS == wptk::SENSOR_VIEWS && wptk::PLAN_ADAPTIVE == wptk::SENSOR_ADAPTIVE
@@ -65,12 +69,15 @@ void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned 
     g_lastPasses.store(passes, std::memory_order_relaxed);
     g_lastSliceStats.store(sliceStats, std::memory_order_relaxed);
     g_lastWorkgroup.store(uint32_t(WG), std::memory_order_relaxed);
+    g_lastHitData.store(0, std::memory_order_relaxed);
 }
 
-/* ... and, behind recordLaunch, the workgroup of a launch that was not one of WG lanes with the plain node array */
-void recordWorkgroup(uint32_t lanes, bool orderedBoxes)
+/* ... and, behind recordLaunch, the workgroup of a launch that was not one of WG lanes with the plain node array, and the parts
+ * of a hit's data it kept in LDS */
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts)
 {
     g_lastWorkgroup.store(lanes | (orderedBoxes ? 0x80000000u : 0u), std::memory_order_relaxed);
+    g_lastHitData.store(hitDataParts, std::memory_order_relaxed);
 }
 
 /* wpt_kernel_form of a launch: "rotated corners" for that form of the kernel with the scene in LDS -- with ", leaf links from
@@ -183,6 +190,11 @@ uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes)
     return w & 0x7fffffffu;
 }
 
+uint32_t wpt_kernel_hit_data(void)
+{
+    return g_lastHitData.load(std::memory_order_relaxed);
+}
+
 uint32_t wpt_last_render_passes(void)
 {
     return g_lastPasses.load(std::memory_order_relaxed);
@@ -251,7 +263,7 @@ wpt_status wpt_set_top_nodes(uint32_t nodes)
 wpt_status wpt_set_walk(uint32_t flags)
 {
     if (flags & ~(WPT_WALK_WIDE | WPT_WALK_FULL_SHADOW | WPT_WALK_COUNT_PRODUCT | WPT_WALK_TRIANGLES_AS_GIVEN | WPT_WALK_SELECT_CORNERS | WPT_WALK_NO_FOLD | WPT_WALK_NO_BYPASS
-            | WPT_WALK_SMALL_WORKGROUPS))
+            | WPT_WALK_SMALL_WORKGROUPS | WPT_WALK_HIT_DATA_IN_HBM))
         return fail(WPT_ERR_INVALID_ARGUMENT, "unknown walk flag");
     settings.walk = flags;
     return WPT_OK;

@@ -110,6 +110,9 @@ struct wpt_scene {
     /* ... and, where every box of the tree has lo <= hi (no NaN bound either), the node array once per sign octant of a ray's
      * direction for the kernels of 1024 lanes (wpt_scene_layout.h, orderedBoxCopies); else NULL */
     const float4* orderedNodes = nullptr;
+    /* the instances whose normal matrix a triangle with WPT_TRI_TRANSFORM names: 0 .. normalsNamed - 1 (0: no triangle is
+     * transformed), which the kernels of 1024 lanes keep in LDS where there is room (wpt_lds_places.h) */
+    uint32_t normalsNamed = 0;
     uint32_t bypassedNodes = 0; /* wpt_scene_bypassed_nodes */
     uint32_t animationCount;
     std::vector<void*> allocations;
@@ -145,7 +148,7 @@ extern Settings settings;
 /* what the process's most recent render call ran (wpt_capi.hip has the words and their readers), the form's name and the
  * kernel table's row of an instantiation: see their definitions there */
 void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned long long* sliceStats);
-void recordWorkgroup(uint32_t lanes, bool orderedBoxes);
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts);
 const char* kernelForm(bool rotated, uint32_t units = 0, bool leafLinksFromNodes = false);
 wpt_status lookupKernel(uint32_t features, bool count, bool ldsScene, bool wide, const wptk::KernelEntry** entry);
 

@@ -223,9 +223,13 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
     }
     /* the large form of the kernel with rotated corners and of its twin, where the launch can take it (wpt_kernel_table.h) */
     size_t largeLdsBytes = 0;
-    const bool large = wptk::selectLargeForm(choice, settings.walk, scene->orderedNodes != nullptr, args.sv.boxesMayBeNan != 0, scene->nodeCount, &largeLdsBytes);
+    uint32_t hitData = 0; /* ... and what of a hit's data it keeps in LDS behind the node copies (wpt_lds_places.h) */
+    const bool large = wptk::selectLargeForm(choice, settings.walk, scene->orderedNodes != nullptr, args.sv.boxesMayBeNan != 0, scene->nodeCount,
+            { scene->triCount, args.sv.materialCount, scene->normalsNamed, args.sv.hotspotCount }, &largeLdsBytes, &hitData);
     if (large && wptk::LARGE_ORDERED)
         args.sv.rglData = reinterpret_cast<const float*>(scene->orderedNodes); /* (the kernel reads the copies there) */
+    if (large)
+        args.materialsInLds |= hitData;
     const SingleKernel run = large
             ? SingleKernel{ wptk::launchPathtraceLarge<FEAT_BASIC | FEAT_ROTATED>, dim3((args.blockSize + WG_LARGE - 1) / WG_LARGE), largeLdsBytes, stream }
             : SingleKernel{ kernel->launch, dim3((args.blockSize + WG - 1) / WG), choice.sceneLdsBytes, stream };
@@ -243,7 +247,7 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
     recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0, choice.rotated && !scene->leafOneToOne), done ? plan.passes : 1u,
             sliceStats);
     if (large)
-        recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED);
+        recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED, (hitData >> wptk::LDS_HIT_DATA_SHIFT) & 7u);
     return hipGetLastError();
 }
 

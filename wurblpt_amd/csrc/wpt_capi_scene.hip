@@ -275,6 +275,7 @@ wpt_status wpt_scene_upload(const wpt_scene_desc* desc, wpt_scene** out_scene)
         WPT_TRY(uploadArray(s, reinterpret_cast<const float4*>(a.data()), size_t(desc->tri_count) * 6, &view.triAttr));
     }
     WPT_TRY(uploadArray(s, desc->instances, desc->instance_count, &view.instances));
+    s->normalsNamed = wptl::normalsNamed(desc);
     WPT_TRY(uploadArray(s, desc->materials, desc->material_count, &view.materials));
     view.materialCount = desc->material_count;
     {

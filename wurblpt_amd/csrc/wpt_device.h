@@ -26,6 +26,7 @@
 #include "wpt_math.h"
 #include "wpt_triangle.h"
 #include "wpt_anim.h"
+#include "wpt_lds_places.h"
 #include "wpt_rgl.h"
 
 namespace wptd {
@@ -557,6 +558,34 @@ struct TriGeomFromScene {
     const float4* triGeom;
     WPT_D float4 operator()(uint32_t i) const { return triGeom[i]; }
 };
+/* The large form of the rotated kernels (wpt_pathtrace_large) hands the blocks this in Tri4's place: the corners in LDS, like
+ * the other kernels' function, and behind the node copies what of a hit's data the kernel keeps in LDS (wpt_lds_places.h has
+ * the three parts and their records; wpt_pathtrace_body.inc.h fills them).  `scene` is the kernel's own LDS array: every read
+ * here is an LDS instruction.  PARTS, wptk::HIT_DATA_*, belongs to the instantiation: a kernel has no code for the place its
+ * data is not in (with the parts as a word of the launch, both ways to a record's values met in one set of registers, and the
+ * frame lost 0.3 % where it now gains 1.4 %: profiles/hit_data_lds_cornell.txt). */
+template<uint32_t PARTS>
+struct LdsHitData {
+    const float4* scene;                       /* the scene's start in LDS */
+    uint32_t corners;                          /* the first corner record, in quadwords from there, like the three below */
+    uint32_t recordsAt, hotspotsAt, normalsAt;
+    WPT_D float4 operator()(uint32_t i) const { return scene[corners + i]; }
+    static constexpr WPT_D bool has(uint32_t part) { return (PARTS & part) != 0; }
+    WPT_D float4 record(uint32_t prim, uint32_t k) const { return scene[recordsAt + wptk::HIT_RECORD_QUADS * prim + k]; }
+    WPT_D float4 hotspot(uint32_t i, uint32_t k) const { return scene[hotspotsAt + wptk::HIT_HOTSPOT_QUADS * i + k]; }
+    WPT_D float4 normalColumn(uint32_t instance, uint32_t k) const { return scene[normalsAt + wptk::HIT_NORMAL_QUADS * instance + k]; }
+};
+template<class Tri4> struct HasLdsHitData { static constexpr bool value = false; };
+template<uint32_t PARTS> struct HasLdsHitData<LdsHitData<PARTS>> { static constexpr bool value = true; };
+/* is `part` of a hit's data in LDS in this kernel? (known at compile time) */
+template<class Tri4> WPT_D bool hitDataInLds(const Tri4& tri4, uint32_t part)
+{
+    if constexpr (HasLdsHitData<Tri4>::value)
+        return tri4.has(part);
+    else
+        return false;
+}
+
 template<uint32_t F = 0, class Tri4 = TriGeomFromScene>
 WPT_D Hit finishHit(const SceneView& sv, const Candidate& c, f3 org, f3 dir, float time, Tri4 tri4)
 {
@@ -565,8 +594,31 @@ WPT_D Hit finishHit(const SceneView& sv, const Candidate& c, f3 org, f3 dir, flo
     Hit h;
     h.a = c.a;
     h.prim = c.prim;
-    uint32_t instance, flags;
-    if constexpr ((F & FEAT_ROTATED) != 0) {
+    uint32_t instance = 0, flags = 0;
+    float4 a0, a1, a2, a3, a4, a5;
+    /* the large form with the hit records in LDS: the six attribute quadwords and the three words from there (every other
+     * kernel compiles the branches it always had) */
+    [[maybe_unused]] const bool recordInLds = hitDataInLds(tri4, wptk::HIT_DATA_RECORDS);
+    if constexpr (HasLdsHitData<Tri4>::value) {
+        static_assert((F & FEAT_ROTATED) != 0, "the large form: a kernel with rotated corners");
+        if (recordInLds) {
+            a0 = tri4.record(c.prim, 0);
+            a1 = tri4.record(c.prim, 1);
+            a2 = tri4.record(c.prim, 2);
+            a3 = tri4.record(c.prim, 3);
+            a4 = tri4.record(c.prim, 4);
+            a5 = tri4.record(c.prim, 5);
+            const float4 words = tri4.record(c.prim, 6);
+            instance = __float_as_uint(words.x);
+            h.material = __float_as_uint(words.y);
+            flags = __float_as_uint(words.z);
+        } else {
+            const uint32_t* words = reinterpret_cast<const uint32_t*>(sv.triGeom + 3 * (size_t)c.prim);
+            instance = words[3];
+            h.material = words[7];
+            flags = words[11];
+        }
+    } else if constexpr ((F & FEAT_ROTATED) != 0) {
         /* the corner records in LDS carry the leaf pass's words in these places (wpt_leaf_words.h): the three words come from
          * the records in HBM, beside the attributes below */
         (void)tri4;
@@ -586,14 +638,37 @@ WPT_D Hit finishHit(const SceneView& sv, const Candidate& c, f3 org, f3 dir, flo
     const float bx = c.invDet * c.U, by = c.invDet * c.V, bz = c.invDet * c.W;
     h.p = add(org, scl(c.a, dir));
     const float4* at = sv.triAttr + 6 * (size_t)c.prim;
-    const float4 a0 = at[0], a1 = at[1], a2 = at[2], a3 = at[3], a4 = at[4], a5 = at[5];
+    if constexpr (HasLdsHitData<Tri4>::value) {
+        if (!recordInLds)
+            a0 = at[0], a1 = at[1], a2 = at[2], a3 = at[3], a4 = at[4], a5 = at[5];
+    } else {
+        a0 = at[0], a1 = at[1], a2 = at[2], a3 = at[3], a4 = at[4], a5 = at[5];
+    }
     /* 24 floats: n0 n1 n2 (9) tc0 tc1 tc2 (6) t0 t1 t2 (9) */
     const f3 n0 = mk3(a0.x, a0.y, a0.z), n1 = mk3(a0.w, a1.x, a1.y), n2 = mk3(a1.z, a1.w, a2.x);
     f3 nrm = add(add(scl(bx, n0), scl(by, n1)), scl(bz, n2));
     const bool transform = (flags & WPT_TRI_TRANSFORM) != 0;
     const float* N = sv.instances[instance].N;
+    /* the large form with the normal matrices in LDS: a transformed triangle's three columns from there */
+    [[maybe_unused]] const bool normalInLds = hitDataInLds(tri4, wptk::HIT_DATA_NORMALS);
+    [[maybe_unused]] float ldsN[9] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if constexpr (HasLdsHitData<Tri4>::value) {
+        if (normalInLds && transform) {
+            const float4 c0 = tri4.normalColumn(instance, 0), c1 = tri4.normalColumn(instance, 1), c2 = tri4.normalColumn(instance, 2);
+            ldsN[0] = c0.x; ldsN[1] = c0.y; ldsN[2] = c0.z;
+            ldsN[3] = c1.x; ldsN[4] = c1.y; ldsN[5] = c1.z;
+            ldsN[6] = c2.x; ldsN[7] = c2.y; ldsN[8] = c2.z;
+        }
+    }
+    auto normalMatrixTimes = [&](f3 v) {
+        if constexpr (HasLdsHitData<Tri4>::value) {
+            if (normalInLds)
+                return mat3mul(ldsN, v);
+        }
+        return mat3mul(N, v);
+    };
     if (transform)
-        nrm = mat3mul(N, nrm);
+        nrm = normalMatrixTimes(nrm);
     float animationN[9];
     const bool animate = (F & FEAT_ANIM) && (flags & WPT_TRI_ANIMATE);
     if (animate) { /* hitable_triangle.hpp:213,296-297 */
@@ -618,7 +693,7 @@ WPT_D Hit finishHit(const SceneView& sv, const Candidate& c, f3 org, f3 dir, flo
         tan = add(add(scl(bx, t0), scl(by, t1)), scl(bz, t2));
         if (dot(tan, tan) > 0.0f) {
             if (transform)
-                tan = mat3mul(N, tan);
+                tan = normalMatrixTimes(tan);
             if (animate)
                 tan = mat3mul(animationN, tan);
             tan = normalize(sub(tan, scl(dot(nrm, tan), nrm)));

@@ -183,8 +183,17 @@ inline KernelChoice selectKernel(const KernelFacts& f)
  * launch of the kernel with rotated corners runs as one workgroup of WG_LARGE lanes per compute unit, with the node array once
  * per sign octant behind the scene, where the scene has those copies (every box of its tree has lo <= hi: hasOrderedCopies), no
  * bound is NaN, the request fits what one workgroup may declare, and wpt_set_walk(WPT_WALK_SMALL_WORKGROUPS) does not keep the
- * workgroups of WG lanes.  *sceneLdsBytes: the large launcher's. */
-inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrderedCopies, bool boxesMayBeNan, uint32_t nodeCount, size_t* sceneLdsBytes)
+ * workgroups of WG lanes.  Behind the node copies such a launch keeps what of a hit's data still fits in front of the cold words
+ * (wpt_lds_places.h, hitDataPlaces and hitDataKernelParts; wpt_set_walk(WPT_WALK_HIT_DATA_IN_HBM): nothing of it); that never
+ * decides the form.
+ * counts: the scene's triangles, the instances its transformed triangles name (wpt_scene::normalsNamed) and its hot spots.
+ * *sceneLdsBytes: the large launcher's; *hitData: what the launch adds to KernelArgs::materialsInLds, the parts in LDS and with
+ * the normal matrices their number. */
+struct HitDataCounts {
+    uint32_t triCount, materialCount, instanceCount, hotspotCount;
+};
+inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrderedCopies, bool boxesMayBeNan, uint32_t nodeCount, const HitDataCounts& counts,
+        size_t* sceneLdsBytes, uint32_t* hitData)
 {
     size_t bytes = c.sceneLdsBytes;
     if (LARGE_ORDERED) {
@@ -192,9 +201,22 @@ inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrdere
         const uint32_t nodeQuads = 2 * nodeCount + 2;
         bytes = size_t(orderedPlaces(nodeQuads, uint32_t(c.sceneLdsBytes / 16) - nodeQuads, base, stride)) * 16;
     }
-    *sceneLdsBytes = bytes;
-    return c.rotated && c.ldsScene && c.features == (FEAT_BASIC | FEAT_ROTATED) && !(walk & WPT_WALK_SMALL_WORKGROUPS) && hasOrderedCopies
+    const bool large = c.rotated && c.ldsScene && c.features == (FEAT_BASIC | FEAT_ROTATED) && !(walk & WPT_WALK_SMALL_WORKGROUPS) && hasOrderedCopies
             && !boxesMayBeNan && COLD_BYTES_LARGE + bytes <= LDS_BYTES_PER_CU;
+    *hitData = 0;
+    if (large && !(walk & WPT_WALK_HIT_DATA_IN_HBM)) {
+        const HitDataPlaces places = hitDataPlaces(nodeCount, counts.triCount, (c.materialsInLds & LDS_MATERIALS) ? counts.materialCount : 0u,
+                counts.instanceCount, counts.hotspotCount, LARGE_ORDERED);
+        /* (the function's own count of the scene in front of the parts is the launcher's: otherwise the parts stay out) */
+        const uint32_t parts = hitDataKernelParts(places.parts); /* the kernels exist for three sets of parts */
+        if (parts && size_t(places.nodeCopiesEnd) * 16 == bytes) {
+            const uint32_t end = (parts & HIT_DATA_NORMALS) ? places.quads : places.normalsAt;
+            bytes = size_t(end) * 16;
+            *hitData = (parts << LDS_HIT_DATA_SHIFT) | ((parts & HIT_DATA_NORMALS) ? counts.instanceCount << LDS_HIT_NORMALS_SHIFT : 0u);
+        }
+    }
+    *sceneLdsBytes = bytes;
+    return large;
 }
 
 } /* namespace wptk */

@@ -48,6 +48,7 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_blocks.h"
+#include "wpt_lds_places.h"
 
 namespace wptk {
 
@@ -60,20 +61,8 @@ constexpr int WG = 256; /* threads per workgroup: 4 waves, one per SIMD */
 constexpr int WG_LARGE = 1024;
 constexpr uint32_t LDS_BYTES_PER_CU = 160 * 1024; /* what one workgroup may declare */
 constexpr uint32_t COLD_AT_LARGE = 32 * 1024;       /* the large form's cold path words: the last 128 KiB (wpt_pathtrace_body.inc.h) */
-constexpr uint32_t ORDERED_COPIES = 8;            /* node arrays of the ordered form, one per sign octant */
-/* Where the ordered form's node arrays lie in LDS, in quadwords from copy 0 (host and device).  nodeQuads: a copy with its null
- * node; behind: corners and material records, which follow copy 0.  Copy k >= 1 lies at base + k * stride, behind all that, with
- * base a multiple of 16 quadwords and stride 2 more than one: the eight records of a node then lie 32 bytes apart modulo the 256
- * bytes of the LDS's 64 banks.  Lanes of a wave that stand on one node in different octants so read different banks; with the
- * copies back to back a copy of the Cornell box's tree is 2304 bytes, nine times 256, and they read the same ones (measured:
- * five times the parent's bank conflict cycles).  Returns the quadwords of the whole. */
-__host__ __device__ inline uint32_t orderedPlaces(uint32_t nodeQuads, uint32_t behind, uint32_t& base, uint32_t& stride)
-{
-    const uint32_t used = nodeQuads + behind;
-    stride = ((nodeQuads + 13u) & ~15u) + 2u;
-    base = used > stride ? ((used - stride + 15u) & ~15u) : 0u;
-    return base + ORDERED_COPIES * stride;
-}
+/* (ORDERED_COPIES, orderedPlaces and hitDataPlaces -- the node arrays of the ordered form, one per sign octant, where they lie, and
+ * what of a hit's data follows them: wpt_lds_places.h) */
 /* measurements: a library built with -DWPT_LARGE_PLAIN_STEP has the large form with the one node array and the sorting box
  * test of the small one, which tells what the workgroup's size costs or gains on its own */
 #ifdef WPT_LARGE_PLAIN_STEP
@@ -98,6 +87,10 @@ constexpr uint32_t LDS_BYTES_PER_WORKGROUP_AT_FOUR = 160 * 1024 / 4;
 constexpr uint32_t LDS_MATERIALS = 1u; /* the material records are in LDS too */
 constexpr uint32_t LDS_FOLD = 2u;      /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h) */
 constexpr uint32_t LDS_LEAF_LINKS = 4u; /* ROTATED kernels: a leaf's skip links are those in its triangle's corner records (every triangle has one leaf) */
+/* the large form: the parts of a hit's data that follow the node copies in LDS (wpt_lds_places.h), HIT_DATA_* << LDS_HIT_DATA_SHIFT
+ * -- the launcher picks the instantiation by them -- and in the word's upper half the instances whose normal matrices
+ * HIT_DATA_NORMALS holds */
+constexpr uint32_t LDS_HIT_DATA_SHIFT = 8, LDS_HIT_NORMALS_SHIFT = 16;
 /* ROTATED kernels, the leaf word of the tree's copy in LDS (wpt_leaf_words.h; wpt_capi.hip asserts that they agree):
  * sign bit | the leaf's node index << LEAF_NODE_SHIFT | quadword offset of the triangle's first corner within a copy */
 constexpr uint32_t LEAF_NODE_SHIFT = 16, LEAF_NODE_MAX = 0x7fffu, LEAF_CORNER_MASK = 0xffffu;
@@ -257,11 +250,12 @@ __global__ __launch_bounds__(WG, OCC) void wpt_pathtrace(const KernelArgs args)
 {
     constexpr int WGS = WG;
     constexpr bool ORDERED = false;
+    constexpr uint32_t HIT = 0;
 #include "wpt_pathtrace_body.inc.h"
 }
 
 /* the large form: a product kernel with the scene in LDS and one workgroup of WG_LARGE lanes per compute unit */
-template<uint32_t F, int OCC, bool ORDERED>
+template<uint32_t F, int OCC, bool ORDERED, uint32_t HIT>
 __global__ __launch_bounds__(WG_LARGE, OCC) void wpt_pathtrace_large(const KernelArgs args)
 {
     constexpr int WGS = WG_LARGE;
@@ -328,14 +322,23 @@ void launchPathtrace(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hi
  * sceneLdsBytes: the node array's copies, the corners' three rotations and the material records where they are in LDS. */
 constexpr uint32_t COLD_BYTES_LARGE = TABLE_BYTES + SLOT_COUNT * WG_LARGE * 16;
 static_assert(COLD_AT_LARGE + SLOT_COUNT * WG_LARGE * 16 == LDS_BYTES_PER_CU && TABLE_BYTES <= COLD_AT_LARGE, "the large form's cold words end the unit's LDS");
+static_assert(LARGE_SCENE_ROOM_QUADS * 16 == COLD_AT_LARGE - TABLE_BYTES, "wpt_lds_places.h restates the room between the math tables and the cold words");
 template<uint32_t F>
 void launchPathtraceLarge(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream);
 #define WPT_PATHTRACE_LARGE_LAUNCHER(F, OCC, ORDERED)                                                                          \
     template<> void launchPathtraceLarge<(F)>(const KernelArgs& args, dim3 grid, size_t sceneLdsBytes, hipStream_t stream)     \
     {                                                                                                                          \
         /* (the cold words lie at a fixed place behind the scene's room: the request is the whole unit's, whatever the scene's size) */   \
-        if (COLD_BYTES_LARGE + sceneLdsBytes <= LDS_BYTES_PER_CU)                                                              \
-            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE);         \
+        if (COLD_BYTES_LARGE + sceneLdsBytes > LDS_BYTES_PER_CU)                                                               \
+            return;                                                                                                            \
+        /* one instantiation per set of parts of a hit's data in LDS that a launch may name (hitDataKernelParts) */            \
+        const uint32_t hit = (args.materialsInLds >> LDS_HIT_DATA_SHIFT) & HIT_DATA_ALL;                                       \
+        if (hit == HIT_DATA_ALL)                                                                                               \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_ALL>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else if (hit == (HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS))                                                                \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else                                                                                                                   \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, 0u>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE);     \
     }
 /* wpt_k_adaptive_cost.hip: args.cost[p] = n_p^2 for the block's pixels, the order's measure of an adaptive launch */
 void launchAdaptiveCost(const KernelArgs& args, hipStream_t stream);

@@ -4,7 +4,8 @@
  * compiles to the code it had before there was a second one.  The including kernel names, as template parameters or constants:
  * F, COUNT, LDSSCENE, WIDE; WGS, the lanes of its workgroup; ORDERED (the large form only): the tree lies in LDS once per sign
  * octant with the bounds of the negative axes mirrored, and a ray without RAY_MAY_NAN walks mirrored the same way, so that its
- * box test finds the six slab distances sorted (ldsStep).
+ * box test finds the six slab distances sorted (ldsStep); HIT (the large form only): the parts of a hit's data that lie in LDS
+ * behind the node copies (wpt_lds_places.h).
  */
     static_assert(!ORDERED || ((F & FEAT_ROTATED) && LDSSCENE && WGS == WG_LARGE), "ordered box copies: the large form of the rotated kernels with the scene in LDS");
     static_assert(!WIDE || (!LDSSCENE && !COUNT), "the wide walk: product kernels that fetch the scene from HBM (counting launches walk like the reference)");
@@ -64,6 +65,7 @@
     const wpt_params& par = args.par;
     const uint32_t nodeCount = sv.nodeCount;
     uint32_t orderedBase = 0, orderedStride = 0; /* ORDERED: copy k >= 1 of the node array lies orderedBase + k * orderedStride quadwords behind copy 0 */
+    LdsHitData<HIT> hitData = {}; /* LARGE: the corners and, behind the node copies, the parts HIT of a hit's data in LDS (wpt_device.h) */
 
     if (LDSSCENE) {
         /* nodes (2 x float4 each), the null node, then the triangle positions (3 x float4 each).  The LDS copy of a node has
@@ -92,7 +94,7 @@
              * and y (kz = 1: z, x, y), records of the same shape behind the stored ones (rotatedCopyOffset).  The fourth words
              * of a triangle's three records are what a leaf pass needs beside the corners, made once per scene on the host
              * (wpt_leaf_words.h, behind the link words): its leaf's skip link under the launch's links, the exact one, and the
-             * triangle's index.  (What finishHit reads in their place comes from the records in HBM.) */
+             * triangle's index.  (What finishHit reads in their place comes from the records in HBM, or with HIT from the hit records below.) */
             const uint32_t* const triSkip = reinterpret_cast<const uint32_t*>(sv.wideNodes) + n4 + 4;
             const uint32_t* const triExact = reinterpret_cast<const uint32_t*>(sv.spheres) + n4 + 4;
             for (uint32_t i = threadIdx.x; i < t4; i += WGS) {
@@ -135,6 +137,58 @@
                 ldsScene[orderedBase + k * orderedStride + at] = q;
             }
         }
+        if constexpr (LARGE) {
+            /* behind the node copies, the parts HIT of a hit's data that this instantiation reads from LDS (wpt_lds_places.h has the
+             * records; the host's selectLargeForm asked the same function with the same counts and launches this kernel only
+             * where it says that they fit): gathered from the arrays every other kernel reads, so that the long round finds
+             * there, word for word, what it would fetch from HBM */
+            const uint32_t m = (args.materialsInLds & LDS_MATERIALS) ? sv.materialCount : 0u;
+            const uint32_t normals = args.materialsInLds >> LDS_HIT_NORMALS_SHIFT;
+            const HitDataPlaces places = hitDataPlaces(nodeCount, sv.triCount, m, normals, sv.hotspotCount, ORDERED);
+            hitData.scene = ldsScene;
+            hitData.corners = n4 + 2;
+            hitData.recordsAt = places.recordsAt;
+            hitData.hotspotsAt = places.hotspotsAt;
+            hitData.normalsAt = places.normalsAt;
+            if (HIT & places.parts & HIT_DATA_RECORDS) {
+                for (uint32_t i = threadIdx.x; i < HIT_RECORD_QUADS * sv.triCount; i += WGS) {
+                    const uint32_t tri = i / HIT_RECORD_QUADS, k = i - HIT_RECORD_QUADS * tri;
+                    float4 q;
+                    if (k < 6) {
+                        q = sv.triAttr[6 * tri + k];
+                    } else { /* instance, material, flags: the fourth words of the triangle's three records in HBM */
+                        const float4* g = sv.triGeom + 3 * tri;
+                        q = make_float4(g[0].w, g[1].w, g[2].w, 0.0f);
+                    }
+                    ldsScene[places.recordsAt + i] = q;
+                }
+            }
+            if (HIT & places.parts & HIT_DATA_HOTSPOTS) {
+                for (uint32_t i = threadIdx.x; i < HIT_HOTSPOT_QUADS * sv.hotspotCount; i += WGS) {
+                    const uint32_t spot = i / HIT_HOTSPOT_QUADS, k = i - HIT_HOTSPOT_QUADS * spot;
+                    const wpt_hotspot& hs = sv.hotspots[spot];
+                    float4 q;
+                    if (k == 0)
+                        q = sv.hotspotFace[spot];
+                    else if (k == 1)
+                        q = make_float4(__uint_as_float(hs.prim), __uint_as_float(hs.transform), hs.p0[0], hs.p0[1]);
+                    else if (k == 2)
+                        q = make_float4(hs.p0[2], hs.p1[0], hs.p1[1], hs.p1[2]);
+                    else if (k == 3)
+                        q = make_float4(hs.p2[0], hs.p2[1], hs.p2[2], 0.0f);
+                    else
+                        q = make_float4(hs.M[4 * (k - 4)], hs.M[4 * (k - 4) + 1], hs.M[4 * (k - 4) + 2], hs.M[4 * (k - 4) + 3]);
+                    ldsScene[places.hotspotsAt + i] = q;
+                }
+            }
+            if (HIT & places.parts & HIT_DATA_NORMALS) {
+                for (uint32_t i = threadIdx.x; i < HIT_NORMAL_QUADS * normals; i += WGS) {
+                    const uint32_t instance = i / HIT_NORMAL_QUADS, k = i - HIT_NORMAL_QUADS * instance;
+                    const float* N = sv.instances[instance].N;
+                    ldsScene[places.normalsAt + i] = make_float4(N[3 * k], N[3 * k + 1], N[3 * k + 2], 0.0f);
+                }
+            }
+        }
     }
     __syncthreads();
     auto node4 = [&](uint32_t i) -> float4 {
@@ -149,7 +203,6 @@
         else
             return sv.triGeom[i];
     };
-
     /* LDSSCENE: the node a ray's walk starts at under the launch's links (the root, or what the plan's links make of it), the
      * entry behind the null node's; rays with RAY_MAY_NAN start at the root and keep to the exact words (in sv.spheres' place) at every step */
     uint32_t walkStart = 0;
@@ -706,7 +759,11 @@
             }
             if (state == S_SHADE) { /* tracePath, one path component (wurblpt.hpp:131-252) */
                 realOrigin();
-                afterBlock(blockShade<F, COUNT>(sv, par, tri4, ps, best, lc, cTrav != 0 ? (int)args.waitBelow : 0, args.bins));
+                /* (the large form's blocks find a triangle by hitData, which knows the hit's data in LDS besides the corners) */
+                if constexpr (LARGE)
+                    afterBlock(blockShade<F, COUNT>(sv, par, hitData, ps, best, lc, cTrav != 0 ? (int)args.waitBelow : 0, args.bins));
+                else
+                    afterBlock(blockShade<F, COUNT>(sv, par, tri4, ps, best, lc, cTrav != 0 ? (int)args.waitBelow : 0, args.bins));
             }
             if (COUNT)
                 sched[12] += (unsigned long long)(clock64() - tBlock);
@@ -721,7 +778,10 @@
             sec<COUNT>(lc, SEC_NEE_END_LIGHT, state == S_NEEEND && ps.rayKind == RAY_NEE_LIGHT && best.prim == ps.getW(SLOT_NEE));
             if (state == S_NEEEND) { /* the next-event ray's contribution, then the path continues */
                 realOrigin();
-                afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best, args.bins));
+                if constexpr (LARGE)
+                    afterBlock(blockNeeEnd<F>(sv, par, hitData, ps, best, args.bins));
+                else
+                    afterBlock(blockNeeEnd<F>(sv, par, tri4, ps, best, args.bins));
             }
             if (COUNT)
                 sched[13] += (unsigned long long)(clock64() - tBlock);

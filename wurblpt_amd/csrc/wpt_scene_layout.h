@@ -23,6 +23,7 @@
 
 #include "../../include/wurblpt_hip.h"
 #include "wpt_fold.h"
+#include "wpt_lds_places.h"
 #include "wpt_rgl.h"
 
 namespace wptl {
@@ -424,6 +425,21 @@ inline bool orderedBoxCopies(const uint32_t* nodes, uint32_t nodeCount, std::vec
         }
     out->swap(copies);
     return true;
+}
+
+/* Where those copies lie in a compute unit's LDS, and which parts of a hit's data -- a record per triangle, the hot spots, the
+ * instances' normal matrices -- follow them there in front of the paths' cold words: wptk::orderedPlaces and
+ * wptk::hitDataPlaces of wpt_lds_places.h (included above), pure functions of the scene's counts that the launch and the
+ * kernels both ask.  The instance count they are given is this one: the normal matrix is read for a triangle with
+ * WPT_TRI_TRANSFORM only, so the matrices in LDS are those of instances 0 .. the largest one such a triangle names; 0 where no
+ * triangle is transformed. */
+inline uint32_t normalsNamed(const wpt_scene_desc* desc)
+{
+    uint32_t named = 0;
+    for (uint32_t i = 0; i < desc->tri_count; i++)
+        if ((desc->tri_geom[i].flags & WPT_TRI_TRANSFORM) && desc->tri_geom[i].instance >= named)
+            named = desc->tri_geom[i].instance + 1;
+    return named;
 }
 
 /* The wide form (wpt_pathtrace.inc.h): the binary tree collapsed by one level, eight quadwords per wide node (lo.x lo.y lo.z

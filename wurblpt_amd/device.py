@@ -18,6 +18,8 @@ def lib_path():
 
 WALK_WIDE, WALK_FULL_SHADOW, WALK_COUNT_PRODUCT, WALK_TRIANGLES_AS_GIVEN, WALK_SELECT_CORNERS, WALK_NO_FOLD, WALK_NO_BYPASS = 1, 2, 4, 8, 16, 32, 64  # wpt_set_walk (include/wurblpt_hip.h)
 WALK_SMALL_WORKGROUPS = 128
+WALK_HIT_DATA_IN_HBM = 256
+HIT_DATA_RECORDS, HIT_DATA_HOTSPOTS, HIT_DATA_NORMALS = 1, 2, 4  # wpt_kernel_hit_data
 SLICES_DECLINE_ODD = 0x100  # wpt_set_slices
 
 EXPORTS = list(_abi.FUNCTIONS)  # every function include/wurblpt_hip.h declares (the test hooks are not among them)
@@ -781,6 +783,11 @@ def kernel_workgroup():
     ordered = C.c_uint32()
     lanes = lib().wpt_kernel_workgroup(C.byref(ordered))
     return int(lanes), bool(ordered.value)
+
+
+def kernel_hit_data():
+    """wpt_kernel_hit_data: the parts of a hit's data (HIT_DATA_*) the most recent render call's kernel read from LDS"""
+    return int(lib().wpt_kernel_hit_data())
 
 
 def fold_plan(host_scene, with_words=False):
