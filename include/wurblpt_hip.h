@@ -364,6 +364,54 @@ wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera,
         const wpt_params* params, uint32_t width, uint32_t height, uint32_t samples_sqrt,
         uint32_t block_start, uint32_t block_size, float* block_rgb);
 
+/* ---- rolling shutter ----
+ * The frame's rows are exposed one after the other, as a CMOS sensor reads them out: one row every `row_time`, from the top row
+ * down (from_top = 1) or from the bottom row up (from_top = 0).  For a frame of `height` rows and the pixels of frame row y
+ * (row 0 = bottom, whatever block or band the launch renders):
+ *
+ *     k = from_top ? height - 1 - y : y        the row's place in the readout
+ *     s = (float)k * row_time                  one rounding
+ *     a = t0 + s ;  b = t1 + s                 one rounding each
+ *
+ * and the row is exposed over [a, b] as the plain render exposes the frame over [t0, t1]: row y of the rolling frame is bit for
+ * bit row y of wpt_render_block_device with params.t0 = a, params.t1 = b.  The decision is taken per row on a != b: then every
+ * camera ray draws its time as a + u * (b - a), and a moving camera is taken at that time.  With a == b (instant rows: t0 == t1,
+ * the classic rolling shutter without motion blur) nothing is drawn, the ray's time is a, a camera with animation >= 0 is taken
+ * where its animation has it at a, and a camera without one uses its record.  row_time == 0 is the plain render, kernel and
+ * all; any other row_time takes the moving-scene kernels, never the wavefront form.
+ * Valid: row_time finite and >= 0, from_top 0 or 1, reserved words 0, and the interval of the row read last finite; anything
+ * else is refused with WPT_ERR_INVALID_ARGUMENT.  The readout spans [t0, b(k = height - 1)] (wpt_shutter_span): a scene with
+ * moving triangles must be bounded for that span, not for [t0, t1].
+ * Progressive sessions, the transient / light-group / time-of-flight / adaptive sensors, batches of views and the ground truth
+ * take no shutter. */
+typedef struct wpt_shutter {
+    float row_time;
+    uint32_t from_top;
+    uint32_t reserved[2]; /* 0 */
+} wpt_shutter;
+
+/* Device-free: the interval [*a, *b] of frame row `row` (< height), and the span [*first, *last] of the whole readout, by the
+ * rule above.  An invalid shutter is refused with a message, as the render calls refuse it. */
+wpt_status wpt_shutter_row_interval(const wpt_shutter* shutter, float t0, float t1, uint32_t height, uint32_t row, float* a, float* b);
+wpt_status wpt_shutter_span(const wpt_shutter* shutter, float t0, float t1, uint32_t height, float* first, float* last);
+
+/* wpt_render_block_device, wpt_render_bands_device, wpt_render_bands and wpt_render_block with a shutter (NULL is refused);
+ * every other argument means what it means there. */
+wpt_status wpt_render_shutter_block_device(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const wpt_shutter* shutter, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        uint32_t block_start, uint32_t block_size,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream);
+wpt_status wpt_render_shutter_bands_device(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const wpt_shutter* shutter, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream);
+wpt_status wpt_render_shutter_bands(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_host);
+wpt_status wpt_render_shutter_block(wpt_scene* scene, const wpt_camera* camera,
+        const wpt_params* params, const wpt_shutter* shutter, uint32_t width, uint32_t height, uint32_t samples_sqrt,
+        uint32_t block_start, uint32_t block_size, float* block_rgb);
+
 /* ---- transient film (light-in-flight rendering) ----
  * One launch renders the frame and bin_count planes: plane k holds the light whose optical path length lies in
  * [edges[k], edges[k + 1]), per channel, behind the distance gate of `params` (its path-length gate applies to the frame

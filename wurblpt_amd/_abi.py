@@ -113,6 +113,11 @@ class Params(C.Structure):
                 ("min_path_len", C.c_float), ("max_path_len", C.c_float), ("t0", C.c_float), ("t1", C.c_float)]
 
 
+class Shutter(C.Structure):
+    """wpt_shutter: the rolling shutter of the wpt_render_shutter_* calls"""
+    _fields_ = [("row_time", C.c_float), ("from_top", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class TofSensor(C.Structure):
     """wpt_tof_sensor: the time-of-flight sensor's constants and the phase offsets of the phase images of one launch"""
     _fields_ = [("pixel_area", C.c_float), ("exposure_time", C.c_float), ("contrast", C.c_float), ("frac_modfreq_c", C.c_float),
@@ -162,7 +167,7 @@ PROGRESS_MAGIC, PROGRESS_STATE_VERSION, PROGRESS_HEADER_BYTES, PROGRESS_CARRY_BY
 STRUCT_SIZES = {
     "wpt_bvh_node": (BvhNode, 32), "wpt_tri_geom": (TriGeom, 48), "wpt_tri_attr": (TriAttr, 96),
     "wpt_instance": (Instance, 48), "wpt_sphere": (Sphere, 48), "wpt_hotspot": (Hotspot, 116), "wpt_material": (Material, 128),
-    "wpt_texture": (Texture, 88), "wpt_rgl_warp": (RglWarp, 76), "wpt_rgl_brdf": (RglBrdf, 388), "wpt_camera": (Camera, 140), "wpt_params": (Params, 40),
+    "wpt_texture": (Texture, 88), "wpt_rgl_warp": (RglWarp, 76), "wpt_rgl_brdf": (RglBrdf, 388), "wpt_camera": (Camera, 140), "wpt_params": (Params, 40), "wpt_shutter": (Shutter, 16),
     "wpt_keyframe": (Keyframe, 44), "wpt_animation": (Animation, 8),
     "wpt_counters": (Counters, 48), "wpt_tof_sensor": (TofSensor, 52),
     "wpt_progress_info": (ProgressInfo, 48), "wpt_denoise_params": (DenoiseParams, 16),
@@ -178,6 +183,7 @@ _I, _U, _Q, _F, _P, _S = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p,
 _pU, _pQ, _pP, _pS = C.POINTER(_U), C.POINTER(_Q), C.POINTER(_P), C.POINTER(_S)
 _CAM, _PAR, _TOF, _DEN = C.POINTER(Camera), C.POINTER(Params), C.POINTER(TofSensor), C.POINTER(DenoiseParams)
 _TMP = C.POINTER(TemporalParams)
+_SHU = C.POINTER(Shutter)
 _SCP = [_P, _CAM, _PAR]  # wpt_scene* scene, const wpt_camera* camera, const wpt_params* params
 _WARP = [_P, _U, _U, _U, _CAM, _I, _P]  # wpt_postproc_lens_warp_host, wpt_postproc_distance_to_coords_host
 
@@ -198,6 +204,12 @@ FUNCTIONS = {
     "wpt_render_block": (_I, _SCP + [_U] * 5 + [_P]),
     "wpt_render_bands_device": (_I, [_P] * 3 + [_U] * 6 + [_P] * 3),
     "wpt_render_bands": (_I, [_P] * 3 + [_U] * 6 + [_P]),
+    "wpt_shutter_row_interval": (_I, [_SHU, _F, _F, _U, _U, _P, _P]),
+    "wpt_shutter_span": (_I, [_SHU, _F, _F, _U, _P, _P]),
+    "wpt_render_shutter_block_device": (_I, _SCP + [_SHU] + [_U] * 5 + [_P] * 3),
+    "wpt_render_shutter_bands_device": (_I, _SCP + [_SHU] + [_U] * 6 + [_P] * 3),
+    "wpt_render_shutter_bands": (_I, _SCP + [_SHU] + [_U] * 6 + [_P]),
+    "wpt_render_shutter_block": (_I, _SCP + [_SHU] + [_U] * 5 + [_P]),
     "wpt_render_transient_block_device": (_I, _SCP + [_P] + [_U] * 6 + [_P] * 3),
     "wpt_render_transient_block": (_I, _SCP + [_P] + [_U] * 6 + [_P] * 2),
     "wpt_render_light_groups_block_device": (_I, _SCP + [_P] + [_U] * 8 + [_P] * 3),

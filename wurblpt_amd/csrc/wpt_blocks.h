@@ -26,6 +26,7 @@
 
 #include "wpt_device.h"
 #include "wpt_lens.h"
+#include "wpt_shutter.h"
 #include "wpt_tof.h"
 
 namespace wptk {
@@ -184,6 +185,9 @@ struct FrameArgs {
     uint32_t width, height, samplesSqrt;
     /* 1.0f / (float)width, / height, / samplesSqrt: divided once on the host (IEEE, the same bits) */
     float invWidth, invHeight, invSamplesSqrt;
+    /* FEAT_ANIM: the rolling shutter (wpt_shutter.h).  Whoever fills a FrameArgs field by field and says nothing has none:
+     * ground truth, first hit, the sensors' kernels, the wavefront form. */
+    wptshutter::Rows shutter = { 0.0f, 0u };
 };
 
 /* A uniform value as the compiler must take it where it stands (a scalar register, no instruction).  Values that
@@ -638,6 +642,30 @@ template<class PS> WPT_D int advancePath(const wpt_params& par, PS& ps, f4 nextA
     return NEXT_TRACE;
 }
 
+/* blockNewFrom for a frame with a rolling shutter (wpt_shutter.h): the time and the pose of a camera ray of frame row `row`, from
+ * the ray (O, D) in camera space.  What blockNewFrom does with [t0, t1] is done with the row's [a, b], and the decision is the
+ * lane's: rounding may give two rows of one wave a different answer to a != b.  An instant row (a == b) draws nothing, and a
+ * moving camera is taken where its animation has it at a -- its record holds Camera::at(t0), the pose of the row read first. */
+template<class PS>
+WPT_D void exposeRow(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const SceneView& sv, Prng& prng, uint32_t row, f3 O, f3 D)
+{
+    const wptshutter::Interval iv = wptshutter::rowInterval(fa.shutter, fa.par.t0, fa.par.t1, fa.height, row);
+    float t = iv.a;
+    if (iv.a != iv.b) {
+        t = iv.a + in01(prng) * (iv.b - iv.a);
+        ps.animCached = -1; /* AnimationCache::init(r.time) */
+    }
+    ps.time = t;
+    if (cam.animation >= 0) {
+        const wptanim::Trs T = animationAt(sv, cam.animation, t);
+        ps.o = add(ld3(T.t), quatRotate(T.q, mul(O, ld3(T.s))));
+        ps.d = normalize(quatRotate(T.q, D));
+    } else {
+        ps.o = add(ld3(cam.translation), quatRotate(cam.rotation, mul(O, ld3(cam.scaling))));
+        ps.d = normalize(quatRotate(cam.rotation, D));
+    }
+}
+
 /* wurblpt.hpp:348-360 + Camera::getRay (camera.hpp:123-185), pinhole or thin lens, from camera `cam`.  UNIFORM: `cam` is the
  * same for every lane of the wave (the launch's camera, or the one view a whole wave of a batch is on), and its frustum and
  * pose are taken as scalars (here()); otherwise each lane reads its own camera's words. */
@@ -706,7 +734,10 @@ WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const
         D = sub(P, O);
         O = add(O, mk3(stereoscopicShift, 0.0f, 0.0f));
     }
-    if ((F & FEAT_ANIM) && fa.par.t0 != fa.par.t1) {
+    if ((F & FEAT_ANIM) && fa.shutter.rowTime != 0.0f) {
+        /* a rolling frame: the row's interval in the place of [t0, t1], and the decision per lane */
+        exposeRow(fa, cam, ps, sv, prng, pxy >> 16, O, D);
+    } else if ((F & FEAT_ANIM) && fa.par.t0 != fa.par.t1) {
         /* camera.hpp:175-184: the ray draws its time in the exposure interval; a moving camera is taken at that time */
         const float t = fa.par.t0 + in01(prng) * (fa.par.t1 - fa.par.t0);
         ps.time = t;

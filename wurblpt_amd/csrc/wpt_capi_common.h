@@ -167,6 +167,7 @@ struct LaunchRequest {
     wptk::BinsView bins = {};         /* SENSOR_TRANSIENT, SENSOR_TOF (wpt_blocks.h, accumulate) */
     wptk::ViewsView views = {};       /* SENSOR_VIEWS */
     wptk::AdaptiveView adaptive = {}; /* SENSOR_ADAPTIVE */
+    wptshutter::Rows shutter = { 0.0f, 0u }; /* SENSOR_FRAME: the rolling shutter, checked by the caller (wpt_render_shutter_*); zeros: none */
 };
 
 /* the launch itself and its parts, which a session's stage is made of too (wpt_capi_render.hip) */

@@ -1,5 +1,6 @@
 /*
- * wpt_capi_render.hip -- of include/wurblpt_hip.h: wpt_render_block(_device) and wpt_render_bands(_device), and behind them the
+ * wpt_capi_render.hip -- of include/wurblpt_hip.h: wpt_render_block(_device) and wpt_render_bands(_device), the same four with a
+ * rolling shutter (wpt_render_shutter_*, wpt_shutter_row_interval, wpt_shutter_span; wpt_shutter.h), and behind them the
  * one launch of the path tracer that every sensor and every stage of a session goes through: check, set up, choose the kernel
  * (wpt_kernel_table.h), plan its passes (wpt_launch_plan.h), execute -- the single kernel by the plan's strategy, or the
  * wavefront form (wpt_wavefront.inc.h).  The kernel itself is in wpt_pathtrace.inc.h.
@@ -275,6 +276,12 @@ wpt_status renderLaunch(const LaunchRequest& rq)
         args.adaptive = rq.adaptive;
     else if (planes)
         args.bins = rq.bins;
+    else if (rq.sensor == wptk::SENSOR_FRAME)
+        args.shutter = rq.shutter;
+    /* rows read out at different times are a moving scene's business even where nothing else moves: each ray carries its row's
+     * time.  (A shutter with row_time == 0 is the plain launch, kernel and all.) */
+    if (rq.sensor == wptk::SENSOR_FRAME && rq.shutter.rowTime != 0.0f)
+        need |= FEAT_ANIM;
     args.rowStop = rq.samplesSqrt;
     const wptk::KernelChoice choice = wptk::selectKernel({ need, rq.sensor, count, rq.scene->nodeCount, rq.scene->triCount,
             uint32_t(rq.scene->view.materialCount), rq.scene->view.wideNodes != nullptr, settings.variant, settings.walk });
@@ -308,18 +315,33 @@ wpt_status renderLaunch(const LaunchRequest& rq)
 
 } /* namespace wptc */
 
-extern "C" {
+namespace {
 
-wpt_status wpt_render_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+/* the shutter of a wpt_render_shutter_* call as the launch carries it, checked against the frame's rows and the exposure interval */
+wpt_status shutterOfCall(const wpt_shutter* shutter, const wpt_params* params, uint32_t height, wptshutter::Rows& rows)
+{
+    if (!shutter || !params)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* why = wptshutter::refusal(shutter->row_time, shutter->from_top, shutter->reserved[0], shutter->reserved[1], params->t0, params->t1, height))
+        return fail(WPT_ERR_INVALID_ARGUMENT, why);
+    rows = { shutter->row_time, shutter->from_top };
+    return WPT_OK;
+}
+
+/* a block of consecutive pixels; shutter: NULL for wpt_render_block_device */
+wpt_status blockDevice(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
         float* frame_device, wpt_counters* counters_device, void* hip_stream)
 {
     LaunchRequest rq = { scene, camera, params, width, height, samples_sqrt, block_start, block_size, frame_device, hip_stream };
     rq.counters = counters_device;
+    if (shutter)
+        WPT_TRY(shutterOfCall(shutter, params, height, rq.shutter));
     return renderLaunch(rq);
 }
 
-wpt_status wpt_render_bands_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+/* one rank's interleaved bands in one launch; shutter: NULL for wpt_render_bands_device */
+wpt_status bandsDevice(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
         float* frame_device, wpt_counters* counters_device, void* hip_stream)
 {
@@ -335,10 +357,13 @@ wpt_status wpt_render_bands_device(wpt_scene* scene, const wpt_camera* camera, c
     rq.bandFirst = first_band;
     rq.bandStride = band_stride;
     rq.counters = counters_device;
+    if (shutter)
+        WPT_TRY(shutterOfCall(shutter, params, height, rq.shutter));
     return renderLaunch(rq);
 }
 
-wpt_status wpt_render_bands(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+/* ... and their synchronous forms for host memory */
+wpt_status bandsHost(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
         uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
         float* frame_host)
 {
@@ -346,10 +371,13 @@ wpt_status wpt_render_bands(wpt_scene* scene, const wpt_camera* camera, const wp
         return fail(WPT_ERR_INVALID_ARGUMENT, "frame_host is NULL");
     if (width == 0 || height == 0 || band_rows == 0 || band_stride == 0)
         return fail(WPT_ERR_INVALID_ARGUMENT, "bands need a frame, band_rows > 0 and band_stride > 0");
+    wptshutter::Rows checked;
+    if (shutter) /* (refused before any memory is asked for) */
+        WPT_TRY(shutterOfCall(shutter, params, height, checked));
     StagedBlock frame;
     const size_t rowBytes = size_t(width) * 3 * sizeof(float);
     HIP_TRY(frame.allocate(rowBytes * height));
-    WPT_TRY(wpt_render_bands_device(scene, camera, params, width, height, samples_sqrt, band_rows, first_band, band_stride,
+    WPT_TRY(bandsDevice(scene, camera, params, shutter, width, height, samples_sqrt, band_rows, first_band, band_stride,
             static_cast<float*>(frame.device), nullptr, nullptr));
     WPT_TRY(wpt_scene_check(scene));
     for (uint64_t band = first_band; band * band_rows < height; band += band_stride) {
@@ -361,17 +389,118 @@ wpt_status wpt_render_bands(wpt_scene* scene, const wpt_camera* camera, const wp
     return WPT_OK;
 }
 
-wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width,
+wpt_status blockHost(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter, uint32_t width,
         uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_rgb)
 {
     if (!block_rgb)
         return fail(WPT_ERR_INVALID_ARGUMENT, "block_rgb is NULL");
+    wptshutter::Rows checked;
+    if (shutter) /* (refused before any memory is asked for, and for an empty block too) */
+        WPT_TRY(shutterOfCall(shutter, params, height, checked));
     if (block_size == 0)
         return WPT_OK;
     StagedBlock block;
     HIP_TRY(block.allocatePixels(block_size));
-    return finishStaged(wpt_render_block_device(scene, camera, params, width, height, samples_sqrt, block_start, block_size,
+    return finishStaged(blockDevice(scene, camera, params, shutter, width, height, samples_sqrt, block_start, block_size,
             block.biased(block_start), nullptr, nullptr), scene, block, block_rgb);
+}
+
+const char* const NULL_SHUTTER = "shutter is NULL";
+
+} /* namespace */
+
+extern "C" {
+
+wpt_status wpt_render_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream)
+{
+    return blockDevice(scene, camera, params, nullptr, width, height, samples_sqrt, block_start, block_size, frame_device, counters_device, hip_stream);
+}
+
+wpt_status wpt_render_bands_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream)
+{
+    return bandsDevice(scene, camera, params, nullptr, width, height, samples_sqrt, band_rows, first_band, band_stride, frame_device, counters_device,
+            hip_stream);
+}
+
+wpt_status wpt_render_bands(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_host)
+{
+    return bandsHost(scene, camera, params, nullptr, width, height, samples_sqrt, band_rows, first_band, band_stride, frame_host);
+}
+
+wpt_status wpt_render_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, uint32_t width,
+        uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_rgb)
+{
+    return blockHost(scene, camera, params, nullptr, width, height, samples_sqrt, block_start, block_size, block_rgb);
+}
+
+/* ---- the rolling shutter: the same launches with a row's interval in the place of [t0, t1] (wpt_shutter.h) ---- */
+
+wpt_status wpt_shutter_row_interval(const wpt_shutter* shutter, float t0, float t1, uint32_t height, uint32_t row, float* a, float* b)
+{
+    if (!shutter || !a || !b)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* why = wptshutter::refusal(shutter->row_time, shutter->from_top, shutter->reserved[0], shutter->reserved[1], t0, t1, height))
+        return fail(WPT_ERR_INVALID_ARGUMENT, why);
+    if (row >= height)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "shutter: row lies outside the frame");
+    const wptshutter::Interval iv = wptshutter::rowInterval({ shutter->row_time, shutter->from_top }, t0, t1, height, row);
+    *a = iv.a;
+    *b = iv.b;
+    return WPT_OK;
+}
+
+wpt_status wpt_shutter_span(const wpt_shutter* shutter, float t0, float t1, uint32_t height, float* first, float* last)
+{
+    if (!shutter || !first || !last)
+        return fail(WPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* why = wptshutter::refusal(shutter->row_time, shutter->from_top, shutter->reserved[0], shutter->reserved[1], t0, t1, height))
+        return fail(WPT_ERR_INVALID_ARGUMENT, why);
+    /* the row read first opens at t0, the row read last closes at b(k = height - 1), whichever end of the frame that is */
+    *first = t0;
+    *last = wptshutter::rowInterval({ shutter->row_time, 0u }, t0, t1, height, height - 1u).b;
+    return WPT_OK;
+}
+
+wpt_status wpt_render_shutter_block_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream)
+{
+    if (!shutter)
+        return fail(WPT_ERR_INVALID_ARGUMENT, NULL_SHUTTER);
+    return blockDevice(scene, camera, params, shutter, width, height, samples_sqrt, block_start, block_size, frame_device, counters_device, hip_stream);
+}
+
+wpt_status wpt_render_shutter_bands_device(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_device, wpt_counters* counters_device, void* hip_stream)
+{
+    if (!shutter)
+        return fail(WPT_ERR_INVALID_ARGUMENT, NULL_SHUTTER);
+    return bandsDevice(scene, camera, params, shutter, width, height, samples_sqrt, band_rows, first_band, band_stride, frame_device, counters_device,
+            hip_stream);
+}
+
+wpt_status wpt_render_shutter_bands(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
+        float* frame_host)
+{
+    if (!shutter)
+        return fail(WPT_ERR_INVALID_ARGUMENT, NULL_SHUTTER);
+    return bandsHost(scene, camera, params, shutter, width, height, samples_sqrt, band_rows, first_band, band_stride, frame_host);
+}
+
+wpt_status wpt_render_shutter_block(wpt_scene* scene, const wpt_camera* camera, const wpt_params* params, const wpt_shutter* shutter,
+        uint32_t width, uint32_t height, uint32_t samples_sqrt, uint32_t block_start, uint32_t block_size, float* block_rgb)
+{
+    if (!shutter)
+        return fail(WPT_ERR_INVALID_ARGUMENT, NULL_SHUTTER);
+    return blockHost(scene, camera, params, shutter, width, height, samples_sqrt, block_start, block_size, block_rgb);
 }
 
 } /* extern "C" */

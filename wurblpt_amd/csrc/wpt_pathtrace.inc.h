@@ -179,6 +179,9 @@ struct KernelArgs {
         ViewsView views; /* FEAT_VIEWS kernels: the batch's cameras; frame holds viewCount full frames, blockSize is all their pixels */
         AdaptiveView adaptive; /* FEAT_ADAPTIVE kernels: the sample-count map and the moment film; samplesSqrt above is unused */
         SlicesView slices; /* FEAT_SLICED kernels: the units pixels are handed out in (read only where the launch has a pool) */
+        /* the FEAT_ANIM kernels of one plain frame, which have no member above: the rolling shutter (wpt_shutter.h; zeros, as a
+         * launch's arguments start: none).  Every other kernel renders without one. */
+        wptshutter::Rows shutter;
     };
 };
 /* the adaptive member must not change the union's size or the layout of what follows it: the existing kernels' code objects
@@ -186,6 +189,12 @@ struct KernelArgs {
 static_assert(sizeof(AdaptiveView) <= sizeof(BinsView) && alignof(AdaptiveView) <= alignof(BinsView), "AdaptiveView must fit in BinsView's place");
 static_assert(sizeof(SlicesView) <= sizeof(BinsView) && alignof(SlicesView) <= alignof(BinsView), "SlicesView must fit in BinsView's place");
 static_assert(sizeof(ViewsView) <= sizeof(BinsView) && alignof(ViewsView) <= alignof(BinsView), "ViewsView must fit in BinsView's place");
+static_assert(sizeof(wptshutter::Rows) <= sizeof(BinsView) && alignof(wptshutter::Rows) <= alignof(BinsView), "the shutter must fit in BinsView's place");
+/* the kernels that read KernelArgs::shutter: moving scenes, one plain frame (FEAT_SLICED has no moving-scene kernel) */
+constexpr bool hasShutter(uint32_t F)
+{
+    return (F & FEAT_ANIM) != 0 && (F & (FEAT_TRANSIENT | FEAT_TOF | FEAT_VIEWS | FEAT_ADAPTIVE | FEAT_SLICED)) == 0;
+}
 
 /* lane index of the launch -> pixel; false: no pixel behind this index */
 WPT_D bool lanePixel(const KernelArgs& args, uint32_t gid, uint32_t& pixel)

@@ -227,6 +227,8 @@
     fa.invWidth = args.invWidth;
     fa.invHeight = args.invHeight;
     fa.invSamplesSqrt = args.invSamplesSqrt;
+    if constexpr (hasShutter(F))
+        fa.shutter = args.shutter;
 
     /* ---- per-lane state: the pixel's path (wpt_blocks.h; its cold words in LDS) and the traversal registers ---- */
     std::conditional_t<ADAPTIVE, PathLdsSum<WG>, PathLds<WG>> ps;

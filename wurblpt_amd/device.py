@@ -91,6 +91,24 @@ def _counters_dict(counters):
     return dict(zip(COUNTER_NAMES, [int(x) for x in counters.cpu().tolist()]))
 
 
+def shutter_row_interval(shutter, t0, t1, height, row):
+    """wpt_shutter_row_interval: (a, b) as numpy float32, the exposure interval of frame row `row` (0 = bottom) of a frame of
+    `height` rows exposed over [t0, t1] under host.shutter(...).  No device needed."""
+    import numpy as np
+    a, b = C.c_float(), C.c_float()
+    _check(lib().wpt_shutter_row_interval(C.byref(shutter), float(t0), float(t1), height, row, C.cast(C.pointer(a), C.c_void_p), C.cast(C.pointer(b), C.c_void_p)))
+    return np.float32(a.value), np.float32(b.value)
+
+
+def shutter_span(shutter, t0, t1, height):
+    """wpt_shutter_span: (first, last) as numpy float32, what the whole readout spans: a scene with moving triangles must be
+    bounded for it.  No device needed."""
+    import numpy as np
+    first, last = C.c_float(), C.c_float()
+    _check(lib().wpt_shutter_span(C.byref(shutter), float(t0), float(t1), height, C.cast(C.pointer(first), C.c_void_p), C.cast(C.pointer(last), C.c_void_p)))
+    return np.float32(first.value), np.float32(last.value)
+
+
 def uniform_edges(start, width, count):
     """Edges of `count` bins of one width from `start`: e_k = start + (float)k * width, each operation rounded to float32
     (no fused multiply-add), as SensorRGBTransient computes them.  Raises ValueError when they do not increase."""
@@ -966,6 +984,59 @@ class DeviceScene:
         torch.cuda.synchronize()
         self.check()
         return frame.cpu().numpy(), _counters_dict(counters) if with_counters else None
+
+    def render_shutter_into(self, frame, samples_sqrt, shutter, block=None, params=None, counters=None, stream=None,
+                            width=None, height=None):
+        """render_block_into under a rolling shutter (host.shutter): row r of the frame, whatever the block, is exposed over
+        shutter_row_interval(shutter, params.t0, params.t1, h, r) and is bit for bit that row of the plain render with it."""
+        w, h = _frame_size(self.host, width, height)
+        assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
+        p = _params(params)
+        start, size = block if block is not None else (0, w * h)
+        _check(lib().wpt_render_shutter_block_device(self._handle, self.host.camera, C.byref(p), C.byref(shutter), w, h, samples_sqrt,
+                                                      start, size, C.c_void_p(frame.data_ptr()), _tensor_ptr(counters), _stream_ptr(stream)))
+
+    def render_shutter_bands_into(self, frame, samples_sqrt, shutter, band_rows, first_band, band_stride, params=None, counters=None,
+                                  stream=None, width=None, height=None):
+        """render_bands_into under a rolling shutter; the rows keep the intervals they have in the frame."""
+        w, h = _frame_size(self.host, width, height)
+        assert frame.is_cuda and frame.is_contiguous() and frame.numel() == w * h * 3
+        p = _params(params)
+        _check(lib().wpt_render_shutter_bands_device(self._handle, self.host.camera, C.byref(p), C.byref(shutter), w, h, samples_sqrt,
+                                                     band_rows, first_band, band_stride, C.c_void_p(frame.data_ptr()), _tensor_ptr(counters),
+                                                     _stream_ptr(stream)))
+
+    def render_shutter(self, samples_sqrt, shutter, block=None, params=None, with_counters=False, width=None, height=None):
+        """Synchronous convenience, as render: (frame as numpy [h, w, 3], counters dict or None)."""
+        import torch
+        w, h = _frame_size(self.host, width, height)
+        frame = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        counters = _new_counters(with_counters)
+        self.render_shutter_into(frame, samples_sqrt, shutter, block, params, counters, torch.cuda.current_stream(), w, h)
+        torch.cuda.synchronize()
+        self.check()
+        return frame.cpu().numpy(), _counters_dict(counters) if with_counters else None
+
+    def render_shutter_host(self, samples_sqrt, shutter, block=None, bands=None, params=None, width=None, height=None):
+        """The synchronous forms for host memory.  block = (start, size): wpt_render_shutter_block, the block's pixels as
+        [size, 3]; bands = (band_rows, first_band, band_stride): wpt_render_shutter_bands, the full frame [h, w, 3] with the
+        other bands left at zero."""
+        import numpy as np
+        w, h = _frame_size(self.host, width, height)
+        p = _params(params)
+        if (block is None) == (bands is None):
+            raise ValueError("render_shutter_host: give block or bands")
+        if block is not None:
+            start, size = block
+            out = np.zeros((size, 3), dtype=np.float32)
+            _check(lib().wpt_render_shutter_block(self._handle, self.host.camera, C.byref(p), C.byref(shutter), w, h, samples_sqrt, start, size,
+                                                   C.c_void_p(out.ctypes.data)))
+            return out
+        band_rows, first_band, band_stride = bands
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        _check(lib().wpt_render_shutter_bands(self._handle, self.host.camera, C.byref(p), C.byref(shutter), w, h, samples_sqrt, band_rows,
+                                               first_band, band_stride, C.c_void_p(out.ctypes.data)))
+        return out
 
     def progressive(self, samples_sqrt, block=None, params=None, width=None, height=None, tag=None, sensor=SENSOR_FRAME,
                     with_counters=False, bands=False):

@@ -98,6 +98,15 @@ def default_params():
     return p
 
 
+def shutter(row_time, from_top=True):
+    """The record of a rolling shutter for DeviceScene.render_shutter: one row is read every `row_time` (rounded to float32),
+    from the top row down or from the bottom row up.  Row r is then exposed over device.shutter_row_interval(...) in the place
+    of [t0, t1]; a scene with moving triangles must be bounded for device.shutter_span(...)."""
+    s = _abi.Shutter()
+    s.row_time, s.from_top = float(row_time), 1 if from_top else 0
+    return s
+
+
 class HostScene:
     """A built and flattened scene with its camera; owns the host buffers."""
 
