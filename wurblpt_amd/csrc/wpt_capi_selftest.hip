@@ -69,7 +69,8 @@ __global__ void wpt_selftest_aabb_kernel(int n, const float* boxes, const float*
 /* The watertight triangle test as the kernels call it, one lane per case.  cases: v0 v1 v2 origin direction amin amax (17 floats);
  * out: 8 words: accepted, the bits of a, invDet, U, V, W (zero when rejected), RayAux::k, one spare.  form 0: rayAux +
  * triangleTest (the walks that select by axis); 1: rayAuxRotated + rotated() + triangleTestRotated with Sz = inv[kz] (the walk on
- * rotated corner copies); 2, 3: the SHEAR_ONLY variants of the light-pdf loop, Sz = inv.x (hotSpotPdfValue, hotSpotPdfValueRotated). */
+ * rotated corner copies); 2, 3: the SHEAR_ONLY variants of the light-pdf loop, Sz = inv.x (hotSpotPdfValue, hotSpotPdfValueRotated);
+ * 4: form 1's arguments through triangleTestRotatedStraight (the leaf pass of the rotated kernels with the scene in LDS). */
 __global__ void wpt_selftest_triangle_kernel(int form, int n, const float* cases, uint32_t* out)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -97,11 +98,17 @@ __global__ void wpt_selftest_triangle_kernel(int form, int n, const float* cases
         const RayAux h = rayAux<true>(dir);
         k = h.k;
         accepted = triangleTest(v0, v1, v2, org, h, amin, amax, c);
-    } else {
+    } else if (form == 3) {
         const RayAux h = rayAuxRotated<true>(dir);
         const int kz = auxKz(h);
         k = h.k;
         accepted = triangleTestRotated(rotated(v0, kz), rotated(v1, kz), rotated(v2, kz), rotated(org, kz), h.Sx, h.Sy, h.inv.x,
+                (uint32_t)h.k & (uint32_t)RAY_FLIP, amin, amax, c);
+    } else {
+        const RayAux h = rayAuxRotated(dir);
+        const int kz = auxKz(h);
+        k = h.k;
+        accepted = triangleTestRotatedStraight(rotated(v0, kz), rotated(v1, kz), rotated(v2, kz), rotated(org, kz), h.Sx, h.Sy, comp(h.inv, kz),
                 (uint32_t)h.k & (uint32_t)RAY_FLIP, amin, amax, c);
     }
     uint32_t* o = out + 8 * (size_t)i;
@@ -176,11 +183,11 @@ wpt_status wpt_selftest_aabb(int n, const float* boxes_device, const float* rays
     return launched();
 }
 
-/* test hooks: the triangle test in the four forms the kernels call it in, the ray's constants, the sphere test, and the closest
+/* test hooks: the triangle test in the five forms the kernels call it in, the ray's constants, the sphere test, and the closest
  * hit of a scene with its finished record (kernels above and in wpt_k_groundtruth.hip; all pointers are device pointers) */
 wpt_status wpt_selftest_triangle(int form, int n, const float* cases_device, uint32_t* out_device)
 {
-    if (form < 0 || form > 3 || n <= 0 || !cases_device || !out_device)
+    if (form < 0 || form > 4 || n <= 0 || !cases_device || !out_device)
         return fail(WPT_ERR_INVALID_ARGUMENT, "bad self test arguments");
     hipLaunchKernelGGL(wpt_selftest_triangle_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, form, n, cases_device, out_device);
     return launched();

@@ -621,8 +621,8 @@
                             c.invDet = c.U = c.V = c.W = 0.0f;
                             accepted = sphereTest(sphereNow<F>(sv, ps, sv.spheres[leafPrim & ~PRIM_SPHERE]), ps.o, ps.d, par.min_hit_distance, amax, c.a);
                         } else if constexpr (ROTATED) {
-                            /* no select by axis */
-                            accepted = triangleTestRotated(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), mk3(r2.x, r2.y, r2.z), orgRotated, aux.Sx, aux.Sy,
+                            /* no select by axis, and one straight run: every lane of the pass computes the whole test */
+                            accepted = triangleTestRotatedStraight(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), mk3(r2.x, r2.y, r2.z), orgRotated, aux.Sx, aux.Sy,
                                     auxSz, (uint32_t)aux.k & (uint32_t)RAY_FLIP, par.min_hit_distance, amax, c);
                         } else {
                             const float4 g0 = tri4(3 * leafPrim), g1 = tri4(3 * leafPrim + 1), g2 = tri4(3 * leafPrim + 2);
@@ -640,7 +640,16 @@
                          * comparisons in the reference) makes the bound grow: children dropped under the smaller bound may be
                          * due after all, so this ray starts again from the root in the binary walk */
                         const bool grown = WIDE && accepted && !(aux.k & (RAY_MAY_NAN | RAY_WALK_BINARY)) && !(c.a <= amax);
-                        if (accepted) {
+                        if constexpr (ROTATED) {
+                            /* the straight test has filled c whatever it found: a rejected lane keeps its words, in selects */
+                            best.prim = accepted ? leafPrim : best.prim;
+                            best.a = accepted ? c.a : best.a;
+                            best.invDet = accepted ? c.invDet : best.invDet;
+                            best.U = accepted ? c.U : best.U;
+                            best.V = accepted ? c.V : best.V;
+                            best.W = accepted ? c.W : best.W;
+                            amax = accepted ? c.a : amax;
+                        } else if (accepted) {
                             c.prim = leafPrim;
                             best = c;
                             amax = c.a;

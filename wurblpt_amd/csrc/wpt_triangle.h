@@ -275,6 +275,60 @@ WPT_D bool triangleTestRotated(f3 c0, f3 c1, f3 c2, f3 org, float Sx0, float Sy0
     return true;
 }
 
+/* triangleTestRotated in one straight run, for the leaf pass of the kernels with the scene in LDS: the same expressions in the same
+ * order, but no early return -- every lane evaluates det, T, the range condition, 1 / det and a, and the three rejections are
+ * combined without short circuit.  A wave leaves a region of the branching form only when all its lanes fail there, which a leaf
+ * pass of a dozen lanes against wall-sized triangles rarely does, while each region costs it scalar instructions, a wait for a
+ * comparison to reach the scalar side and a branch ("The leaf pass in one straight run").  The comparisons
+ * are the reference's own, not their negated opposites: with a NaN all of them are false and the case is accepted, as there.
+ * c is written in every case; where the result is false its values are not the branching form's (which leaves c alone) and may be
+ * infinite or NaN -- nothing traps -- so the caller selects by the result.  The double-precision fall-back is rare and long and
+ * keeps its branch.  Held to triangleTestRotated bit for bit in tests/test_triangle_straight.py. */
+WPT_D bool triangleTestRotatedStraight(f3 c0, f3 c1, f3 c2, f3 org, float Sx0, float Sy0, float Sz, uint32_t flip, float amin, float amax, Candidate& c)
+{
+    const f3 A = sub(c0, org);
+    const f3 B = sub(c1, org);
+    const f3 C = sub(c2, org);
+    const float Ax = A.x - Sx0 * A.z;
+    const float Ay = wptm::bits_to_float(wptm::float_to_bits(A.y - Sy0 * A.z) ^ flip);
+    const float Bx = B.x - Sx0 * B.z;
+    const float By = wptm::bits_to_float(wptm::float_to_bits(B.y - Sy0 * B.z) ^ flip);
+    const float Cx = C.x - Sx0 * C.z;
+    const float Cy = wptm::bits_to_float(wptm::float_to_bits(C.y - Sy0 * C.z) ^ flip);
+    float U = Cx * By - Cy * Bx;
+    float V = Ax * Cy - Ay * Cx;
+    float W = Bx * Ay - By * Ax;
+    if (__builtin_expect(__builtin_fabsf(U) < k_ldeps || __builtin_fabsf(V) < k_ldeps || __builtin_fabsf(W) < k_ldeps, 0)) {
+        double CxBy = (double)Cx * (double)By;
+        double CyBx = (double)Cy * (double)Bx;
+        U = (float)(CxBy - CyBx);
+        double AxCy = (double)Ax * (double)Cy;
+        double AyCx = (double)Ay * (double)Cx;
+        V = (float)(AxCy - AyCx);
+        double BxAy = (double)Bx * (double)Ay;
+        double ByAx = (double)By * (double)Ax;
+        W = (float)(BxAy - ByAx);
+    }
+    const int mixedSigns = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
+    const float det = U + V + W;
+    const int zeroDet = det == 0.0f;
+    const float Az = Sz * A.z;
+    const float Bz = Sz * B.z;
+    const float Cz = Sz * C.z;
+    const float T = U * Az + V * Bz + W * Cz;
+    const uint32_t sgn = wptm::float_to_bits(det) & 0x80000000u;
+    const float Ts = wptm::bits_to_float(wptm::float_to_bits(T) ^ sgn);
+    const float ds = wptm::bits_to_float(wptm::float_to_bits(det) ^ sgn);
+    const int outOfRange = (Ts < amin * ds) | (Ts > amax * ds);
+    const float invDet = 1.0f / det;
+    c.a = invDet * T;
+    c.invDet = invDet;
+    c.U = U;
+    c.V = V;
+    c.W = W;
+    return !(mixedSigns | zeroDet | outOfRange);
+}
+
 } /* namespace wptd */
 
 #endif

@@ -1508,7 +1508,8 @@ def selftest_aabb(boxes, rays):
 def selftest_triangle(form, cases):
     """The watertight triangle test as the kernels call it (wpt_selftest_triangle_kernel).  cases (n, 17): v0 v1 v2 origin
     direction amin amax; form 0 rayAux + triangleTest, 1 rayAuxRotated + triangleTestRotated, 2 and 3 their forms in the
-    light-pdf loop.  Returns uint32 (n, 8): accepted, the bits of a, invDet, U, V, W (zero when rejected), RayAux::k, spare."""
+    light-pdf loop, 4 form 1 through triangleTestRotatedStraight (the LDS kernels' leaf pass).  Returns uint32 (n, 8): accepted,
+    the bits of a, invDet, U, V, W (zero when rejected), RayAux::k, spare."""
     import numpy as np
     import torch
     tc = torch.as_tensor(np.ascontiguousarray(cases, dtype=np.float32).reshape(-1, 17), device="cuda")
