@@ -1133,6 +1133,20 @@ uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes);
 #define WPT_HIT_DATA_HOTSPOTS 2u
 #define WPT_HIT_DATA_NORMALS 4u
 uint32_t wpt_kernel_hit_data(void);
+/* 1 if the path-tracing kernel of the most recent render call read the material records by LDS address, else 0: a launch in the
+ * form of 1024 lanes whose kernel reads hit records and hot spots from LDS keeps the material records there as well -- behind
+ * the corners where they are in LDS anyway, else behind that data where they still end in front of the paths' cold words -- and
+ * fetches a hit's material with LDS instructions; every other launch reads them through the scene's array.  Not a part of
+ * wpt_kernel_hit_data's sum; WPT_WALK_HIT_DATA_IN_HBM switches it off with the parts. */
+uint32_t wpt_kernel_materials_in_lds(void);
+/* Where such a launch keeps the material records: a pure function that needs no device (tests).  node_count, tri_count,
+ * material_count: the scene's tree, triangles and materials; behind_corners: 1 if the kernel choice has the material records in
+ * LDS behind the corners anyway (wpt_kernel_choice's materials_in_lds & 1); instance_count: the instances whose normal matrix a
+ * transformed triangle names; hotspot_count: the hot spots.  *at (or NULL): the quadword (16 bytes), from the scene's start in
+ * LDS, where the records start or would; *quads (or NULL): the quadwords of the scene with everything the launch keeps.
+ * Returns 1 if the launch reads them by LDS address, else 0. */
+int wpt_material_places(uint32_t node_count, uint32_t tri_count, uint32_t material_count, uint32_t behind_corners, uint32_t instance_count,
+        uint32_t hotspot_count, uint32_t* at, uint32_t* quads);
 /* Which instantiation of the single kernel renders a launch, from the facts the library decides by: a pure function that needs
  * no device (tests).  need: the feature bits of the scene and the launch's cameras (wpt_device.h, FEAT_*; FEAT_ANIM for a moving
  * scene, a moving camera or an exposure interval); sensor: 0 one frame, 1 transient film, 2 batch of views, 3 adaptive sampling,

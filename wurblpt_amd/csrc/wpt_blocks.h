@@ -823,7 +823,7 @@ WPT_D int blockShade(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS& 
         tSection = clock64();
     sec<COUNT>(lc, SEC_HIT_RECORD);
     Hit h = finishHit<F>(sv, best, ray.o, ray.d, ps.time, tri4);
-    const wpt_material& m = resolveMaterial<F>(sv, h.material, h);
+    const wpt_material& m = hitMaterial<F>(sv, tri4, h.material, h);
     if ((F & ~(FEAT_GGX | FEAT_GLASS | FEAT_TRANSIENT | FEAT_ADAPTIVE | FEAT_ROTATED | FEAT_SLICED | ((F & FEAT_TOF) ? (FEAT_TOF | FEAT_SPOT | FEAT_TWOSIDED) : 0u))) == 0 && waitBelow > 0) { /* the all-features builds have no register to spare for it */
         /* Each kind of material is its own stretch of code below, as long for one lane as for
          * forty.  A kind with few lanes in this round, next to lanes of other kinds, stands back
@@ -1026,7 +1026,7 @@ WPT_D int blockNeeEnd(const SceneView& sv, const wpt_params& par, Tri4 tri4, PS&
         const Slot nee = ps.get(SLOT_NEE);
         if (best.prim == nee.w) {
             Hit lh = finishHit<F>(sv, best, ps.o, ps.d, ps.time, tri4);
-            const wpt_material& lm = resolveMaterial<F>(sv, lh.material, lh);
+            const wpt_material& lm = hitMaterial<F>(sv, tri4, lh.material, lh);
             f4 rad = mul(neeFactorOf<F>(nee), materialEmitted<F>(sv, lm, lh, ps.d));
             const f4 ri = ps.get4(SLOT_RI);
             f3 oplLight = add(mk3(oplSlot.x, oplSlot.y, oplSlot.z), scl(lh.a, sensorChannels<F>(ri)));
@@ -1063,7 +1063,7 @@ WPT_D void blockNeeResult(const SceneView& sv, const wpt_params& par, Tri4 tri4,
     if (ps.neeKind == RAY_NEE_LIGHT) {
         if (neeBest.prim == nee.w) {
             Hit lh = finishHit<F>(sv, neeBest, ps.neeO, ps.neeD, ps.time, tri4);
-            const wpt_material& lm = resolveMaterial<F>(sv, lh.material, lh);
+            const wpt_material& lm = hitMaterial<F>(sv, tri4, lh.material, lh);
             f4 rad = mul(mk4(nee.x, nee.y, nee.z, 0.0f), materialEmitted<F>(sv, lm, lh, ps.neeD));
             const Slot opl = ps.get(SLOT_NEXTATT), ri = ps.get(SLOT_SRDIR);
             f3 oplLight = add(mk3(opl.x, opl.y, opl.z), scl(lh.a, mk3(ri.x, ri.y, ri.z)));

@@ -35,6 +35,8 @@ std::atomic<unsigned long long*> g_lastSliceStats{nullptr};
 std::atomic<uint32_t> g_lastWorkgroup{uint32_t(WG)};
 /* WPT_HIT_DATA_* of the parts the most recent render call's kernel kept in LDS (wpt_kernel_hit_data) */
 std::atomic<uint32_t> g_lastHitData{0};
+/* 1: that kernel read the material records by LDS address (wpt_kernel_materials_in_lds) */
+std::atomic<uint32_t> g_lastMaterialsInLds{0};
 static_assert(WPT_HIT_DATA_RECORDS == wptk::HIT_DATA_RECORDS && WPT_HIT_DATA_HOTSPOTS == wptk::HIT_DATA_HOTSPOTS && WPT_HIT_DATA_NORMALS == wptk::HIT_DATA_NORMALS,
         "wpt_lds_places.h restates the header's names of the parts");
 
@@ -70,12 +72,14 @@ void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned 
     g_lastSliceStats.store(sliceStats, std::memory_order_relaxed);
     g_lastWorkgroup.store(uint32_t(WG), std::memory_order_relaxed);
     g_lastHitData.store(0, std::memory_order_relaxed);
+    g_lastMaterialsInLds.store(0, std::memory_order_relaxed);
 }
 
 /* ... and, behind recordLaunch, the workgroup of a launch that was not one of WG lanes with the plain node array, and the parts
- * of a hit's data it kept in LDS */
-void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts)
+ * of a hit's data it kept in LDS, the material records by LDS address among them or not */
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts, bool materialsByLdsAddress)
 {
+    g_lastMaterialsInLds.store(materialsByLdsAddress ? 1u : 0u, std::memory_order_relaxed);
     g_lastWorkgroup.store(lanes | (orderedBoxes ? 0x80000000u : 0u), std::memory_order_relaxed);
     g_lastHitData.store(hitDataParts, std::memory_order_relaxed);
 }
@@ -193,6 +197,22 @@ uint32_t wpt_kernel_workgroup(uint32_t* ordered_boxes)
 uint32_t wpt_kernel_hit_data(void)
 {
     return g_lastHitData.load(std::memory_order_relaxed);
+}
+
+uint32_t wpt_kernel_materials_in_lds(void)
+{
+    return g_lastMaterialsInLds.load(std::memory_order_relaxed);
+}
+
+int wpt_material_places(uint32_t node_count, uint32_t tri_count, uint32_t material_count, uint32_t behind_corners, uint32_t instance_count,
+        uint32_t hotspot_count, uint32_t* at, uint32_t* quads)
+{
+    const wptk::MaterialPlaces m = wptk::launchMaterialPlaces(node_count, tri_count, material_count, behind_corners != 0, instance_count, hotspot_count);
+    if (at)
+        *at = m.at;
+    if (quads)
+        *quads = m.quads;
+    return m.in ? 1 : 0;
 }
 
 uint32_t wpt_last_render_passes(void)

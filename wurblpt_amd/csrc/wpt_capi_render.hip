@@ -248,7 +248,8 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
     recordLaunch(kernel->name, kernelForm(choice.rotated, sliceStats ? plan.units : 0, choice.rotated && !scene->leafOneToOne), done ? plan.passes : 1u,
             sliceStats);
     if (large)
-        recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED, (hitData >> wptk::LDS_HIT_DATA_SHIFT) & 7u);
+        recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED, (hitData >> wptk::LDS_HIT_DATA_SHIFT) & 7u,
+                ((hitData >> wptk::LDS_HIT_DATA_SHIFT) & wptk::HIT_DATA_MATERIALS) != 0);
     return hipGetLastError();
 }
 

@@ -569,8 +569,10 @@ struct LdsHitData {
     const float4* scene;                       /* the scene's start in LDS */
     uint32_t corners;                          /* the first corner record, in quadwords from there, like the three below */
     uint32_t recordsAt, hotspotsAt, normalsAt;
+    uint32_t materialsAt;                      /* HIT_DATA_MATERIALS: the material records, whole, read by LDS address */
     WPT_D float4 operator()(uint32_t i) const { return scene[corners + i]; }
     static constexpr WPT_D bool has(uint32_t part) { return (PARTS & part) != 0; }
+    WPT_D const wpt_material& material(uint32_t i) const { return *reinterpret_cast<const wpt_material*>(scene + materialsAt + wptk::HIT_MATERIAL_QUADS * i); }
     WPT_D float4 record(uint32_t prim, uint32_t k) const { return scene[recordsAt + wptk::HIT_RECORD_QUADS * prim + k]; }
     WPT_D float4 hotspot(uint32_t i, uint32_t k) const { return scene[hotspotsAt + wptk::HIT_HOTSPOT_QUADS * i + k]; }
     WPT_D float4 normalColumn(uint32_t instance, uint32_t k) const { return scene[normalsAt + wptk::HIT_NORMAL_QUADS * instance + k]; }
@@ -1181,7 +1183,21 @@ template<uint32_t F> WPT_D const wpt_material& resolveMaterial(const SceneView& 
     return *m;
 }
 
-/* Material::scatter.  `h` must already be resolved through resolveMaterial. */
+/* ... for the blocks, which have the walk's Tri4 at hand: the large form with HIT_DATA_MATERIALS fetches the record by its LDS
+ * address (wpt_lds_places.h), so that every read of it is an LDS instruction that waits for lgkmcnt alone; every other kernel
+ * resolves it through SceneView::materials as above */
+template<uint32_t F, class Tri4> WPT_D const wpt_material& hitMaterial(const SceneView& sv, const Tri4& tri4, uint32_t mat, Hit& h)
+{
+    if constexpr (HasLdsHitData<Tri4>::value) {
+        if constexpr (Tri4::has(wptk::HIT_DATA_MATERIALS)) {
+            static_assert(!(F & FEAT_TWOSIDED), "materials by LDS address: kernels of the basic feature set");
+            return tri4.material(mat);
+        }
+    }
+    return resolveMaterial<F>(sv, mat, h);
+}
+
+/* Material::scatter. `h` must already be resolved through resolveMaterial. */
 template<uint32_t F> WPT_D Scatter materialScatter(const SceneView& sv, const wpt_material& m, const Ray& ray, const Hit& h, Prng& prng, MatCache& mc)
 {
     switch (m.type) {

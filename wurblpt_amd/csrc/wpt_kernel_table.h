@@ -211,8 +211,11 @@ inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrdere
         const uint32_t parts = hitDataKernelParts(places.parts); /* the kernels exist for three sets of parts */
         if (parts && size_t(places.nodeCopiesEnd) * 16 == bytes) {
             const uint32_t end = (parts & HIT_DATA_NORMALS) ? places.quads : places.normalsAt;
-            bytes = size_t(end) * 16;
-            *hitData = (parts << LDS_HIT_DATA_SHIFT) | ((parts & HIT_DATA_NORMALS) ? counts.instanceCount << LDS_HIT_NORMALS_SHIFT : 0u);
+            /* ... and the material records by LDS address where they have a place: a bit of the launch's word beside the parts */
+            const MaterialPlaces materials = materialPlaces(nodeCount, counts.triCount, counts.materialCount, (c.materialsInLds & LDS_MATERIALS) != 0, end);
+            bytes = size_t(materials.quads) * 16;
+            *hitData = ((parts | (materials.in ? HIT_DATA_MATERIALS : 0u)) << LDS_HIT_DATA_SHIFT)
+                    | ((parts & HIT_DATA_NORMALS) ? counts.instanceCount << LDS_HIT_NORMALS_SHIFT : 0u);
         }
     }
     *sceneLdsBytes = bytes;

@@ -1,11 +1,12 @@
 /*
  * wpt_lds_places.h -- where the large form of the rotated kernels keeps what in a compute unit's LDS (host and device; no HIP
  * header, nothing global: wpt_scene_layout.h includes it for the host, wpt_pathtrace.inc.h for the kernels and the launch, and
- * tests/hit_data_layout.cpp compiles it on its own under the host sanitizers).
+ * tests/hit_data_layout.cpp and tests/material_places.cpp compile it on their own under the host sanitizers).
  *
- *   [ math tables ][ nodes, null node | corners x 3 | materials ][ node copies 1 .. 7 ][ hit data ] ... [ cold words at 32 KiB ]
+ *   [ math tables ][ nodes, null node | corners x 3 | materials ][ node copies 1 .. 7 ][ hit data ][ materials ] ... [ cold words at 32 KiB ]
  *
- * orderedPlaces says where the node copies lie, hitDataPlaces what of a hit's data follows them and where.  All places are
+ * orderedPlaces says where the node copies lie, hitDataPlaces what of a hit's data follows them and where, materialPlaces where
+ * the material records are read by LDS address (in either of the two places, never both).  All places are
  * quadwords (16 bytes) from the scene's start, which lies behind the math tables.
  */
 #ifndef WPT_LDS_PLACES_H
@@ -112,6 +113,64 @@ WPT_PLACES_FN HitDataPlaces hitDataPlaces(uint32_t nodeCount, uint32_t triCount,
     part(HIT_DATA_NORMALS, instanceCount <= HIT_NORMALS_MAX ? instanceCount : 0xffffffffull, HIT_NORMAL_QUADS, p.normalsAt);
     p.quads = at;
     return p;
+}
+
+/* ---- the material records by LDS address (the large form; LdsHitData::material reads them) ----
+ * A launch whose kernel reads hit records and hot spots from LDS (hitDataKernelParts: not 0) reads the material records there
+ * as well where they have a place, and then "the materials are in LDS" is a fact of the instantiation, HIT_DATA_MATERIALS among
+ * its template argument's bits: the long round fetches a hit's material with LDS instructions at an offset from the scene's
+ * start, not through a generic pointer that may as well point to HBM.  The bit is the kernels' and the launch word's own:
+ * HIT_DATA_ALL, hitDataPlaces and what wpt_kernel_hit_data reports do not know it.
+ * The records, whole (HIT_MATERIAL_QUADS quadwords each, as in HBM), have a place
+ *   behind the corners, where the launch keeps them already (behindCorners: LDS_MATERIALS, and hitDataPlaces counted them), or
+ *   at `end`, the quadword where the launch's scene and its parts of a hit's data end, if they end in front of the cold words.
+ * Otherwise, and for a scene without materials, they are not in: the launch runs the kernel without the bit, which fetches them
+ * through SceneView::materials like every other kernel. */
+constexpr uint32_t HIT_DATA_MATERIALS = 8u;
+constexpr uint32_t HIT_MATERIAL_QUADS = uint32_t(sizeof(wpt_material) / 16);
+
+struct MaterialPlaces {
+    bool in;        /* the kernel reads the material records by LDS address */
+    uint32_t at;    /* where they start, in quadwords from the scene's start (not in: where they would) */
+    uint32_t quads; /* the quadwords of the scene with them: `end`, or behind the records placed there */
+};
+
+/* nodeCount, triCount: as for hitDataPlaces; materialCount: the scene's material records; end: HitDataPlaces::quads of the parts
+ * the launch's kernel has.  Nothing here overflows for any input. */
+WPT_PLACES_FN MaterialPlaces materialPlaces(uint32_t nodeCount, uint32_t triCount, uint32_t materialCount, bool behindCorners, uint32_t end)
+{
+    MaterialPlaces p = { false, end, end };
+    const uint64_t need = uint64_t(materialCount) * HIT_MATERIAL_QUADS;
+    if (materialCount == 0 || end > LARGE_SCENE_ROOM_QUADS)
+        return p;
+    if (behindCorners) {
+        const uint64_t at = 2ull * nodeCount + 2ull + 9ull * triCount;
+        p.at = at <= LARGE_SCENE_ROOM_QUADS ? uint32_t(at) : 0xffffffffu;
+        p.in = at + need <= end; /* (the node copies lie behind them: a launch in the large form has it so) */
+        return p;
+    }
+    if (end + need <= LARGE_SCENE_ROOM_QUADS) {
+        p.in = true;
+        p.quads = uint32_t(end + need);
+    }
+    return p;
+}
+
+/* The steps of a launch in the large form in one (selectLargeForm's, wpt_kernel_table.h): the parts that fit, the kernel's set of
+ * them (*kernelParts, or NULL), and the material records behind what that kernel keeps.  A kernel without parts reads the
+ * material records like every other kernel: they are not in. */
+WPT_PLACES_FN MaterialPlaces launchMaterialPlaces(uint32_t nodeCount, uint32_t triCount, uint32_t materialCount, bool behindCorners, uint32_t instanceCount,
+        uint32_t hotspotCount, uint32_t* kernelParts = nullptr)
+{
+    const HitDataPlaces places = hitDataPlaces(nodeCount, triCount, behindCorners ? materialCount : 0u, instanceCount, hotspotCount);
+    const uint32_t parts = hitDataKernelParts(places.parts);
+    if (kernelParts)
+        *kernelParts = parts;
+    if (!parts) {
+        const MaterialPlaces none = { false, places.nodeCopiesEnd, places.nodeCopiesEnd };
+        return none;
+    }
+    return materialPlaces(nodeCount, triCount, materialCount, behindCorners, (parts & HIT_DATA_NORMALS) ? places.quads : places.normalsAt);
 }
 
 } /* namespace wptk */

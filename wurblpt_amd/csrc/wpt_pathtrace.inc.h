@@ -88,8 +88,8 @@ constexpr uint32_t LDS_MATERIALS = 1u; /* the material records are in LDS too */
 constexpr uint32_t LDS_FOLD = 2u;      /* the LDS copy of the tree folds first children that repeat their parent's box (wpt_fold.h) */
 constexpr uint32_t LDS_LEAF_LINKS = 4u; /* ROTATED kernels: a leaf's skip links are those in its triangle's corner records (every triangle has one leaf) */
 /* the large form: the parts of a hit's data that follow the node copies in LDS (wpt_lds_places.h), HIT_DATA_* << LDS_HIT_DATA_SHIFT
- * -- the launcher picks the instantiation by them -- and in the word's upper half the instances whose normal matrices
- * HIT_DATA_NORMALS holds */
+ * -- the launcher picks the instantiation by them -- with HIT_DATA_MATERIALS beside them where the kernel reads the material
+ * records by LDS address (materialPlaces), and in the word's upper half the instances whose normal matrices HIT_DATA_NORMALS holds */
 constexpr uint32_t LDS_HIT_DATA_SHIFT = 8, LDS_HIT_NORMALS_SHIFT = 16;
 /* ROTATED kernels, the leaf word of the tree's copy in LDS (wpt_leaf_words.h; wpt_capi.hip asserts that they agree):
  * sign bit | the leaf's node index << LEAF_NODE_SHIFT | quadword offset of the triangle's first corner within a copy */
@@ -341,8 +341,13 @@ void launchPathtraceLarge(const KernelArgs& args, dim3 grid, size_t sceneLdsByte
         if (COLD_BYTES_LARGE + sceneLdsBytes > LDS_BYTES_PER_CU)                                                               \
             return;                                                                                                            \
         /* one instantiation per set of parts of a hit's data in LDS that a launch may name (hitDataKernelParts) */            \
-        const uint32_t hit = (args.materialsInLds >> LDS_HIT_DATA_SHIFT) & HIT_DATA_ALL;                                       \
-        if (hit == HIT_DATA_ALL)                                                                                               \
+        /* ... and, for the two that have parts, one more that reads the material records by LDS address (materialPlaces) */   \
+        const uint32_t hit = (args.materialsInLds >> LDS_HIT_DATA_SHIFT) & (HIT_DATA_ALL | HIT_DATA_MATERIALS);                \
+        if (hit == (HIT_DATA_ALL | HIT_DATA_MATERIALS))                                                                        \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_ALL | HIT_DATA_MATERIALS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else if (hit == (HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS))                                           \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else if (hit == HIT_DATA_ALL)                                                                                          \
             launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_ALL>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
         else if (hit == (HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS))                                                                \
             launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \

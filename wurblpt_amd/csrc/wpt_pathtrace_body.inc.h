@@ -188,6 +188,18 @@
                     ldsScene[places.normalsAt + i] = make_float4(N[3 * k], N[3 * k + 1], N[3 * k + 2], 0.0f);
                 }
             }
+            if constexpr ((HIT & HIT_DATA_MATERIALS) != 0) {
+                /* the material records by LDS address (materialPlaces; the host asked it with the same counts): behind the
+                 * corners where the copy above has put them, else behind the parts above, whole as they are in HBM */
+                const bool behindCorners = (args.materialsInLds & LDS_MATERIALS) != 0;
+                const MaterialPlaces mp = materialPlaces(nodeCount, sv.triCount, sv.materialCount, behindCorners, places.quads);
+                hitData.materialsAt = mp.at;
+                if (mp.in && !behindCorners) {
+                    const float4* from = reinterpret_cast<const float4*>(sv.materials);
+                    for (uint32_t i = threadIdx.x; i < HIT_MATERIAL_QUADS * sv.materialCount; i += WGS)
+                        ldsScene[mp.at + i] = from[i];
+                }
+            }
         }
     }
     __syncthreads();

@@ -808,6 +808,19 @@ def kernel_hit_data():
     return int(lib().wpt_kernel_hit_data())
 
 
+def kernel_materials_in_lds():
+    """wpt_kernel_materials_in_lds: did the most recent render call's kernel read the material records by LDS address?"""
+    return bool(lib().wpt_kernel_materials_in_lds())
+
+
+def material_places(node_count, tri_count, material_count, behind_corners, instance_count, hotspot_count):
+    """wpt_material_places: (read by LDS address?, first quadword, quadwords of the scene) for a launch in the large form"""
+    at, quads = C.c_uint32(0), C.c_uint32(0)
+    fits = lib().wpt_material_places(node_count, tri_count, material_count, 1 if behind_corners else 0, instance_count, hotspot_count,
+                                     C.byref(at), C.byref(quads))
+    return bool(fits), at.value, quads.value
+
+
 def fold_plan(host_scene, with_words=False):
     """wpt_fold_plan: the nodes whose link the kernels with the scene in LDS fold in their copy of the scene's tree; with
     with_words (count, word 7 of every node's LDS copy as numpy uint32).  Needs no device"""
