@@ -1139,6 +1139,12 @@ uint32_t wpt_kernel_hit_data(void);
  * fetches a hit's material with LDS instructions; every other launch reads them through the scene's array.  Not a part of
  * wpt_kernel_hit_data's sum; WPT_WALK_HIT_DATA_IN_HBM switches it off with the parts. */
 uint32_t wpt_kernel_materials_in_lds(void);
+/* 1 if the path-tracing kernel of the most recent render call read the launch's constants -- the origin of the camera's rays,
+ * evaluated once per launch, its frustum and rotation, the reciprocals of the frame's size and of samples_sqrt -- from a record
+ * of four quadwords in LDS, else 0: a launch that reads the material records by LDS address has that record in the last
+ * quadwords in front of the paths' cold words where the scene ends in front of them; every other launch reads the kernel's
+ * arguments per sample.  The words are the same, and so is the frame, bit for bit. */
+uint32_t wpt_kernel_launch_record(void);
 /* Where such a launch keeps the material records: a pure function that needs no device (tests).  node_count, tri_count,
  * material_count: the scene's tree, triangles and materials; behind_corners: 1 if the kernel choice has the material records in
  * LDS behind the corners anyway (wpt_kernel_choice's materials_in_lds & 1); instance_count: the instances whose normal matrix a

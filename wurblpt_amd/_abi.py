@@ -290,6 +290,7 @@ FUNCTIONS = {
     "wpt_kernel_workgroup": (_U, [_pU]),
     "wpt_kernel_hit_data": (_U, []),
     "wpt_kernel_materials_in_lds": (_U, []),
+    "wpt_kernel_launch_record": (_U, []),
     "wpt_material_places": (_I, [_U] * 6 + [_pU, _pU]),
     "wpt_kernel_choice": (_I, [_U] * 9 + [_pS, _pS, _pU, _pQ, _pU]),
     "wpt_kernel_table_entry": (_I, [_U, _pU, _pS]),

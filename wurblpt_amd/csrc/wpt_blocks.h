@@ -666,37 +666,72 @@ WPT_D void exposeRow(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const S
     }
 }
 
+/* What blockNewFrom may be handed of a launch's constants in the place of its arguments (the large form of the kernels with the
+ * scene in LDS, whose camera is the launch's own, at rest, without a lens): LaunchRecordInLds, the words the block reads of the
+ * launch -- the rays' origin, evaluated once in the kernel's prologue (cameraOriginAtRest), the frustum, the rotation, the three
+ * reciprocals, samplesSqrt, randomize_ray_over_pixel -- as a record of LAUNCH_RECORD_QUADS quadwords that the prologue has
+ * written to LDS (wpt_lds_places.h, LAUNCH_RECORD_AT).  Every lane reads the same address: a broadcast, which lands in the
+ * vector registers the arithmetic takes its operands from, where the arguments' scalars came out of spilled SGPRs one
+ * v_readlane_b32 at a time.  The words are the arguments'.  NoLaunchConstants: everything from the arguments, per sample, as
+ * every other kernel has it. */
+struct NoLaunchConstants {
+    static constexpr bool inLds = false;
+};
+struct LaunchRecordInLds {
+    static constexpr bool inLds = true;
+    const float4* at; /* origin x y z, invSamplesSqrt | l r b t | rotation | invWidth, invHeight, samplesSqrt, randomize_ray_over_pixel */
+};
+/* quadword k of the record, from the launch's arguments (the words FrameArgs carries, and the origin made of its camera) */
+WPT_D float4 launchRecordQuad(uint32_t k, const wpt_camera& cam, const wpt_params& par, f3 origin, float invWidth, float invHeight, float invSamplesSqrt,
+        uint32_t samplesSqrt)
+{
+    return k == 0 ? make_float4(origin.x, origin.y, origin.z, invSamplesSqrt)
+            : k == 1 ? make_float4(cam.l, cam.r, cam.b, cam.t)
+            : k == 2 ? make_float4(cam.rotation[0], cam.rotation[1], cam.rotation[2], cam.rotation[3])
+            : make_float4(invWidth, invHeight, __uint_as_float(samplesSqrt), __uint_as_float(par.randomize_ray_over_pixel ? 1u : 0u));
+}
+
 /* wurblpt.hpp:348-360 + Camera::getRay (camera.hpp:123-185), pinhole or thin lens, from camera `cam`.  UNIFORM: `cam` is the
  * same for every lane of the wave (the launch's camera, or the one view a whole wave of a batch is on), and its frustum and
  * pose are taken as scalars (here()); otherwise each lane reads its own camera's words. */
-template<uint32_t F, bool UNIFORM, class PS>
-WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const SceneView& sv)
+template<uint32_t F, bool UNIFORM, class PS, class LC = NoLaunchConstants>
+WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const SceneView& sv, const LC launch = LC{})
 {
+    static_assert(!LC::inLds || (UNIFORM && !(F & (FEAT_LENS | FEAT_ANIM))), "a launch's origin: the launch's own camera, at rest, without a lens");
     auto uni = [](float x) {
         if constexpr (UNIFORM)
             return here(x);
         else
             return x;
     };
+    /* the launch record's quadwords (LC::inLds); every use below names the argument beside the record's word, and the
+     * condition is a constant: a kernel without a record reads its arguments where it always did */
+    [[maybe_unused]] float4 recOrigin, recFrustum, recRotation, recRest;
+    if constexpr (LC::inLds) {
+        recOrigin = launch.at[0];
+        recFrustum = launch.at[1];
+        recRotation = launch.at[2];
+        recRest = launch.at[3];
+    }
     const uint32_t stratum = ps.getW(SLOT_ACC);
     const uint32_t i = stratum & 0xffffu, j = stratum >> 16; /* sampleIndex % samplesSqrt, sampleIndex / samplesSqrt */
-    if (j >= fa.samplesSqrt)
+    if (j >= (LC::inLds ? __float_as_uint(recRest.z) : fa.samplesSqrt))
         return NEXT_DONE;
     const uint32_t pxy = ps.getW(SLOT_SRDIR);
     Prng prng = loadPrng(ps);
     float u = (float)(pxy & 0xffffu), v = (float)(pxy >> 16);
-    if (fa.par.randomize_ray_over_pixel) {
+    if (LC::inLds ? __float_as_uint(recRest.w) != 0 : fa.par.randomize_ray_over_pixel != 0) {
         /* stratified jitter; the reference compiler draws the vertical stratum first */
         const float fj = (float)j + in01(prng);
         const float fi = (float)i + in01(prng);
-        u += fi * fa.invSamplesSqrt;
-        v += fj * fa.invSamplesSqrt;
+        u += fi * (LC::inLds ? recOrigin.w : fa.invSamplesSqrt);
+        v += fj * (LC::inLds ? recOrigin.w : fa.invSamplesSqrt);
     } else {
         u += 0.5f;
         v += 0.5f;
     }
-    u *= fa.invWidth;
-    v *= fa.invHeight;
+    u *= LC::inLds ? recRest.x : fa.invWidth;
+    v *= LC::inLds ? recRest.y : fa.invHeight;
     /* Camera::getRay (camera.hpp:123-185) */
     float stereoscopicShift = 0.0f;
     if ((F & FEAT_LENS) && cam.stereoscopic_distance > 0.0f) {
@@ -724,7 +759,11 @@ WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const
         /* the samples lie in the distorted output image: rays are made from the undistorted coordinates */
         if ((F & FEAT_LENS) && cam.distortion_type != WPT_DISTORTION_NONE)
             wptlens::undistort(cam, u, v, fa.width, fa.height); /* a real call; the coefficients travel by value */
-        f3 P = mk3(mixr(uni(cam.l), uni(cam.r), u), mixr(uni(cam.b), uni(cam.t), v), -1.0f);
+        f3 P;
+        if constexpr (LC::inLds)
+            P = mk3(mixr(recFrustum.x, recFrustum.y, u), mixr(recFrustum.z, recFrustum.w, v), -1.0f);
+        else
+            P = mk3(mixr(uni(cam.l), uni(cam.r), u), mixr(uni(cam.b), uni(cam.t), v), -1.0f);
         O = mk3(0.0f, 0.0f, 0.0f);
         if ((F & FEAT_LENS) && cam.lens_radius > 0.0f) {
             P = sclr(P, cam.focus_dist);
@@ -753,6 +792,11 @@ WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const
             ps.o = add(ld3(cam.translation), quatRotate(cam.rotation, mul(O, ld3(cam.scaling))));
             ps.d = normalize(quatRotate(cam.rotation, D));
         }
+    } else if constexpr (LC::inLds) {
+        /* O is the literal zero above: the origin is the launch's (cameraOriginAtRest: the last branch's expression, evaluated once) */
+        const float rotation[4] = { recRotation.x, recRotation.y, recRotation.z, recRotation.w };
+        ps.o = mk3(recOrigin.x, recOrigin.y, recOrigin.z);
+        ps.d = normalize(quatRotate(rotation, D));
     } else {
         if (F & FEAT_ANIM)
             ps.time = fa.par.t0;
@@ -770,15 +814,15 @@ WPT_D int blockNewFrom(const FrameArgs& fa, const wpt_camera& cam, PS& ps, const
     opl.x = opl.y = opl.z = 0.0f;
     opl.w = 0; /* pathComponent */
     ps.set(SLOT_OPL, opl);
-    ps.setW(SLOT_ACC, i + 1 < fa.samplesSqrt ? stratum + 1 : (j + 1) << 16);
+    ps.setW(SLOT_ACC, i + 1 < (LC::inLds ? __float_as_uint(recRest.z) : fa.samplesSqrt) ? stratum + 1 : (j + 1) << 16);
     ps.rayKind = RAY_PATH;
     return NEXT_TRACE;
 }
 
-template<uint32_t F, class PS>
-WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv)
+template<uint32_t F, class PS, class LC = NoLaunchConstants>
+WPT_D int blockNew(const FrameArgs& fa, PS& ps, const SceneView& sv, const LC launch = LC{})
 {
-    return blockNewFrom<F, true>(fa, fa.cam, ps, sv);
+    return blockNewFrom<F, true>(fa, fa.cam, ps, sv, launch);
 }
 
 /* tracePath, one path component (wurblpt.hpp:131-252); `best` is the path ray's result.

@@ -37,6 +37,8 @@ std::atomic<uint32_t> g_lastWorkgroup{uint32_t(WG)};
 std::atomic<uint32_t> g_lastHitData{0};
 /* 1: that kernel read the material records by LDS address (wpt_kernel_materials_in_lds) */
 std::atomic<uint32_t> g_lastMaterialsInLds{0};
+/* 1: that kernel read the launch's constants from the launch record in LDS (wpt_kernel_launch_record) */
+std::atomic<uint32_t> g_lastLaunchRecord{0};
 static_assert(WPT_HIT_DATA_RECORDS == wptk::HIT_DATA_RECORDS && WPT_HIT_DATA_HOTSPOTS == wptk::HIT_DATA_HOTSPOTS && WPT_HIT_DATA_NORMALS == wptk::HIT_DATA_NORMALS,
         "wpt_lds_places.h restates the header's names of the parts");
 
@@ -73,13 +75,15 @@ void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned 
     g_lastWorkgroup.store(uint32_t(WG), std::memory_order_relaxed);
     g_lastHitData.store(0, std::memory_order_relaxed);
     g_lastMaterialsInLds.store(0, std::memory_order_relaxed);
+    g_lastLaunchRecord.store(0, std::memory_order_relaxed);
 }
 
 /* ... and, behind recordLaunch, the workgroup of a launch that was not one of WG lanes with the plain node array, and the parts
- * of a hit's data it kept in LDS, the material records by LDS address among them or not */
-void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts, bool materialsByLdsAddress)
+ * of a hit's data it kept in LDS, the material records by LDS address among them or not, and the launch record with them or not */
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts, bool materialsByLdsAddress, bool launchRecord)
 {
     g_lastMaterialsInLds.store(materialsByLdsAddress ? 1u : 0u, std::memory_order_relaxed);
+    g_lastLaunchRecord.store(launchRecord ? 1u : 0u, std::memory_order_relaxed);
     g_lastWorkgroup.store(lanes | (orderedBoxes ? 0x80000000u : 0u), std::memory_order_relaxed);
     g_lastHitData.store(hitDataParts, std::memory_order_relaxed);
 }
@@ -202,6 +206,11 @@ uint32_t wpt_kernel_hit_data(void)
 uint32_t wpt_kernel_materials_in_lds(void)
 {
     return g_lastMaterialsInLds.load(std::memory_order_relaxed);
+}
+
+uint32_t wpt_kernel_launch_record(void)
+{
+    return g_lastLaunchRecord.load(std::memory_order_relaxed);
 }
 
 int wpt_material_places(uint32_t node_count, uint32_t tri_count, uint32_t material_count, uint32_t behind_corners, uint32_t instance_count,

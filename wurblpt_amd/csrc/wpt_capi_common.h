@@ -148,7 +148,7 @@ extern Settings settings;
 /* what the process's most recent render call ran (wpt_capi.hip has the words and their readers), the form's name and the
  * kernel table's row of an instantiation: see their definitions there */
 void recordLaunch(const char* name, const char* form, uint32_t passes, unsigned long long* sliceStats);
-void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts, bool materialsByLdsAddress);
+void recordWorkgroup(uint32_t lanes, bool orderedBoxes, uint32_t hitDataParts, bool materialsByLdsAddress, bool launchRecord);
 const char* kernelForm(bool rotated, uint32_t units = 0, bool leafLinksFromNodes = false);
 wpt_status lookupKernel(uint32_t features, bool count, bool ldsScene, bool wide, const wptk::KernelEntry** entry);
 

@@ -249,7 +249,7 @@ hipError_t runSingleKernel(const wpt_scene* scene, wptk::KernelArgs& args, const
             sliceStats);
     if (large)
         recordWorkgroup(WG_LARGE, wptk::LARGE_ORDERED, (hitData >> wptk::LDS_HIT_DATA_SHIFT) & 7u,
-                ((hitData >> wptk::LDS_HIT_DATA_SHIFT) & wptk::HIT_DATA_MATERIALS) != 0);
+                ((hitData >> wptk::LDS_HIT_DATA_SHIFT) & wptk::HIT_DATA_MATERIALS) != 0, ((hitData >> wptk::LDS_HIT_DATA_SHIFT) & wptk::HIT_DATA_LAUNCH) != 0);
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@
 #include "../../include/wurblpt_hip.h"
 #include "wpt_math.h"
 #include "wpt_triangle.h"
+#include "wpt_camera_origin.h"
 #include "wpt_anim.h"
 #include "wpt_lds_places.h"
 #include "wpt_rgl.h"
@@ -39,7 +40,6 @@ namespace wptd {
 WPT_D float dot(f2 a, f2 b) { float d = 0.0f; d += a.x * b.x; d += a.y * b.y; return d; }
 WPT_D float dot(f3 a, f3 b) { float d = 0.0f; d += a.x * b.x; d += a.y * b.y; d += a.z * b.z; return d; }
 WPT_D f3 normalize(f3 v) { return divs(v, __builtin_sqrtf(dot(v, v))); }
-WPT_D f3 cross(f3 v, f3 w) { return mk3(v.y * w.z - v.z * w.y, v.z * w.x - v.x * w.z, v.x * w.y - v.y * w.x); }
 WPT_D f3 reflect(f3 i, f3 n) { return sub(i, scl(2.0f * dot(n, i), n)); } /* gvm.hpp:1213 */
 WPT_D f3 refract(f3 i, f3 n, float eta)                                  /* gvm.hpp:1218 */
 {
@@ -82,13 +82,7 @@ WPT_D f3 mat4mulPoint(const float* m, f3 p)
     r.z = 0.0f; r.z += m[2] * p.x; r.z += m[6] * p.y; r.z += m[10] * p.z; r.z += m[14] * 1.0f;
     return r;
 }
-/* quaternion (x, y, z, w) rotates v, gvm.hpp:1713-1720 */
-WPT_D f3 quatRotate(const float* q, f3 v)
-{
-    f3 s = mk3(q[0], q[1], q[2]);
-    f3 t = scl(2.0f, cross(s, v));
-    return add(add(v, scl(q[3], t)), cross(s, t));
-}
+/* (cross and quatRotate: with the vector basics in wpt_triangle.h) */
 
 /* ---- Prng: xoshiro128+ seeded by splitmix64 (prng.hpp:47-101) ---- */
 struct Prng {

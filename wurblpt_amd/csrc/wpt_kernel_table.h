@@ -214,7 +214,9 @@ inline bool selectLargeForm(const KernelChoice& c, uint32_t walk, bool hasOrdere
             /* ... and the material records by LDS address where they have a place: a bit of the launch's word beside the parts */
             const MaterialPlaces materials = materialPlaces(nodeCount, counts.triCount, counts.materialCount, (c.materialsInLds & LDS_MATERIALS) != 0, end);
             bytes = size_t(materials.quads) * 16;
-            *hitData = ((parts | (materials.in ? HIT_DATA_MATERIALS : 0u)) << LDS_HIT_DATA_SHIFT)
+            /* ... and with them the launch record, where what the scene keeps in LDS ends in front of its place: one more bit */
+            const uint32_t record = materials.in && launchRecordFits(materials.quads) ? HIT_DATA_LAUNCH : 0u;
+            *hitData = ((parts | (materials.in ? HIT_DATA_MATERIALS : 0u) | record) << LDS_HIT_DATA_SHIFT)
                     | ((parts & HIT_DATA_NORMALS) ? counts.instanceCount << LDS_HIT_NORMALS_SHIFT : 0u);
         }
     }

@@ -156,6 +156,23 @@ WPT_PLACES_FN MaterialPlaces materialPlaces(uint32_t nodeCount, uint32_t triCoun
     return p;
 }
 
+/* ---- the launch record (the large form; blockNewFrom reads it, wpt_blocks.h: LaunchRecordInLds) ----
+ * What the new-sample block reads of a launch's constants, LAUNCH_RECORD_QUADS quadwords that the kernel's prologue writes: the
+ * rays' origin and invSamplesSqrt | the frustum l r b t | the rotation | invWidth, invHeight, samplesSqrt, randomize_ray_over_pixel.
+ * Its place does not depend on the scene: the last quadwords of the scene's room, straight in front of the cold words, so that no
+ * part of the layout above moves for it and its address is a literal of the instruction.  A launch whose kernel reads the
+ * material records by LDS address has it where those (materialPlaces' quads: the end of all the scene keeps in LDS) end in
+ * front of it, and then the record is a fact of the instantiation like the records themselves, HIT_DATA_LAUNCH among its template
+ * argument's bits; every other launch runs the kernel without the bit, whose block reads the arguments. */
+constexpr uint32_t HIT_DATA_LAUNCH = 16u;
+constexpr uint32_t LAUNCH_RECORD_QUADS = 4;
+constexpr uint32_t LAUNCH_RECORD_AT = LARGE_SCENE_ROOM_QUADS - LAUNCH_RECORD_QUADS;
+/* end: the quadwords of the launch's scene with all that follows it (MaterialPlaces::quads) */
+WPT_PLACES_FN bool launchRecordFits(uint32_t end)
+{
+    return end <= LAUNCH_RECORD_AT;
+}
+
 /* The steps of a launch in the large form in one (selectLargeForm's, wpt_kernel_table.h): the parts that fit, the kernel's set of
  * them (*kernelParts, or NULL), and the material records behind what that kernel keeps.  A kernel without parts reads the
  * material records like every other kernel: they are not in. */

@@ -342,8 +342,13 @@ void launchPathtraceLarge(const KernelArgs& args, dim3 grid, size_t sceneLdsByte
             return;                                                                                                            \
         /* one instantiation per set of parts of a hit's data in LDS that a launch may name (hitDataKernelParts) */            \
         /* ... and, for the two that have parts, one more that reads the material records by LDS address (materialPlaces) */   \
-        const uint32_t hit = (args.materialsInLds >> LDS_HIT_DATA_SHIFT) & (HIT_DATA_ALL | HIT_DATA_MATERIALS);                \
-        if (hit == (HIT_DATA_ALL | HIT_DATA_MATERIALS))                                                                        \
+        /* ... and, for those two, one more that reads the launch's constants from a record in LDS (launchRecordFits) */        \
+        const uint32_t hit = (args.materialsInLds >> LDS_HIT_DATA_SHIFT) & (HIT_DATA_ALL | HIT_DATA_MATERIALS | HIT_DATA_LAUNCH); \
+        if (hit == (HIT_DATA_ALL | HIT_DATA_MATERIALS | HIT_DATA_LAUNCH))                                                      \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_ALL | HIT_DATA_MATERIALS | HIT_DATA_LAUNCH>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else if (hit == (HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS | HIT_DATA_LAUNCH))                         \
+            launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS | HIT_DATA_LAUNCH>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
+        else if (hit == (HIT_DATA_ALL | HIT_DATA_MATERIALS))                                                                   \
             launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_ALL | HIT_DATA_MATERIALS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \
         else if (hit == (HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS))                                           \
             launchMaybePooled(wpt_pathtrace_large<(F), OCC, ORDERED, HIT_DATA_RECORDS | HIT_DATA_HOTSPOTS | HIT_DATA_MATERIALS>, args, grid, LDS_BYTES_PER_CU, stream, WG_LARGE); \

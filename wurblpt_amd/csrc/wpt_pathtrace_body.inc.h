@@ -200,6 +200,13 @@
                         ldsScene[mp.at + i] = from[i];
                 }
             }
+            if constexpr ((HIT & HIT_DATA_LAUNCH) != 0) {
+                /* the launch record in front of the cold words (wpt_lds_places.h; the host launches this kernel only where the
+                 * scene ends in front of it): four lanes write a quadword each, and the origin is evaluated here, once */
+                if (threadIdx.x < LAUNCH_RECORD_QUADS)
+                    ldsScene[LAUNCH_RECORD_AT + threadIdx.x] = launchRecordQuad(threadIdx.x, args.cam, args.par, cameraOriginAtRest(args.cam), args.invWidth,
+                            args.invHeight, args.invSamplesSqrt, args.samplesSqrt);
+            }
         }
     }
     __syncthreads();
@@ -241,6 +248,13 @@
     fa.invSamplesSqrt = args.invSamplesSqrt;
     if constexpr (hasShutter(F))
         fa.shutter = args.shutter;
+    /* HIT_DATA_LAUNCH: the new-sample block reads the launch's constants from the record the prologue has left in LDS (wpt_blocks.h) */
+    const auto launch = [&]() {
+        if constexpr ((HIT & HIT_DATA_LAUNCH) != 0)
+            return LaunchRecordInLds{ ldsScene + LAUNCH_RECORD_AT };
+        else
+            return NoLaunchConstants{};
+    }();
 
     /* ---- per-lane state: the pixel's path (wpt_blocks.h; its cold words in LDS) and the traversal registers ---- */
     std::conditional_t<ADAPTIVE, PathLdsSum<WG>, PathLds<WG>> ps;
@@ -824,7 +838,7 @@
                     /* the lane's unit ends where the pixel's next row of strata is the next unit's first */
                     const uint32_t g = unit >> SLICE_SLOT_BITS;
                     const uint32_t rowEnd = (g + 1) * sliceRows < args.samplesSqrt ? (g + 1) * sliceRows : args.samplesSqrt;
-                    next = (ps.getW(SLOT_ACC) >> 16) >= rowEnd ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv);
+                    next = (ps.getW(SLOT_ACC) >> 16) >= rowEnd ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv, launch);
                     if (next == NEXT_DONE && rowEnd < args.samplesSqrt) {
                         /* not the pixel's last: leave generator and sum behind, then say so.  Whoever drew the next unit before
                          * this moment has passed it by: then it is this lane's, which has the pixel's state where it is */
@@ -866,7 +880,7 @@
                     else
                         next = blockNewFrom<F, false>(fa, args.views.cams[view], ps, sv);
                 } else {
-                    next = passEnds ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv);
+                    next = passEnds ? (int)NEXT_DONE : blockNew<F>(fa, ps, sv, launch);
                 }
                 sec<COUNT>(lc, SEC_PIXEL_DONE, next == NEXT_DONE);
                 if (next == NEXT_DONE) {

@@ -53,6 +53,14 @@ WPT_D f4 mul(f4 a, f4 b) { return mk4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w
 WPT_D f4 scl(float s, f4 a) { return mk4(s * a.x, s * a.y, s * a.z, s * a.w); }
 WPT_D f4 sclr(f4 a, float s) { return mk4(a.x * s, a.y * s, a.z * s, a.w * s); }
 WPT_D f4 divs(f4 a, float s) { return mk4(a.x / s, a.y / s, a.z / s, a.w / s); }
+WPT_D f3 cross(f3 v, f3 w) { return mk3(v.y * w.z - v.z * w.y, v.z * w.x - v.x * w.z, v.x * w.y - v.y * w.x); }
+/* quaternion (x, y, z, w) rotates v, gvm.hpp:1713-1720 */
+WPT_D f3 quatRotate(const float* q, f3 v)
+{
+    f3 s = mk3(q[0], q[1], q[2]);
+    f3 t = scl(2.0f, cross(s, v));
+    return add(add(v, scl(q[3], t)), cross(s, t));
+}
 WPT_D float comp(f3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
 WPT_D float comp(f4 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : (i == 2 ? a.z : a.w)); }
 

@@ -813,6 +813,11 @@ def kernel_materials_in_lds():
     return bool(lib().wpt_kernel_materials_in_lds())
 
 
+def kernel_launch_record():
+    """wpt_kernel_launch_record: did the most recent render call's kernel read the launch's constants from a record in LDS?"""
+    return bool(lib().wpt_kernel_launch_record())
+
+
 def material_places(node_count, tri_count, material_count, behind_corners, instance_count, hotspot_count):
     """wpt_material_places: (read by LDS address?, first quadword, quadwords of the scene) for a launch in the large form"""
     at, quads = C.c_uint32(0), C.c_uint32(0)
